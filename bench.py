@@ -9,10 +9,24 @@ raygen -> [trace, shade, resolve]* -> splat -> film reduce -> develop), scene an
 already resident in HBM.  value = W*H*spp / seconds / 1e6 (Mpaths/s), whole job over all
 ranks.  The image is fixed and sharded by pixel rows => "strong" scaling (BASELINE.json:
 "1M-tri scene 512^2 x 256 spp, 1/2/4/8 GPU"); the row bands are rebalanced by measured
-per-rank time over the first three frames.  After the timed forward steps the PRB adjoint
-(RBIntegrator.render_backward: weight pass + primal pass + adjoint replay) is timed the same
-way on the TEXTURED variant of the scene (bitmap albedo: texel gradient atomics) with
-emitter gradients on, and reported in `prb_adjoint`.  rank 0 prints ONE JSON line.
+per-rank time over the first three frames.  rank 0 prints ONE JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line; everything else the
+benchmark measures runs only with --full (its fields are null otherwise):
+  prb_adjoint   the PRB adjoint (RBIntegrator.render_backward: weight pass + primal pass +
+                adjoint replay) timed the same way on the TEXTURED variant of the scene (bitmap
+                albedo: texel gradient atomics) with emitter gradients on;
+  secondary     the flattened 1M-triangle scene (instanced1m only);
+  roofline      per-kernel HIP-event breakdown over extra profiled frames, roofline of the
+                dominant kernel, committed PMC summaries;
+  cpu_baseline  the CPU oracle on the same scene;
+  loop          (c4_loop / vertex_loop) kernel share, GPU-busy trace, params.update() cost, plain
+                primal + backward step.
+--dump-outputs DIR writes what the last timed step returned to its caller as DIR/<name>.npy
+(float32; the forward image, or the loop's image, loss and updated parameter), right after the
+timed steps.  An array above its share of 64 MB is written as a fixed, seeded sample of its
+elements.  Inputs are fixed (seed 0 scenes and sampler seeds), so two builds can be compared
+output for output.
 
 Process layout.  Started without a torch.distributed environment, this file is a LAUNCHER:
   --gpus 1 : runs the measurement in one child process (`--worker`); a child killed by a
@@ -57,6 +71,9 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--retry-on-signal", action="store_true", help="re-run a worker killed by a signal even when it died after the preflight (off: such a crash is reported, not retried)")
     ap.add_argument("--no-secondary", action="store_true", help="skip the secondary forward workload (flat1m: the 64 MB-BVH variant of the scene)")
+    ap.add_argument("--full", action="store_true", help="also run the measurements beyond the headline figure: PRB adjoint, secondary workload, "
+                    "per-kernel breakdown and roofline, CPU baseline, loop details (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy (float32, at most 64 MB in all)")
     ap.add_argument("--worker", action="store_true", help="(internal) this process measures; see the module docstring")
     return ap.parse_args(argv)
 
@@ -92,6 +109,28 @@ def algorithmic_bytes(kernel, stats, accel, launches, overlapped=False, shading_
     if kernel == "raygen":
         return p * (32 + 16)
     return p * 16
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays):
+    """arrays: {name: tensor or array} -> directory/<name>.npy in float32 (float64 stays float64).  Every array gets an equal share of
+    DUMP_BYTES; a larger one is written as a sample of its flattened elements at fixed indices (seed 0, sorted), the same from run to run"""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    share = DUMP_BYTES // max(1, len(arrays))
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.asarray(a)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        cap = share // a.itemsize
+        if a.size > cap:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, cap, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(directory, name + ".npy"), a)
+    log("outputs written to %s: %s" % (directory, ", ".join(sorted(arrays))))
 
 
 # --------------------------------------------------------------------------------------------- launcher
@@ -265,6 +304,7 @@ def optimisation_loop(args, mi, torch, timed, sync_barrier, world, rank):
     params.update()
     opt = torch.optim.Adam([params[key]], lr=(0.01 if args.workload == "c4_loop" else 1e-4))
     it = [0]
+    last = {}              # the latest step's image and loss: --dump-outputs
 
     def step():
         opt.zero_grad(set_to_none=True)
@@ -274,12 +314,25 @@ def optimisation_loop(args, mi, torch, timed, sync_barrier, world, rank):
         opt.step()
         params.update()
         it[0] += 1
+        last["image"] = img; last["loss"] = loss
 
     log("first step (workspace allocation, code object load)")
     step(); sync_barrier()
     log("loop: %d warmup + %d timed steps" % (args.warmup, args.steps))
     dt = timed(step, args.steps, args.warmup)
     ms = dt / args.steps * 1e3
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"image": last["image"], "loss": last["loss"], "parameter": params[key]})
+    last.clear()
+    out = {"metric": "optimisation steps/s: render -> loss -> backward -> Adam -> params.update() (BASELINE config 4 loop)" if args.workload == "c4_loop"
+                     else "optimisation steps/s over vertex positions (device accel refit per step)",
+           "value": round(args.steps / dt, 3), "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
+           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+           "config": {"workload": what, "parameter": key, "parameter_values": int(params[key].numel()), "optimizer": "torch.optim.Adam"}, "loop": None}
+    if not args.full:
+        print(json.dumps(out)); sys.stdout.flush()
+        log("done")
+        return
     # kernel time of the library per step: HIP events around every launch (forward render = 1 frame, backward = 1 frame)
     integ.set_profiling(True)
     n_prof = max(2, min(args.steps, 5))
@@ -355,11 +408,7 @@ def optimisation_loop(args, mi, torch, timed, sync_barrier, world, rank):
     dt_plain = timed(plain, max(2, min(args.steps, 5)), 1)
     integ.shape_gradients = saved
     plain_ms = dt_plain / max(2, min(args.steps, 5)) * 1e3
-    out = {"metric": "optimisation steps/s: render -> loss -> backward -> Adam -> params.update() (BASELINE config 4 loop)" if args.workload == "c4_loop"
-                     else "optimisation steps/s over vertex positions (device accel refit per step)",
-           "value": round(args.steps / dt, 3), "unit": "steps/s", "n_gpus": 1, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3),
-           "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-           "config": {"workload": what, "parameter": key, "parameter_values": int(params[key].numel()), "optimizer": "torch.optim.Adam"},
+    out.update({
            # frames too large for the shadow-ray overlap run as two half-jobs on two streams (har_render): their kernels overlap in time, the sum of the
            # launch durations is then no longer a time and `outside_kernels` is left out -- profiles/rNN_kernel_trace_stats_vertex_loop.txt holds the step's
            # GPU-idle time from the union of the kernel intervals of a rocprofv3 trace (tools/rocpd_summary.py --busy)
@@ -368,7 +417,7 @@ def optimisation_loop(args, mi, torch, timed, sync_barrier, world, rank):
                     "outside_kernels_share": (round(busy["outside_library_kernels_ms_per_step"] / ms, 4) if busy and "outside_library_kernels_ms_per_step" in busy else (round((ms - kernel_ms) / ms, 4) if kernel_ms <= ms else None)), "loop_minus_plain_ms": round(ms - plain_ms, 3), "gpu_busy": busy, "params_update_ms": round(update_ms, 4), "params_update_host_enqueue_ms": round(update_host_ms, 4), "params_update_no_change_ms": round(update_nochange_ms, 4),
                     "plain_primal_plus_backward_ms": round(plain_ms, 3), "loop_over_plain": round(ms / plain_ms, 3),
                     "mpaths_per_s_primal_plus_adjoint": round(res * res * spp / (ms / 1e3) / 1e6, 2),
-                    "kernel_ms_per_frame": {k: round(v[0], 3) for k, v in timing.items() if k != "frames"}, "frames_per_step": frames / n_prof}}
+                    "kernel_ms_per_frame": {k: round(v[0], 3) for k, v in timing.items() if k != "frames"}, "frames_per_step": frames / n_prof}})
     if args.workload == "vertex_loop":
         try:
             out["loop"]["accel"] = dict(scene.refit_info(), device_resident_updates=bool(getattr(scene, "_stale_meshes", None)), accel=scene.accel_info())
@@ -376,6 +425,185 @@ def optimisation_loop(args, mi, torch, timed, sync_barrier, world, rank):
             out["loop"]["accel"] = {"note": str(e)[:200], "rebuilds": getattr(scene, "accel_rebuilds", 0)}
     print(json.dumps(out)); sys.stdout.flush()
     log("done")
+
+
+def forward_breakdown(args, scene, integ, accel, fwd, sync_barrier, world, value, ms_per_step):
+    """--full: per-kernel HIP events over a few extra frames right after the timed region, and the roofline of the dominant kernel.
+    Returns (roofline, stats), the counters read after the profiled frames"""
+    prof_frames = max(2, min(args.steps, 5))
+    integ.set_profiling(True)
+    for _ in range(prof_frames):
+        fwd()
+    sync_barrier()
+    timing = integ.timing()            # per-kernel HIP-event durations, average per frame over the profiled frames of this rank
+    integ.set_profiling(False)
+    stats = integ.stats()
+    log("forward done: %.1f Mpaths/s (%d timed frames, then %d profiled frames for the kernel breakdown)" % (value, args.steps, prof_frames))
+
+    # roofline of the dominant kernel, algorithmic bytes per SURVEY.md 8(d) (DESIGN.md section 3):
+    #   trace_closest: 56 B/ray (32 B ray in + 24 B hit out) + unique accel bytes once per launch
+    #   resolve: 33 B/shadow ray + accel ; shade: state in/out + hit + gathers ; raygen/splat: 152 + 16 B/path
+    kern_ms = {k: v[0] for k, v in timing.items() if k != "frames"}
+    frames_profiled = int(timing["frames"][0])
+    dominant = max(("trace_closest", "shade", "resolve", "splat", "raygen"), key=lambda k: kern_ms[k])
+    launches = max(timing[dominant][1], 1)
+    # jobs of at most 2^25 lanes per rank (N > 1) run bounce b's shadow rays on a second stream NEXT TO bounce b + 1's closest-hit rays (har_capi.hip overlap_applies):
+    # the interval the trace class times then holds both traversal kernels, so its bytes are the bytes of both
+    overlapped = stats["shadow_rays"] > 0 and kern_ms["resolve"] < 0.05 * kern_ms["trace_closest"]
+    alg_bytes = algorithmic_bytes(dominant, stats, accel, launches, overlapped=overlapped, shading_bytes=shading_geometry_bytes(scene))
+    achieved = alg_bytes / 1e9 / (kern_ms[dominant] / 1e3) if kern_ms[dominant] > 0 else 0.0
+    # HBM traffic from the committed PMC passes (separate FETCH_SIZE / WRITE_SIZE runs of this command, tools/gpu_profile.sh ... mem):
+    # bytes = (FETCH_SIZE x 2 [gfx950 correction, MI355X_MICROARCH.md "HBM"] + WRITE_SIZE) KiB x 1024; per launch for the dominant kernel,
+    # summed over all kernels of a frame for `frame_traffic`.  Only valid for the launch shape it was collected at (N = 1, 512^2 x 256).
+    traffic = frame_traffic = traffic_src = None
+    bound_actual = None
+    profile_check = None
+    if args.res == 512 and args.spp == 256 and world == 1 and not args.chunk:
+        prof, traffic_src = load_profile("traffic", args.workload)
+        rec = kernel_record(prof, dominant)
+        # a committed profile is only quoted when it describes THIS build's launch sequence: same kernels, same launches per frame
+        profile_check = profile_matches_run(prof, timing)
+        if profile_check is not True:
+            rec = None
+        if rec and "FETCH_SIZE" in rec["counters"] and "WRITE_SIZE" in rec["counters"]:
+            f, w = rec["counters"]["FETCH_SIZE"], rec["counters"]["WRITE_SIZE"]
+            traffic = round((2.0 * f["sum"] / f["dispatches"] + w["sum"] / w["dispatches"]) * 1024.0)
+            # whole frame: every kernel's FETCH x 2 + WRITE of the profiled run, divided by the frames that run rendered (= raygen dispatches)
+            rg = kernel_record(prof, "raygen")
+            frames_prof = max(1, int(rg["counters"]["FETCH_SIZE"]["dispatches"])) if rg else 1
+            tot = 0.0
+            for r in prof.values():
+                c = r.get("counters", {})
+                if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
+                    tot += (2.0 * c["FETCH_SIZE"]["sum"] + c["WRITE_SIZE"]["sum"]) * 1024.0
+            tot /= frames_prof
+            frame_traffic = {"bytes_per_frame": round(tot), "GBs": round(tot / 1e9 / (ms_per_step / 1e3), 1),
+                             "frac_of_peak": round(tot / 1e9 / (ms_per_step / 1e3) / HBM_PEAK_GBS, 4), "source": "profiles/" + traffic_src}
+        sq, sq_src = load_profile("sq", args.workload)
+        rec = kernel_record(sq, dominant) if profile_matches_run(sq, timing) is True else None
+        if rec and "SQ_INSTS_VALU" in rec["counters"] and rec.get("total_ms"):
+            c = rec["counters"]
+            rays = stats["closest_rays"] if dominant == "trace_closest" else stats["shadow_rays"] if dominant == "resolve" else stats["vertices"]
+            frames_sq = max(1, int(c["SQ_INSTS_VALU"]["dispatches"]) // max(launches, 1))
+            # what the kernel is really bound by: wave64 VALU instructions issued (SQ_INSTS_VALU) x ~2.7 cycles per instruction (tools/ubench/valu_ubench,
+            # the fma / mul / add rate; conversions and min3 / max3 are slower) over the SIMD cycles of its launches (1024 SIMDs x 2.4 GHz x duration)
+            bound_actual = {"kind": "valu_issue",
+                            "valu_insts_per_64_rays": round(c["SQ_INSTS_VALU"]["sum"] / frames_sq / max(rays / 64.0, 1.0), 1),
+                            "valu_issue_frac_of_simd_cycles": round(c["SQ_INSTS_VALU"]["sum"] * 2.7 / (1024 * rec["total_ms"] * 1e-3 * 2.4e9), 3),
+                            "source": "profiles/" + sq_src}
+    # `bound`: what the committed counters say the dominant kernel is limited by ("valu_issue" for the traversal kernels); achieved / peak / frac stay the
+    # HBM figures the contract asks for (algorithmic bytes per launch over the measured launch duration against the 8 TB/s peak), repeated as `hbm_frac`
+    roofline = {"bound": (bound_actual["kind"] if bound_actual else "hbm"), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
+                "valu_issue_frac": (bound_actual["valu_issue_frac_of_simd_cycles"] if bound_actual else None), "kernel": dominant + ("+resolve (concurrent on two streams)" if dominant == "trace_closest" and overlapped else ""), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": ("profiles/" + traffic_src) if traffic is not None else None,
+                "algorithmic_bytes_per_launch": round(alg_bytes / launches),
+                "avg_launch_ms": round(kern_ms[dominant] / launches, 4), "launches": launches, "frames_averaged": frames_profiled,
+                "kernel_ms": {k: round(v, 3) for k, v in kern_ms.items()},
+                "bound_actual": bound_actual, "frame_traffic": frame_traffic,
+                "profile_check": ("ok: the committed profile's kernels and launches per frame equal this run's" if profile_check is True else profile_check)}
+    return roofline, stats
+
+
+def further_measurements(args, mi, torch, np, scene, timed, sync_barrier, world, rank, n_paths):
+    """--full: the PRB adjoint, the secondary forward workload and the CPU baseline.  Returns (prb, secondary, cpu)"""
+    # ---------------- PRB adjoint ----------------
+    prb = None
+    scene_p = None
+    if not args.no_prb:
+        log("PRB adjoint: building the textured scene")
+        scene_p = build_scene(mi, args, "prb")
+        integ_p = scene_p.integrator()
+        grad_in = torch.full((args.res, args.res, 3), 1.0 / (args.res * args.res * 3), device="cuda")
+
+        def bwd():
+            return mi.render_backward_distributed(scene_p, grad_in, integ_p, seed=1, spp=args.spp)
+
+        p_steps = max(1, min(args.steps, 5))
+        log("PRB adjoint: 1 warmup + %d timed steps" % p_steps)
+        dtp = timed(bwd, p_steps, 1)
+        pst = integ_p.stats()
+        prb = {"metric": "Mpaths/s prb adjoint (weight pass + primal + adjoint replay)",
+               "value": round(n_paths / (dtp / p_steps) / 1e6, 2), "ms_per_step": round(dtp / p_steps * 1e3, 2), "steps": p_steps,
+               "workload": "%s + 256x256 bitmap albedo on the `white` BSDF (walls + spheres), emitter_gradients=True" % args.workload,
+               "gradient_targets": {"texels": int(sum(int(np.prod(t.shape)) for t in scene_p.textures)), "constant_albedos": len(scene_p.bsdfs), "emitters": len(scene_p.emitters)},
+               "stats": {k: int(v) for k, v in pst.items()},
+               "stats_note": "counters of the adjoint replay: its ray queries are served by the replay cache (shadow_rays = 0 traced); the primal pass of the same step traces the rays"}
+        log("PRB adjoint done: %.1f Mpaths/s" % prb["value"])
+
+    # ---------------- secondary forward workload: the FLATTENED 1M-triangle scene (64 MB BVH instead of 0.65 MB: SURVEY.md 8(d)'s BVH-size stress) ----------------
+    secondary = None
+    if args.workload == "instanced1m" and not args.no_secondary and world == 1:
+        import copy
+        a2 = copy.copy(args); a2.workload = "flat1m"
+        log("secondary workload flat1m: building the scene + BVH")
+        scene2 = build_scene(mi, a2, "path")
+        integ2 = scene2.integrator()
+
+        def fwd2():
+            return mi.render_distributed(scene2, integ2, seed=0, spp=args.spp)
+
+        fwd2(); sync_barrier()
+        s_steps = max(1, min(args.steps, 5))
+        dt2 = timed(fwd2, s_steps, 1)
+        integ2.set_profiling(True)
+        for _ in range(2):
+            fwd2()
+        sync_barrier()
+        t2 = integ2.timing(); integ2.set_profiling(False)
+        st2 = integ2.stats(); acc2 = scene2.accel_info()
+        l2 = max(t2["trace_closest"][1], 1)
+        ach2 = (st2["closest_rays"] * 56 + acc2["bytes"] * l2) / 1e9 / (t2["trace_closest"][0] / 1e3)
+        secondary = {"workload": "flat1m %dx%dx%dspp (flattened: unique triangles, %.0f MB BVH)" % (args.res, args.res, args.spp, acc2["bytes"] / 1e6),
+                     "value": round(n_paths / (dt2 / s_steps) / 1e6, 2), "unit": "Mpaths/s", "ms_per_step": round(dt2 / s_steps * 1e3, 2), "steps": s_steps,
+                     "accel": acc2, "kernel_ms": {k: round(v[0], 3) for k, v in t2.items() if k != "frames"},
+                     "trace_closest_achieved_GBs": round(ach2, 2), "trace_closest_frac_of_hbm_peak": round(ach2 / HBM_PEAK_GBS, 5),
+                     "stats": {k: int(v) for k, v in st2.items()}}
+        log("secondary done: %.1f Mpaths/s" % secondary["value"])
+        del scene2, integ2
+
+    # ---------------- CPU baseline (oracle = CPU restatement of llvm_ad_rgb; rank 0, N = 1 only) ----------------
+    cpu = None
+    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+        from oracle import oracle as O
+        # threads = the cores this container may really use (affinity mask capped by its cgroup CPU quota: the GPU boxes show 256 logical CPUs behind a quota of
+        # 16, and 256 threads run at HALF the rate of 16 there -- profiles/r03_cpu_scaling.txt); `cores` in the line is this count
+        cores = max(1, int(O.lib().orc_default_threads()))
+        log("CPU baseline: oracle on %d host threads of %d logical CPUs (forward)" % (cores, os.cpu_count() or 1))
+        if args.workload in ("instanced1m", "flat1m"):      # the oracle's own lowering of the scene description (independent of the product's host code)
+            sd_o, sensor = O.benchmark_spheres_scene(args.res, args.res, flatten=(args.workload == "flat1m"))
+            osc = O.OracleScene(sd_o)
+        else:
+            osc, sensor = O.scene_from_product(scene)
+        t0 = time.perf_counter()
+        _, st = osc.render_path(sensor, seed=0, spp=1, max_depth=args.max_depth, threads=cores)
+        probe = time.perf_counter() - t0
+        budget = args.cpu_seconds * (0.6 if scene_p is not None else 1.0)
+        spp_cpu = int(max(1, min(64, budget / max(probe, 1e-3))))
+        t0 = time.perf_counter()
+        _, st = osc.render_path(sensor, seed=0, spp=spp_cpu, max_depth=args.max_depth, threads=cores)
+        el = time.perf_counter() - t0
+        cpu = {"value": round(st.paths / el / 1e6, 4), "unit": "Mpaths/s", "cores": cores, "logical_cpus": os.cpu_count() or 1, "kind": "port",
+               "note": "the oracle is a slow, readable restatement written as a CHECKER (%.0f us x thread per path in this run); it is NOT llvm_ad_rgb -- an Embree-backed llvm_ad_rgb on these cores would be one to two orders of magnitude faster; the ratio value / cpu_baseline.value bounds nothing" % (el * cores / max(st.paths, 1) * 1e6),
+               "sample": "%dx%dx%d spp of the same scene/seed (%.1f s); CPU restatement of llvm_ad_rgb (reference not installable)"
+                         % (args.res, args.res, spp_cpu, el)}
+        if scene_p is not None:
+            log("CPU baseline: oracle PRB backward")
+            if args.workload in ("instanced1m", "flat1m"):
+                sd_p, sensorp = O.benchmark_spheres_scene(args.res, args.res, flatten=(args.workload == "flat1m"), textured=True)
+                oscp = O.OracleScene(sd_p)
+            else:
+                oscp, sensorp = O.scene_from_product(scene_p)
+            g = np.full((args.res, args.res, 3), 1.0 / (args.res * args.res * 3), np.float32)
+            t0 = time.perf_counter()
+            oscp.render_prb_backward(sensorp, g, seed=1, spp=1, max_depth=args.max_depth, threads=cores)
+            probe = time.perf_counter() - t0
+            spp_p = int(max(1, min(32, args.cpu_seconds * 0.4 / max(probe, 1e-3))))
+            t0 = time.perf_counter()
+            oscp.render_prb_backward(sensorp, g, seed=1, spp=spp_p, max_depth=args.max_depth, threads=cores)
+            elp = time.perf_counter() - t0
+            cpu["prb_adjoint"] = {"value": round(args.res * args.res * spp_p / elp / 1e6, 4), "unit": "Mpaths/s",
+                                  "sample": "%dx%dx%d spp of the textured scene (%.1f s), render_prb_backward of the oracle" % (args.res, args.res, spp_p, elp)}
+    return prb, secondary, cpu
 
 
 def worker(args):
@@ -475,10 +703,14 @@ def worker(args):
     # replicas on device 0 -- k = 1 measures what the entry adds to har_render (nothing: same launches), k > 1 rehearses the bands + the reduce on one GPU
     group = mi.DeviceGroup(scene, devices=[0] * int(os.environ["HAR_BENCH_GROUP"])) if os.environ.get("HAR_BENCH_GROUP") and world == 1 else None
 
+    last = [None]          # what the latest frame returned to its caller (the developed image on rank 0): --dump-outputs
+
     def fwd():
         if group is not None:
-            return group.render(seed=0, spp=args.spp)
-        return mi.render_distributed(scene, integ, seed=0, spp=args.spp)
+            last[0] = group.render(seed=0, spp=args.spp)
+        else:
+            last[0] = mi.render_distributed(scene, integ, seed=0, spp=args.spp)
+        return last[0]
 
     log("first forward frame (workspace allocation, code object load)")
     fwd(); sync_barrier()
@@ -486,179 +718,20 @@ def worker(args):
     # HIP events on the launch stream, one per kernel launch, over the TIMED frames only (har_integrator_set_profiling restarts the statistics;
     # every frame records into its own event set, see include/hip_ad_rgb.h)
     # `value` comes from frames rendered WITHOUT the per-launch events; the per-kernel breakdown (HIP events on the launch stream, one per kernel launch,
-    # har_integrator_set_profiling) is taken over a few extra frames right after the timed region
+    # har_integrator_set_profiling) is taken over a few extra frames right after the timed region (--full)
     dt = timed(fwd, args.steps, args.warmup)
     ms_per_step = dt / args.steps * 1e3
     value = n_paths / (dt / args.steps) / 1e6
-    prof_frames = max(2, min(args.steps, 5))
-    integ.set_profiling(True)
-    for _ in range(prof_frames):
-        fwd()
-    sync_barrier()
-    timing = integ.timing()            # per-kernel HIP-event durations, average per frame over the profiled frames of this rank
-    integ.set_profiling(False)
-    stats = integ.stats()
-    log("forward done: %.1f Mpaths/s (%d timed frames, then %d profiled frames for the kernel breakdown)" % (value, args.steps, prof_frames))
-
-    # roofline of the dominant kernel, algorithmic bytes per SURVEY.md 8(d):
-    #   trace_closest: 56 B/ray (32 B ray in + 24 B hit out) + unique accel bytes once per launch
-    #   resolve: 33 B/shadow ray + accel ; shade: state in/out + hit + gathers ; raygen/splat: 152 + 16 B/path
-    kern_ms = {k: v[0] for k, v in timing.items() if k != "frames"}
-    frames_profiled = int(timing["frames"][0])
-    dominant = max(("trace_closest", "shade", "resolve", "splat", "raygen"), key=lambda k: kern_ms[k])
-    launches = max(timing[dominant][1], 1)
-    # jobs of at most 2^25 lanes per rank (N > 1) run bounce b's shadow rays on a second stream NEXT TO bounce b + 1's closest-hit rays (har_capi.hip overlap_applies):
-    # the interval the trace class times then holds both traversal kernels, so its bytes are the bytes of both
-    overlapped = stats["shadow_rays"] > 0 and kern_ms["resolve"] < 0.05 * kern_ms["trace_closest"]
-    alg_bytes = algorithmic_bytes(dominant, stats, accel, launches, overlapped=overlapped, shading_bytes=shading_geometry_bytes(scene))
-    achieved = alg_bytes / 1e9 / (kern_ms[dominant] / 1e3) if kern_ms[dominant] > 0 else 0.0
-    # HBM traffic from the committed PMC passes (separate FETCH_SIZE / WRITE_SIZE runs of this command, tools/gpu_profile.sh ... mem):
-    # bytes = (FETCH_SIZE x 2 [gfx950 correction, MI355X_MICROARCH.md "HBM"] + WRITE_SIZE) KiB x 1024; per launch for the dominant kernel,
-    # summed over all kernels of a frame for `frame_traffic`.  Only valid for the launch shape it was collected at (N = 1, 512^2 x 256).
-    traffic = frame_traffic = traffic_src = None
-    bound_actual = None
-    profile_check = None
-    if args.res == 512 and args.spp == 256 and world == 1 and not args.chunk:
-        prof, traffic_src = load_profile("traffic", args.workload)
-        rec = kernel_record(prof, dominant)
-        # a committed profile is only quoted when it describes THIS build's launch sequence: same kernels, same launches per frame
-        profile_check = profile_matches_run(prof, timing)
-        if profile_check is not True:
-            rec = None
-        if rec and "FETCH_SIZE" in rec["counters"] and "WRITE_SIZE" in rec["counters"]:
-            f, w = rec["counters"]["FETCH_SIZE"], rec["counters"]["WRITE_SIZE"]
-            traffic = round((2.0 * f["sum"] / f["dispatches"] + w["sum"] / w["dispatches"]) * 1024.0)
-            # whole frame: every kernel's FETCH x 2 + WRITE of the profiled run, divided by the frames that run rendered (= raygen dispatches)
-            rg = kernel_record(prof, "raygen")
-            frames_prof = max(1, int(rg["counters"]["FETCH_SIZE"]["dispatches"])) if rg else 1
-            tot = 0.0
-            for r in prof.values():
-                c = r.get("counters", {})
-                if "FETCH_SIZE" in c and "WRITE_SIZE" in c:
-                    tot += (2.0 * c["FETCH_SIZE"]["sum"] + c["WRITE_SIZE"]["sum"]) * 1024.0
-            tot /= frames_prof
-            frame_traffic = {"bytes_per_frame": round(tot), "GBs": round(tot / 1e9 / (ms_per_step / 1e3), 1),
-                             "frac_of_peak": round(tot / 1e9 / (ms_per_step / 1e3) / HBM_PEAK_GBS, 4), "source": "profiles/" + traffic_src}
-        sq, sq_src = load_profile("sq", args.workload)
-        rec = kernel_record(sq, dominant) if profile_matches_run(sq, timing) is True else None
-        if rec and "SQ_INSTS_VALU" in rec["counters"] and rec.get("total_ms"):
-            c = rec["counters"]
-            rays = stats["closest_rays"] if dominant == "trace_closest" else stats["shadow_rays"] if dominant == "resolve" else stats["vertices"]
-            frames_sq = max(1, int(c["SQ_INSTS_VALU"]["dispatches"]) // max(launches, 1))
-            # what the kernel is really bound by: wave64 VALU instructions issued (SQ_INSTS_VALU) x ~2.7 cycles per instruction (tools/ubench/valu_ubench,
-            # the fma / mul / add rate; conversions and min3 / max3 are slower) over the SIMD cycles of its launches (1024 SIMDs x 2.4 GHz x duration)
-            bound_actual = {"kind": "valu_issue",
-                            "valu_insts_per_64_rays": round(c["SQ_INSTS_VALU"]["sum"] / frames_sq / max(rays / 64.0, 1.0), 1),
-                            "valu_issue_frac_of_simd_cycles": round(c["SQ_INSTS_VALU"]["sum"] * 2.7 / (1024 * rec["total_ms"] * 1e-3 * 2.4e9), 3),
-                            "source": "profiles/" + sq_src}
-    # `bound`: what the committed counters say the dominant kernel is limited by ("valu_issue" for the traversal kernels); achieved / peak / frac stay the
-    # HBM figures the contract asks for (algorithmic bytes per launch over the measured launch duration against the 8 TB/s peak), repeated as `hbm_frac`
-    roofline = {"bound": (bound_actual["kind"] if bound_actual else "hbm"), "hbm_frac": round(achieved / HBM_PEAK_GBS, 5),
-                "valu_issue_frac": (bound_actual["valu_issue_frac_of_simd_cycles"] if bound_actual else None), "kernel": dominant + ("+resolve (concurrent on two streams)" if dominant == "trace_closest" and overlapped else ""), "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_source": ("profiles/" + traffic_src) if traffic is not None else None,
-                "algorithmic_bytes_per_launch": round(alg_bytes / launches),
-                "avg_launch_ms": round(kern_ms[dominant] / launches, 4), "launches": launches, "frames_averaged": frames_profiled,
-                "kernel_ms": {k: round(v, 3) for k, v in kern_ms.items()},
-                "bound_actual": bound_actual, "frame_traffic": frame_traffic,
-                "profile_check": ("ok: the committed profile's kernels and launches per frame equal this run's" if profile_check is True else profile_check)}
-
-    # ---------------- PRB adjoint ----------------
-    prb = None
-    scene_p = None
-    if not args.no_prb:
-        log("PRB adjoint: building the textured scene")
-        scene_p = build_scene(mi, args, "prb")
-        integ_p = scene_p.integrator()
-        grad_in = torch.full((args.res, args.res, 3), 1.0 / (args.res * args.res * 3), device="cuda")
-
-        def bwd():
-            return mi.render_backward_distributed(scene_p, grad_in, integ_p, seed=1, spp=args.spp)
-
-        p_steps = max(1, min(args.steps, 5))
-        log("PRB adjoint: 1 warmup + %d timed steps" % p_steps)
-        dtp = timed(bwd, p_steps, 1)
-        pst = integ_p.stats()
-        prb = {"metric": "Mpaths/s prb adjoint (weight pass + primal + adjoint replay)",
-               "value": round(n_paths / (dtp / p_steps) / 1e6, 2), "ms_per_step": round(dtp / p_steps * 1e3, 2), "steps": p_steps,
-               "workload": "%s + 256x256 bitmap albedo on the `white` BSDF (walls + spheres), emitter_gradients=True" % args.workload,
-               "gradient_targets": {"texels": int(sum(int(np.prod(t.shape)) for t in scene_p.textures)), "constant_albedos": len(scene_p.bsdfs), "emitters": len(scene_p.emitters)},
-               "stats": {k: int(v) for k, v in pst.items()},
-               "stats_note": "counters of the adjoint replay: its ray queries are served by the replay cache (shadow_rays = 0 traced); the primal pass of the same step traces the rays"}
-        log("PRB adjoint done: %.1f Mpaths/s" % prb["value"])
-
-    # ---------------- secondary forward workload: the FLATTENED 1M-triangle scene (64 MB BVH instead of 0.65 MB: SURVEY.md 8(d)'s BVH-size stress) ----------------
-    secondary = None
-    if args.workload == "instanced1m" and not args.no_secondary and world == 1:
-        import copy
-        a2 = copy.copy(args); a2.workload = "flat1m"
-        log("secondary workload flat1m: building the scene + BVH")
-        scene2 = build_scene(mi, a2, "path")
-        integ2 = scene2.integrator()
-
-        def fwd2():
-            return mi.render_distributed(scene2, integ2, seed=0, spp=args.spp)
-
-        fwd2(); sync_barrier()
-        s_steps = max(1, min(args.steps, 5))
-        dt2 = timed(fwd2, s_steps, 1)
-        integ2.set_profiling(True)
-        for _ in range(2):
-            fwd2()
-        sync_barrier()
-        t2 = integ2.timing(); integ2.set_profiling(False)
-        st2 = integ2.stats(); acc2 = scene2.accel_info()
-        l2 = max(t2["trace_closest"][1], 1)
-        ach2 = (st2["closest_rays"] * 56 + acc2["bytes"] * l2) / 1e9 / (t2["trace_closest"][0] / 1e3)
-        secondary = {"workload": "flat1m %dx%dx%dspp (flattened: unique triangles, %.0f MB BVH)" % (args.res, args.res, args.spp, acc2["bytes"] / 1e6),
-                     "value": round(n_paths / (dt2 / s_steps) / 1e6, 2), "unit": "Mpaths/s", "ms_per_step": round(dt2 / s_steps * 1e3, 2), "steps": s_steps,
-                     "accel": acc2, "kernel_ms": {k: round(v[0], 3) for k, v in t2.items() if k != "frames"},
-                     "trace_closest_achieved_GBs": round(ach2, 2), "trace_closest_frac_of_hbm_peak": round(ach2 / HBM_PEAK_GBS, 5),
-                     "stats": {k: int(v) for k, v in st2.items()}}
-        log("secondary done: %.1f Mpaths/s" % secondary["value"])
-        del scene2, integ2
-
-    # ---------------- CPU baseline (oracle = CPU restatement of llvm_ad_rgb; rank 0, N = 1 only) ----------------
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        from oracle import oracle as O
-        # threads = the cores this container may really use (affinity mask capped by its cgroup CPU quota: the GPU boxes show 256 logical CPUs behind a quota of
-        # 16, and 256 threads run at HALF the rate of 16 there -- profiles/r03_cpu_scaling.txt); `cores` in the line is this count
-        cores = max(1, int(O.lib().orc_default_threads()))
-        log("CPU baseline: oracle on %d host threads of %d logical CPUs (forward)" % (cores, os.cpu_count() or 1))
-        if args.workload in ("instanced1m", "flat1m"):      # the oracle's own lowering of the scene description (independent of the product's host code)
-            sd_o, sensor = O.benchmark_spheres_scene(args.res, args.res, flatten=(args.workload == "flat1m"))
-            osc = O.OracleScene(sd_o)
-        else:
-            osc, sensor = O.scene_from_product(scene)
-        t0 = time.perf_counter()
-        _, st = osc.render_path(sensor, seed=0, spp=1, max_depth=args.max_depth, threads=cores)
-        probe = time.perf_counter() - t0
-        budget = args.cpu_seconds * (0.6 if scene_p is not None else 1.0)
-        spp_cpu = int(max(1, min(64, budget / max(probe, 1e-3))))
-        t0 = time.perf_counter()
-        _, st = osc.render_path(sensor, seed=0, spp=spp_cpu, max_depth=args.max_depth, threads=cores)
-        el = time.perf_counter() - t0
-        cpu = {"value": round(st.paths / el / 1e6, 4), "unit": "Mpaths/s", "cores": cores, "logical_cpus": os.cpu_count() or 1, "kind": "port",
-               "note": "the oracle is a slow, readable restatement written as a CHECKER (%.0f us x thread per path in this run); it is NOT llvm_ad_rgb -- an Embree-backed llvm_ad_rgb on these cores would be one to two orders of magnitude faster; the ratio value / cpu_baseline.value bounds nothing" % (el * cores / max(st.paths, 1) * 1e6),
-               "sample": "%dx%dx%d spp of the same scene/seed (%.1f s); CPU restatement of llvm_ad_rgb (reference not installable)"
-                         % (args.res, args.res, spp_cpu, el)}
-        if scene_p is not None:
-            log("CPU baseline: oracle PRB backward")
-            if args.workload in ("instanced1m", "flat1m"):
-                sd_p, sensorp = O.benchmark_spheres_scene(args.res, args.res, flatten=(args.workload == "flat1m"), textured=True)
-                oscp = O.OracleScene(sd_p)
-            else:
-                oscp, sensorp = O.scene_from_product(scene_p)
-            g = np.full((args.res, args.res, 3), 1.0 / (args.res * args.res * 3), np.float32)
-            t0 = time.perf_counter()
-            oscp.render_prb_backward(sensorp, g, seed=1, spp=1, max_depth=args.max_depth, threads=cores)
-            probe = time.perf_counter() - t0
-            spp_p = int(max(1, min(32, args.cpu_seconds * 0.4 / max(probe, 1e-3))))
-            t0 = time.perf_counter()
-            oscp.render_prb_backward(sensorp, g, seed=1, spp=spp_p, max_depth=args.max_depth, threads=cores)
-            elp = time.perf_counter() - t0
-            cpu["prb_adjoint"] = {"value": round(args.res * args.res * spp_p / elp / 1e6, 4), "unit": "Mpaths/s",
-                                  "sample": "%dx%dx%d spp of the textured scene (%.1f s), render_prb_backward of the oracle" % (args.res, args.res, spp_p, elp)}
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"image": last[0]})
+    last[0] = None
+    roofline = prb = secondary = cpu = None
+    if args.full:
+        roofline, stats = forward_breakdown(args, scene, integ, accel, fwd, sync_barrier, world, value, ms_per_step)
+        prb, secondary, cpu = further_measurements(args, mi, torch, np, scene, timed, sync_barrier, world, rank, n_paths)
+    else:
+        stats = integ.stats()
+        log("forward done: %.1f Mpaths/s (%d timed frames)" % (value, args.steps))
 
     if rank == 0:
         out = {

@@ -3,7 +3,7 @@
 (`python tests/golden/make_golden.py`); the outputs are committed because neither
 /root/reference nor a real mitsuba install exists on the GPU box.
 
-Two kinds of fixture:
+Three kinds of fixture (`python tests/golden/make_golden.py reference_suite` writes the third alone):
 
 1. reference_kats.json -- known-answer vectors TRANSCRIBED from the reference's own test
    files under /root/reference (parsed, not retyped; each entry carries file:line).  These
@@ -14,6 +14,10 @@ Two kinds of fixture:
    inputs: forward images, a PRB texture gradient, ray-query results, sampler streams.  The
    `-m gpu` tests compare the HIP path against them (in addition to running the oracle
    live), and a CPU test checks the oracle still reproduces them (drift guard).
+
+3. reference_suite.json -- the backend calls and known-answer checks of a few of the reference's
+   own test functions (microfacet, Fresnel, discrete distribution), recorded while they run
+   against the oracle; tests/test_reference_suite_cpu.py replays them on both backends.
 """
 import json
 import os
@@ -227,7 +231,35 @@ def oracle_fixtures():
     return fx
 
 
+# the reference test functions tests/test_reference_suite_cpu.py replays (file -> names)
+REFERENCE_SUITE = {"src/render/tests/test_microfacet.py": ["test02_eval_pdf_beckmann", "test03_smith_g1_beckmann", "test04_sample_beckmann", "test03_smith_g1_ggx",
+                                                           "test05_sample_ggx"],
+                   "src/render/tests/test_fresnel.py": ["test01_fresnel", "test02_fresnel_polarized_vec", "test03_fresnel_conductor", "test04_snell"],
+                   "src/core/tests/test_distr_1d.py": ["test05_discr_sample", "test07_discr_leading_trailing_zeros"]}
+
+
+def record_reference_suite():
+    """reference_suite.json -- the backend calls and known-answer checks of the reference test functions above, recorded by running them
+    against the oracle through the stand-ins of tests/ref_shim (record_reference_tests)"""
+    from oracle import oracle as O
+    from tests.ref_shim import make_modules, record_reference_tests
+    mi, dr = make_modules("oracle", O=O)
+    out = {"_comment": "recorded by tests/golden/make_golden.py from the reference test-suite; do not edit by hand", "tests": {}}
+    for rel, names in REFERENCE_SUITE.items():
+        for name, rec in record_reference_tests(os.path.join(REF, rel), names, mi, dr).items():
+            rec["src"] = "%s::%s" % (rel, name)
+            out["tests"][name] = rec
+    with open(os.path.join(HERE, "reference_suite.json"), "w") as f:
+        json.dump(out, f, separators=(",", ":"))
+        f.write("\n")
+    return out
+
+
 if __name__ == "__main__":
+    if sys.argv[1:] == ["reference_suite"]:
+        r = record_reference_suite()
+        print("reference_suite.json:", {n: (len(t["calls"]), len(t["checks"]), t["untracked"]) for n, t in r["tests"].items()})
+        sys.exit(0)
     old = dict(np.load(os.path.join(HERE, "oracle_fixtures.npz"))) if os.path.exists(os.path.join(HERE, "oracle_fixtures.npz")) else {}
     k = transcribe_kats()
     print("reference_kats.json:", sorted(k.keys()))

@@ -159,3 +159,180 @@ def run_reference_tests(path, names, mi, dr, extra=None):
                 sys.modules.pop(k, None)
             else:
                 sys.modules[k] = v
+
+
+# ------------------------------------------------------------------------------------------------ recorded checks
+# tests/golden/reference_suite.json holds what the selected reference test functions ask of the backend, as data: every call into `mi.*` (its
+# arguments, float32 values as float) and every check of a call's output against a known answer (dr.allclose with the test's rtol / atol, or ==),
+# or of two calls' outputs against each other.  tests/golden/make_golden.py writes it by running the reference tests through `record_reference_tests`;
+# tests/test_reference_suite_cpu.py replays it through `replay_reference_checks` against either backend, without the reference tree.
+
+def _f32(x):
+    return [float(v) for v in np.asarray(x, np.float32).reshape(-1)]
+
+
+def call_backend(mi, spec):
+    """one recorded call -> {output name: float32 / int64 array}"""
+    fn, a = spec["fn"], spec["args"]
+    if fn.startswith("microfacet."):
+        md = mi.MicrofacetDistribution(a["type"], a["alpha_u"], a["alpha_v"], bool(a["sample_visible"]))
+        m = fn.split(".", 1)[1]
+        if m == "eval":
+            return {"value": md.eval(a["m"])}
+        if m == "pdf":
+            return {"value": md.pdf(a["wi"], a["m"])}
+        if m == "smith_g1":
+            return {"value": md.smith_g1(a["v"], a["m"])}
+        (m0, m1, m2), pdf = md.sample(a["wi"], a["u"])
+        return {"m0": m0, "m1": m1, "m2": m2, "pdf": pdf}
+    if fn == "fresnel":
+        c = np.asarray(a["cos_theta_i"], np.float32)
+        r = mi.fresnel(c if c.size > 1 else c.reshape(()), a["eta"])
+        return dict(zip(("F", "cos_theta_t", "eta_it", "eta_ti"), (np.asarray(v, np.float32).reshape(-1) for v in r)))
+    if fn == "fresnel_conductor":
+        c = np.asarray(a["cos_theta_i"], np.float32)
+        return {"value": np.asarray(mi.fresnel_conductor(c if c.size > 1 else c.reshape(()), complex(*a["eta"])), np.float32).reshape(-1)}
+    if fn.startswith("discrete."):
+        idx, reused, pmf = mi.DiscreteDistribution(a["pmf"])._run(a["values"])
+        return {"index": idx, "reused": reused, "pmf": pmf}
+    raise KeyError(fn)
+
+
+class _Out(np.ndarray):
+    """an output of a recorded call; arithmetic on it gives plain arrays, `==` against a known answer is recorded as a check"""
+    tag = None
+    recorder = None
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kw):
+        plain = [np.asarray(x) if isinstance(x, _Out) else x for x in inputs]
+        tagged = [x for x in inputs if isinstance(x, _Out) and x.tag is not None]
+        if ufunc is np.equal and method == "__call__" and len(tagged) == 1 and self.recorder is not None:
+            other = plain[1] if inputs[0] is tagged[0] else plain[0]
+            self.recorder.checks.append({"op": "equal", "actual": [list(tagged[0].tag)], "expected": np.asarray(other, np.float64).tolist()})
+        return getattr(ufunc, method)(*plain, **kw)
+
+
+class _Recorder:
+    def __init__(self):
+        self.calls = []; self.checks = []; self.untracked = 0
+
+    def out(self, spec, outputs):
+        """record the call; its outputs come back tagged with (call index, output name)"""
+        k = len(self.calls)
+        self.calls.append(spec)
+        res = {}
+        for name, v in outputs.items():
+            o = np.asarray(v).view(_Out); o.tag = (k, name); o.recorder = self
+            res[name] = o
+        return res
+
+    @staticmethod
+    def tags(x):
+        if isinstance(x, _Out) and x.tag is not None:
+            return [list(x.tag)]
+        if isinstance(x, (list, tuple)) and x and all(isinstance(e, _Out) and e.tag is not None for e in x):
+            return [list(e.tag) for e in x]
+        return None
+
+
+def record_reference_tests(path, names, mi, dr):
+    """run the named reference test functions with recording stand-ins over `mi`, `dr` (make_modules); returns
+    {test name: {"calls": [...], "checks": [...], "untracked": number of dr.allclose checks on derived values}}"""
+    out = {}
+    for name in names:
+        R = _Recorder()
+        rmi = types.ModuleType("mitsuba"); rmi.__dict__.update(mi.__dict__)
+        rdr = types.ModuleType("drjit"); rdr.__dict__.update(dr.__dict__)
+
+        class MicrofacetDistribution(mi.MicrofacetDistribution):
+            def _spec(self, method, **a):
+                return {"fn": "microfacet." + method, "args": dict({"type": int(self.t), "alpha_u": self.au, "alpha_v": self.av, "sample_visible": self.sv},
+                                                              **{k: np.asarray(v, np.float32).tolist() for k, v in a.items()})}
+
+            def eval(self, m):
+                s = self._spec("eval", m=m); return R.out(s, call_backend(mi, s))["value"]
+
+            def pdf(self, wi, m):
+                s = self._spec("pdf", wi=wi, m=m); return R.out(s, call_backend(mi, s))["value"]
+
+            def smith_g1(self, v, m):
+                s = self._spec("smith_g1", v=v, m=m); return R.out(s, call_backend(mi, s))["value"]
+
+            def sample(self, wi, u):
+                s = self._spec("sample", wi=wi, u=u); o = R.out(s, call_backend(mi, s))
+                return [o["m0"], o["m1"], o["m2"]], o["pdf"]
+        rmi.MicrofacetDistribution = MicrofacetDistribution
+
+        def fresnel(cos_theta_i, eta):
+            s = {"fn": "fresnel", "args": {"cos_theta_i": _f32(cos_theta_i), "eta": float(eta)}}
+            o = R.out(s, call_backend(mi, s))
+            r = tuple(o[k] for k in ("F", "cos_theta_t", "eta_it", "eta_ti"))
+            if np.ndim(cos_theta_i) == 0:
+                r = tuple(_retag(v.reshape(()), v) for v in r)
+            return r
+        rmi.fresnel = fresnel
+
+        def fresnel_conductor(cos_theta_i, eta):
+            e = complex(eta)
+            s = {"fn": "fresnel_conductor", "args": {"cos_theta_i": _f32(cos_theta_i), "eta": [e.real, e.imag]}}
+            v = R.out(s, call_backend(mi, s))["value"]
+            return _retag(v.reshape(()), v) if np.ndim(cos_theta_i) == 0 else v
+        rmi.fresnel_conductor = fresnel_conductor
+
+        class DiscreteDistribution(mi.DiscreteDistribution):
+            def _call(self, m, values):
+                s = {"fn": "discrete." + m, "args": {"pmf": _f32(self.pmf), "values": _f32(values)}}
+                return R.out(s, call_backend(mi, s))
+
+            def sample(self, values): return self._call("sample", values)["index"]
+            def sample_pmf(self, values): o = self._call("sample_pmf", values); return o["index"], o["pmf"]
+            def sample_reuse(self, values): o = self._call("sample_reuse", values); return o["index"], o["reused"]
+            def sample_reuse_pmf(self, values): o = self._call("sample_reuse_pmf", values); return o["index"], o["reused"], o["pmf"]
+        rmi.DiscreteDistribution = DiscreteDistribution
+
+        def allclose(a, b, rtol=1e-5, atol=1e-8):
+            ta, tb = R.tags(a), R.tags(b)
+            if ta and tb:
+                R.checks.append({"op": "allclose", "actual": ta, "other": tb, "rtol": rtol, "atol": atol})
+            elif ta or tb:
+                R.checks.append({"op": "allclose", "actual": ta or tb, "actual_first": bool(ta), "rtol": rtol, "atol": atol,
+                                 "expected": np.asarray(b if ta else a, np.float64).tolist()})
+            else:
+                R.untracked += 1
+            return dr.allclose(a, b, rtol=rtol, atol=atol)
+        rdr.allclose = allclose
+        assert run_reference_tests(path, [name], rmi, rdr) == [name]
+        out[name] = {"calls": R.calls, "checks": R.checks, "untracked": R.untracked}
+    return out
+
+
+def _retag(v, src):
+    v = np.asarray(v).view(_Out); v.tag = src.tag; v.recorder = src.recorder
+    return v
+
+
+def _gather(outputs, tags):
+    return np.stack([np.asarray(outputs[k][n], np.float64).reshape(-1) for k, n in tags]).reshape(-1)
+
+
+def replay_reference_checks(tests, names, mi):
+    """the recorded calls of each named test through this `mi` (make_modules), then every recorded check; returns the names replayed"""
+    ran = []
+    for name in names:
+        rec = tests[name]
+        outputs = [call_backend(mi, spec) for spec in rec["calls"]]
+        assert rec["checks"] or rec["untracked"], name
+        for i, c in enumerate(rec["checks"]):
+            actual = _gather(outputs, c["actual"])
+            what = "%s check %d (%s of %s)" % (name, i, c["op"], [rec["calls"][k]["fn"] for k, _ in c["actual"]])
+            if c["op"] == "equal":
+                assert np.array_equal(actual, np.asarray(c["expected"], np.float64).reshape(-1)), (what, actual, c["expected"])
+            elif "other" in c:
+                other = _gather(outputs, c["other"])
+                assert np.allclose(actual, other, rtol=c["rtol"], atol=c["atol"]), (what, actual, other)
+            else:
+                expected = np.asarray(c["expected"], np.float64).reshape(-1)
+                a, b = (actual, expected) if c["actual_first"] else (expected, actual)
+                assert np.allclose(a, b, rtol=c["rtol"], atol=c["atol"]), (what, actual, expected)
+        ran.append(name)
+    return ran

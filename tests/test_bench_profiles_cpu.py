@@ -73,3 +73,18 @@ def test_the_shade_model_is_within_1_3x_of_the_counter_measured_traffic():
     measured = sum((2.0 * r["counters"]["FETCH_SIZE"]["sum"] + r["counters"]["WRITE_SIZE"]["sum"]) * 1024.0 for k, r in prof.items() if "k_shade" in k) / frames
     model = bench.algorithmic_bytes("shade", line["stats"], line["config"]["accel"], HEADLINE_LAUNCHES["shade"], shading_bytes=96 * line["config"]["accel"]["triangles"])
     assert 1 / 1.3 <= model / measured <= 1.3, (model, measured)
+
+
+def test_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """--dump-outputs: float32 (float64 kept), every array within its share of the budget, a larger one sampled at the same indices on every run"""
+    import numpy as np
+    bench = _load(os.path.join(ROOT, "bench.py"), "bench_under_test")
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4096)
+    img = np.arange(40 * 40 * 3, dtype=np.float32).reshape(40, 40, 3)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"image": img, "loss": np.float64(0.5), "index": np.arange(5)})
+    a = np.load(tmp_path / "a" / "image.npy")
+    assert a.dtype == np.float32 and a.nbytes <= 4096 // 3 and np.array_equal(a, np.load(tmp_path / "b" / "image.npy"))
+    assert np.all(np.diff(a) > 0) and np.all(np.isin(a, img))
+    assert np.load(tmp_path / "a" / "loss.npy").dtype == np.float64
+    assert np.array_equal(np.load(tmp_path / "a" / "index.npy"), np.arange(5, dtype=np.float32))

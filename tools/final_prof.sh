@@ -1,8 +1,9 @@
+export OUT_ROOT=${OUT_ROOT:-out}      # where this script writes its logs and summaries
 cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
-mkdir -p gpurun_out/r03 gpurun_out/prof
-python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r03/bench_final.json 2> gpurun_out/r03/bench_final.err
-tail -3 gpurun_out/r03/bench_final.err
+mkdir -p $OUT_ROOT/r03 $OUT_ROOT/prof
+python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT_ROOT/r03/bench_final.json 2> $OUT_ROOT/r03/bench_final.err
+tail -3 $OUT_ROOT/r03/bench_final.err
 bash tools/gpu_profile.sh r03_instanced1m kt mem sq -- --workload instanced1m
 # PRB step (record tape, default build)
 cat > /tmp/prb_only.py <<'PY'
@@ -19,13 +20,13 @@ for _ in range(3):
 torch.cuda.synchronize()
 PY
 D=/tmp/prof_prb_final; rm -rf $D
-rocprofv3 --kernel-trace --stats -d $D -o r -- python /tmp/prb_only.py > gpurun_out/prof/r03_prb_final_kt.log 2>&1
-python tools/rocpd_summary.py $(find $D -name '*.db') > gpurun_out/prof/r03_prb_final_kt.txt 2>&1
-head -16 gpurun_out/prof/r03_prb_final_kt.txt
-head -12 gpurun_out/prof/r03_instanced1m_kt.txt
-python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > gpurun_out/r03/bench_final2.json 2> gpurun_out/r03/bench_final2.err
+rocprofv3 --kernel-trace --stats -d $D -o r -- python /tmp/prb_only.py > $OUT_ROOT/prof/r03_prb_final_kt.log 2>&1
+python tools/rocpd_summary.py $(find $D -name '*.db') > $OUT_ROOT/prof/r03_prb_final_kt.txt 2>&1
+head -16 $OUT_ROOT/prof/r03_prb_final_kt.txt
+head -12 $OUT_ROOT/prof/r03_instanced1m_kt.txt
+python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT_ROOT/r03/bench_final2.json 2> $OUT_ROOT/r03/bench_final2.err
 python -c "
 import json
-for f in ('gpurun_out/r03/bench_final.json','gpurun_out/r03/bench_final2.json'):
+for f in ('$OUT_ROOT/r03/bench_final.json','$OUT_ROOT/r03/bench_final2.json'):
     d=json.load(open(f)); print(d["value"], d["ms_per_step"], d["roofline"]["frac"], d["roofline"]["profile_check"], (d.get("prb_adjoint") or {}).get("value"), (d.get("secondary") or {}).get("value"), (d.get("cpu_baseline") or {}).get("value"))
 "

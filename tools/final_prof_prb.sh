@@ -1,6 +1,7 @@
+export OUT_ROOT=${OUT_ROOT:-out}      # where this script writes its logs and summaries
 cd ${GRAFT_REPO_ROOT:-.}
 export TMPDIR=/tmp
-mkdir -p gpurun_out/r03 gpurun_out/prof
+mkdir -p $OUT_ROOT/r03 $OUT_ROOT/prof
 cat > /tmp/prb_only.py <<'PY'
 import sys, torch
 sys.path.insert(0, ".")
@@ -15,10 +16,10 @@ for _ in range(3):
 torch.cuda.synchronize()
 PY
 D=/tmp/prof_prb_final; rm -rf $D
-rocprofv3 --kernel-trace --stats -d $D -o r -- python /tmp/prb_only.py > gpurun_out/prof/r03_prb_final_kt.log 2>&1
-python tools/rocpd_summary.py $(find $D -name '*.db') > gpurun_out/prof/r03_prb_final_kt.txt 2>&1
-head -12 gpurun_out/prof/r03_prb_final_kt.txt
-python bench.py --workload materials1m --steps 10 --warmup 3 --no-cpu-baseline --no-prb --no-secondary > gpurun_out/r03/bench_materials4.json 2> /dev/null
+rocprofv3 --kernel-trace --stats -d $D -o r -- python /tmp/prb_only.py > $OUT_ROOT/prof/r03_prb_final_kt.log 2>&1
+python tools/rocpd_summary.py $(find $D -name '*.db') > $OUT_ROOT/prof/r03_prb_final_kt.txt 2>&1
+head -12 $OUT_ROOT/prof/r03_prb_final_kt.txt
+python bench.py --full --workload materials1m --steps 10 --warmup 3 --no-cpu-baseline --no-prb --no-secondary > $OUT_ROOT/r03/bench_materials4.json 2> /dev/null
 python -c "
 import json
-d=json.loads(open('gpurun_out/r03/bench_materials4.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
+d=json.loads(open('$OUT_ROOT/r03/bench_materials4.json').read().strip().splitlines()[-1]); print(d['value'], d['ms_per_step'], d['roofline']['kernel_ms'])"
