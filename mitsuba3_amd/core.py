@@ -1222,17 +1222,21 @@ class Integrator:
             h = C.c_void_p()
             check(lib().har_integrator_create(0 if self.type == 'path' else 1, self.max_depth, self.rr_depth, self.chunk_lanes, C.byref(h)))
             self._h = h
-            if not self.replay_cache:
-                check(lib().har_integrator_set_replay_cache(h, 0))
-            if self.material_queues:
-                check(lib().har_integrator_set_material_queues(h, 1))
-            if self.packet_tracing is not None:
-                check(lib().har_integrator_set_packet_tracing(h, 1 if self.packet_tracing else 0))
-            if self.hide_emitters:
-                check(lib().har_integrator_set_hide_emitters(h, 1))
-            if self.samples_per_pass is not None:
-                check(lib().har_integrator_set_samples_per_pass(h, self.samples_per_pass))
+            self._apply_settings(h)
         return self._h
+
+    def _apply_settings(self, h):
+        """the settings har_integrator_create does not take, on a library integrator `h` (this one's, or a DeviceGroup replica's)"""
+        if not self.replay_cache:
+            check(lib().har_integrator_set_replay_cache(h, 0))
+        if self.material_queues:
+            check(lib().har_integrator_set_material_queues(h, 1))
+        if self.packet_tracing is not None:
+            check(lib().har_integrator_set_packet_tracing(h, 1 if self.packet_tracing else 0))
+        if self.hide_emitters:
+            check(lib().har_integrator_set_hide_emitters(h, 1))
+        if self.samples_per_pass is not None:
+            check(lib().har_integrator_set_samples_per_pass(h, self.samples_per_pass))
 
     def pass_layout(self, sensor, spp=0):
         """(spp_per_pass, n_passes) of a render() with `spp` samples (integrator.cpp:173-183,276-294)"""
@@ -1381,7 +1385,6 @@ class Integrator:
         g_tex = [torch.zeros(tuple(t.shape), dtype=torch.float32, device=dev) for t in scene.textures]
         ptrs = (C.c_void_p * max(1, len(g_tex)))(*[t.data_ptr() for t in g_tex])
         g_emit = torch.zeros((max(1, len(scene.emitters)), 3), dtype=torch.float32, device=dev)
-        check(lib().har_integrator_set_grad_emitters(self._handle(), _ptr(g_emit) if self.emitter_gradients else None))
         g_pos = {}; g_inst = None; inst_wanted = {}; rect_wanted = {}
         if self.shape_gradients:
             keys = scene._position_keys(); ikeys = scene._instance_keys()
@@ -1418,10 +1421,18 @@ class Integrator:
             check(lib().har_integrator_set_grad_positions(self._handle(), None, None))
             check(lib().har_integrator_set_grad_instances(self._handle(), None, None))
         g_extra = torch.zeros((max(1, len(scene.bsdfs)), 15), dtype=torch.float32, device=dev) if self.bsdf_parameter_gradients else None
-        check(lib().har_integrator_set_grad_bsdf_params(self._handle(), _ptr(g_extra) if g_extra is not None else None))
-        check(lib().har_integrator_set_grad_light_texels(self._handle(), 1 if self.light_texel_gradients else 0))
-        check(lib().har_render_backward(scene._handle(), self._handle(), C.byref(sensor.har), _ptr(grad_in), _ptr(weight_film), sd, spp,
-                                        lb, le, _ptr(g_refl), ptrs, _stream()))
+        try:
+            check(lib().har_integrator_set_grad_emitters(self._handle(), _ptr(g_emit) if self.emitter_gradients else None))
+            check(lib().har_integrator_set_grad_bsdf_params(self._handle(), _ptr(g_extra) if g_extra is not None else None))
+            check(lib().har_integrator_set_grad_light_texels(self._handle(), 1 if self.light_texel_gradients else 0))
+            check(lib().har_render_backward(scene._handle(), self._handle(), C.byref(sensor.har), _ptr(grad_in), _ptr(weight_film), sd, spp,
+                                            lb, le, _ptr(g_refl), ptrs, _stream()))
+        finally:
+            # no pointer into this call's tensors and no switch of it outlives the call: the primal pass of a later mi.render reads all three (HAR_SHADE_EMITTER_GRADS,
+            # HAR_SHADE_LIGHT_TEXELS: extra shadow rays), and a forward render must not depend on what ran before it
+            check(lib().har_integrator_set_grad_emitters(self._handle(), None))
+            check(lib().har_integrator_set_grad_bsdf_params(self._handle(), None))
+            check(lib().har_integrator_set_grad_light_texels(self._handle(), 0))
         out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None)
         if g_extra is not None:
             for k, (what, b) in scene._bsdf_param_keys().items():
@@ -1717,13 +1728,26 @@ class Scene:
             self._stale_instances = False
 
     def _drop_handle(self, keep_geometry=True):
-        """the next render builds a new scene handle from the host mirrors: bring them up to date first (unless the handle is being dropped BECAUSE an update failed)"""
+        """the next render builds a new scene handle from the host mirrors: bring them up to date first.  When the handle is dropped BECAUSE an update failed
+        (keep_geometry=False), what the device-resident updates before the failing one wrote is still valid and is read back as well -- except vertex records that are
+        not finite (the update a late "not finite" reports): that mesh keeps its last valid mirror.  (Instances: the device keeps the old transform of a singular one.)"""
         if self._h is None:
             return
         if keep_geometry:
             self._sync_host_geometry()
         else:
-            getattr(self, "_stale_meshes", set()).clear(); self._stale_instances = False
+            for i in sorted(getattr(self, "_stale_meshes", ())):
+                V = np.array(self.meshes[i]["V"], np.float32)
+                if lib().har_scene_get_vertices(self._h, int(i), _fp(V), _stream()) == 0 and np.isfinite(V).all():
+                    self.meshes[i]["V"] = V
+            getattr(self, "_stale_meshes", set()).clear()
+            if getattr(self, "_stale_instances", False) and self.instances:
+                n = len(self.instances)
+                tw = np.zeros((n, 12), np.float32); to = np.zeros((n, 12), np.float32)
+                if lib().har_scene_get_instances(self._h, 0, n, _fp(tw), _fp(to), _stream()) == 0 and np.isfinite(tw).all() and np.isfinite(to).all():
+                    self.instances = [(self.instances[i][0], [float(x) for x in tw[i]], [float(x) for x in to[i]]) for i in range(n)]
+            self._stale_instances = False
+            self._update_failures = getattr(self, "_update_failures", 0) + 1       # (SceneParameters._changed_keys: keys it remembers as applied are looked at again)
         lib().har_scene_destroy(self._h); self._h = None
 
     # -- C ABI description
@@ -2016,6 +2040,25 @@ class Scene:
             e["to_world"] = tw.col_major_3x4(); e["normal"] = n; e["inv_area"] = ia.value
         self._drop_handle()
 
+    def _rect_frame(self, i, p):
+        """the 'to_world' of rectangle i whose corners (-1, -1), (1, -1), (-1, 1), (1, 1) -- har_shape_rectangle's vertex order -- are the four positions `p`: the first two
+        columns and the translation come from the corners; the third, which no corner reaches, is the unit normal of the new frame at the old column's length and
+        orientation (T * to_world for any T that maps the plane's normal to the new plane's normal at the same length: rigid motions, stretches within the plane)"""
+        p = np.asarray(p, np.float64).reshape(4, 3)
+        key = self.meshes[i]["key"] + ".to_world"
+        c = p.mean(axis=0); x = (p[1] - p[0] + p[3] - p[2]) / 4.0; y = (p[2] - p[0] + p[3] - p[1]) / 4.0
+        n = np.cross(x, y); nn = np.linalg.norm(n)
+        fit = np.stack([c - x - y, c + x - y, c - x + y, c + x + y])
+        if not nn > 0.0 or np.abs(fit - p).max() > 1e-5 * max(np.abs(p).max(), np.linalg.norm(x), np.linalg.norm(y)):
+            raise RuntimeError("%s.positions: the four vertices of a rectangle light must form a non-degenerate parallelogram (its sampling record is its frame); "
+                               "move it through '%s'" % (self.meshes[i]["key"], key))
+        old = self._rect_matrix(i).astype(np.float64)
+        z = old[:3, 2]
+        side = 1.0 if np.dot(np.cross(old[:3, 0], old[:3, 1]), z) >= 0.0 else -1.0
+        m4 = np.eye(4)
+        m4[:3, 0] = x; m4[:3, 1] = y; m4[:3, 2] = side * np.linalg.norm(z) * n / nn; m4[:3, 3] = c
+        return m4
+
     @_static_table
     def _instance_keys(self):
         """'<instance>.to_world' (4 x 4, Instance::traverse, instance.cpp:79-85)"""
@@ -2049,11 +2092,14 @@ class Scene:
         run of consecutive instances"""
         self._sync_host_geometry()          # other instances may have moved on the device since: the mirror is read and rewritten below
         recs = {}
-        for i, m4 in items:
-            m = np.asarray(m4, np.float64).reshape(4, 4); inv = np.linalg.inv(m)
-            tw = _f32(m[:3, :].T.reshape(-1)); to = _f32(inv[:3, :].T.reshape(-1))
+        for i, m4 in items:                 # every matrix is checked before the mirror takes any of them
+            m = np.asarray(m4, np.float64).reshape(4, 4)
+            if not np.isfinite(m).all() or np.linalg.det(m[:3, :3]) == 0.0:
+                raise RuntimeError("instance transform is singular or not finite")
+            inv = np.linalg.inv(m)
+            recs[int(i)] = (_f32(m[:3, :].T.reshape(-1)), _f32(inv[:3, :].T.reshape(-1)))
+        for i, (tw, to) in recs.items():
             self.instances[i] = (self.instances[i][0], [float(x) for x in tw], [float(x) for x in to])
-            recs[int(i)] = (tw, to)
         if self._h is None or not recs:
             return
         idx = sorted(recs); start = 0
@@ -2074,7 +2120,15 @@ class Scene:
         """params['<shape>.positions'] = ... (a host tensor / array) + params.update(): normals regenerated on the host, the BLAS refitted on the device
         (har_scene_update_vertices); CUDA tensors take _set_vertex_positions_device instead"""
         V = self.meshes[mesh]["V"]
-        V[:, :3] = np.asarray(positions, np.float32).reshape(V.shape[0], 3)
+        p = np.asarray(positions, np.float32).reshape(V.shape[0], 3)
+        if not np.isfinite(p).all():
+            raise RuntimeError("%s.positions: a vertex position is not finite" % self.meshes[mesh]["key"])
+        if self.meshes[mesh].get("rect") is not None and self.meshes[mesh]["emitter"] >= 0:
+            # a rectangle light samples its frame, not its triangles (Rectangle::sample_position): the frame follows the positions, and the vertex records and the
+            # sampling record are re-baked from it -- what '<rect>.to_world' reads back
+            self._set_rect_to_world(mesh, self._rect_frame(mesh, p))
+            return
+        V[:, :3] = p
         if self.meshes[mesh]["flags"] & 1:
             # Mesh::parameters_changed (mesh.cpp:876-878): pack(regenerate_normals = positions written and normals not) -> compute_normals (:1216-1267)
             F = np.ascontiguousarray(self.meshes[mesh]["F"])
@@ -2113,12 +2167,18 @@ class Scene:
         p = positions.detach().to(torch.float32).contiguous()
         if p.numel() != 3 * V.shape[0]:
             raise RuntimeError("positions: expected %d rows of 3 values" % V.shape[0])
+        if self.meshes[mesh]["emitter"] >= 0:
+            # the library refuses an emitter mesh before it writes anything (its sampling records are lowered from the positions): the host route, new scene included
+            self._set_vertex_positions(mesh, p.cpu().numpy())
+            return
         if not hasattr(self, "_stale_meshes"):
             self._stale_meshes = set()
-        self._stale_meshes.add(mesh)
         self.device_vertex_updates = getattr(self, "device_vertex_updates", 0) + 1
         self._keep_positions = p                  # alive until the kernels that read it were enqueued on this stream (they were: the call below enqueues them)
-        self._after_vertex_update(mesh, lib().har_scene_update_vertices_device(self._h, int(mesh), _ptr(p), _stream()))
+        rc = lib().har_scene_update_vertices_device(self._h, int(mesh), _ptr(p), _stream())
+        if rc in (0, 3):                          # (3: HAR_UPDATE_REBUILD_ADVISED) the device arrays hold the new positions, the mirror does not yet
+            self._stale_meshes.add(mesh)
+        self._after_vertex_update(mesh, rc)
 
     def refit_info(self):
         """(refits since the scene handle was created, cost figure of the last refit, its ratio to the first refit's, nodes)"""
@@ -2439,6 +2499,7 @@ class SceneParameters(dict):
                 key = k + "." + name
                 self[key] = torch.tensor(val, dtype=torch.float32 if "clip" in name or "shutter" in name else torch.int64, device=dev)
                 self._read_only.add(key)
+        self._failures_seen = getattr(scene, "_update_failures", 0)
         self._written = set()           # keys assigned since the last update() (SceneParameters.__setitem__ flags them in the reference, util.py)
         # the tensors above ARE the scene's values: recorded as applied, so that the first update() touches only what was written or stepped since (vertex positions on
         # the GPU are never compared -- a mesh is updated when its tensor's version counter moved, see _changed_keys)
@@ -2490,6 +2551,14 @@ class SceneParameters(dict):
         table = self._host_kinds()
         snap = self.__dict__.setdefault("_snapshot", {})
         seen = self.__dict__.setdefault("_seen", {})          # key -> (the tensor object, its version counter) at the last update()
+        fails = getattr(self.scene, "_update_failures", 0)
+        if self.__dict__.get("_failures_seen", 0) != fails:
+            # an update failed since the last call and took the scene handle with it: what the device held is in the mirrors as far as it was valid, so every geometry
+            # key is compared with its mirror again -- a value the device rejected late (not finite, singular) is not remembered as applied
+            for k, what, _ in table:
+                if what in ("pos", "inst"):
+                    seen.pop(k, None); snap.pop(k, None)
+            self._failures_seen = fails
         changed = set(k for k, _, _ in table if k in written or k not in snap)
         flags = []; names = []
         device_pos = set()
@@ -2735,6 +2804,10 @@ class DeviceGroup:
         check(lib().har_multi_create(C.byref(d), 0 if integrator.type == 'path' else 1, integrator.max_depth, integrator.rr_depth, integrator.chunk_lanes or 0,
                                      devs, len(self.devices), C.byref(h)))
         self._h = h
+        for k in range(len(self.devices)):          # every replica renders with the integrator's own settings (Integrator._handle)
+            _, it, dev = self.replica(k)
+            with _torch().cuda.device(dev):
+                integrator._apply_settings(it)
 
     def __del__(self):
         try:
@@ -2746,6 +2819,8 @@ class DeviceGroup:
     def render(self, sensor=0, seed=0, spp=0, develop=True):
         torch = _torch()
         s = self.scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+        if getattr(s.film(), "alpha", False):
+            raise RuntimeError("DeviceGroup.render(): the group's film has no alpha channel; an `rgba` film renders with render_distributed or mi.render")
         if spp:
             s.sampler().set_sample_count(spp)
         spp = s.sampler().sample_count()
@@ -2781,6 +2856,8 @@ class DeviceGroup:
             g_emit = torch.zeros((max(1, len(sc.emitters)), 3), dtype=torch.float32, device=dev) if self.integrator.emitter_gradients else None
             check(lib().har_multi_render_backward(self._h, C.byref(s.har), _ptr(g_in), (s.sampler().m_base_seed + int(seed)) & 0xffffffff, spp, _ptr(g_refl), ptrs,
                                                   _ptr(g_emit) if g_emit is not None else None, _stream()))
+        for k in range(len(self.devices)):          # the replicas keep no pointer into the group's gradient buffers: their next primal pass is a plain render
+            check(lib().har_integrator_set_grad_emitters(self.replica(k)[1], None))
         return sc._gradients(g_refl, g_tex, g_emit)
 
     def replica(self, k):

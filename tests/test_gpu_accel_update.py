@@ -146,8 +146,11 @@ def test_degraded_refit_advises_a_rebuild_and_emitter_meshes_get_a_new_scene(mi)
     # a mesh with an area emitter: its sampling records are lowered from the positions -> new scene, not a refit
     cb = mi.load_dict(mi.cornell_box()); mi.render(cb, spp=4, seed=0)
     pc = mi.traverse(cb)
-    pc["light.positions"] = pc["light.positions"] * 1.0; pc.update()
+    light = cb.emitters[cb.meshes[cb._position_keys()["light.positions"]]["emitter"]]
+    corner = np.asarray(light["to_world"], np.float32)[9:12].copy()
+    pc["light.positions"] = pc["light.positions"] + torch.tensor([0.1, -0.05, 0.08], device="cuda"); pc.update()
     assert cb._h is None
+    assert np.allclose(np.asarray(light["to_world"], np.float32)[9:12] - corner, [0.1, -0.05, 0.08], atol=1e-6)      # the light's sampling record moved with it
 
 
 def test_shape_optimisation_steps_keep_the_handle(mi):

@@ -351,7 +351,8 @@ def test_random_scene_options(mi, O, seed):
 
 
 def _perturb(mi, scene, params, rng, torch):
-    """new values for a random subset of the keys of mi.traverse(scene), of every kind an update path exists for; returns the list of keys written"""
+    """new values for a random subset of the keys of mi.traverse(scene), of every kind an update path exists for; returns {key written: a host copy of its value}"""
+    from tests.update_reference import final_values
     written = []
     pose = scene._pose_keys(); bsdfp = scene._bsdf_param_keys(); pos = scene._position_keys(); inst = scene._instance_keys(); colour = scene._param_keys(); rect = scene._rect_keys()
     for k in list(params.keys()):
@@ -367,8 +368,8 @@ def _perturb(mi, scene, params, rng, torch):
                 params[k] = new
         elif k in pos:
             m = pos[k]
-            if scene.meshes[m]["emitter"] >= 0:
-                continue
+            if scene.meshes[m]["emitter"] >= 0 and scene.meshes[m].get("rect") is not None:
+                continue                                          # (a rectangle light moves through its '<rect>.to_world' here)
             noise = torch.as_tensor(rng.normal(0.0, 0.004, tuple(v.shape)), dtype=v.dtype, device=v.device)
             params[k] = (v + noise) if rng.random() < 0.5 else (v + noise).cpu()          # device-resident and host update paths
         elif k in inst:
@@ -419,15 +420,19 @@ def _perturb(mi, scene, params, rng, torch):
         else:
             continue
         written.append(k)
-    return written
+    return final_values(params, written)
 
 
 @pytest.mark.parametrize("seed", _seeds("HAR_FUZZ_SEEDS3", 24))
 def test_random_parameter_updates(mi, O, seed):
     """params.update() after writing a random subset of mi.traverse(scene) -- colours and texels (device-to-device, in place or as new tensors), emitter radiances, vertex positions
-    (device-resident refit and the host path), instance transforms, alpha / eta / k, light placements and cones, sampling weights, the sensor's pose -- then a second round on
-    top: every render equals the oracle's render of the scene's host mirrors (device state == host state == what was written), forward and one backward call"""
+    (device-resident refit and the host path; emitter meshes included), instance transforms, alpha / eta / k, light placements and cones, sampling weights, the sensor's pose --
+    then a second round on top.  After each round: the render equals the oracle's render of the scene's host mirrors (device state == host state), every key written so far
+    reads back its last written value through a new mi.traverse (host state == what was written: update_reference.assert_values_kept), and the render equals the render of a
+    FRESH load with those values written before its first render, and the oracle's render of that fresh scene (update_reference.fresh_reference: a reference that is not
+    made from the scene under test); one backward call at the end"""
     import torch
+    from tests.update_reference import assert_values_kept, fresh_reference
     d, cfg = random_scene(mi, seed + 900)
     spp, md, rr = cfg["spp"], cfg["max_depth"], cfg["rr_depth"]
     d["integrator"] = {"type": "prb", "max_depth": md, "rr_depth": rr}
@@ -435,9 +440,18 @@ def test_random_parameter_updates(mi, O, seed):
     params = mi.traverse(scene)
     first = mi.render(scene, spp=spp, seed=seed).cpu().numpy()
     rng = np.random.default_rng(4000 + seed)
+    values = {}                                                     # every key written so far -> its last written value
     for rnd in range(2):
         written = _perturb(mi, scene, params, rng, torch)
         params.update()
+        rect = scene._rect_keys()
+        for k in written:                                           # a rectangle moved through its positions and through its to_world: the later write is its state
+            base = k.rsplit(".", 1)[0]
+            if k in rect:
+                values.pop(base + ".positions", None)
+            elif k.endswith(".positions") and base + ".to_world" in rect:
+                values.pop(base + ".to_world", None)
+        values.update(written)
         img = mi.render(scene, spp=spp, seed=seed).cpu().numpy()
         osc, sensor = O.scene_from_product(scene)
         ref, ost = osc.render_prb(sensor, seed=seed, spp=spp, max_depth=md, rr_depth=rr)
@@ -445,6 +459,13 @@ def test_random_parameter_updates(mi, O, seed):
         assert scene.integrator().stats()["vertices"] == ost.vertices, (rnd, written)
         if rnd == 0 and len(written) >= 3 and np.abs(first).max() > 0:                # (a sensor that sees nothing stays black)
             assert rel_l2(img, first) > 1e-4, written              # the update did change the picture
+        assert_values_kept(scene, values)
+        fresh = fresh_reference(d, values)
+        # (1e-5, not 1e-6: normals regenerated on the device differ from the host's by a few ulps, test_gpu_accel_update.py)
+        _compare("image after update round %d vs a fresh load" % rnd, img, mi.render(fresh, spp=spp, seed=seed).cpu().numpy(), 1e-5)
+        fosc, fsensor = O.scene_from_product(fresh)
+        fref, _ = fosc.render_prb(fsensor, seed=seed, spp=spp, max_depth=md, rr_depth=rr)
+        _compare("image after update round %d vs the oracle of a fresh load" % rnd, img, fref, 1e-4)
     grad_in = np.random.default_rng(seed).uniform(0.5, 1.5, ref.shape).astype(np.float32)
     grads = scene.integrator().render_backward(scene, None, grad_in, seed=seed + 2, spp=spp)
     w_refl, w_tex, w_emit, _ = osc.render_prb_backward_emitters(sensor, grad_in, seed=seed + 2, spp=spp, max_depth=md, rr_depth=rr)
