@@ -577,6 +577,41 @@ int har_integrator_set_material_queues(HarIntegrator integrator, int enable);
 int har_integrator_set_packet_tracing(HarIntegrator integrator, int mode);
 int har_render_timing(HarIntegrator integrator, float ms[8], uint32_t launches[8]);
 
+/* ------------------------------------------------------------------------
+ *  AOV integrator (src/integrators/aov.cpp): per-pixel depth, position, normals, albedo, uv, partials, ids.
+ *  An AOV is a function of the camera ray's surface interaction (AOVIntegratorImpl::sample, aov.cpp:175-306); a miss zeroes the interaction (:186), so
+ *  every channel of a missed or masked lane is 0.  Types and their channels (:117-168):
+ * ---------------------------------------------------------------------- */
+#define HAR_AOV_ALBEDO      0   /* R G B  BSDF::eval_diffuse_reflectance(si) (:206-222; diffuse.cpp:181, plastic.cpp:362, roughplastic.cpp:504, twosided.cpp:284-307, bsdf.cpp:38-43) */
+#define HAR_AOV_DEPTH       1   /* T      si.t */
+#define HAR_AOV_POSITION    2   /* X Y Z  si.p */
+#define HAR_AOV_UV          3   /* U V    si.uv */
+#define HAR_AOV_GEO_NORMAL  4   /* X Y Z  si.n */
+#define HAR_AOV_SH_NORMAL   5   /* X Y Z  sh_frame.n */
+#define HAR_AOV_DP_DU       6   /* X Y Z */
+#define HAR_AOV_DP_DV       7   /* X Y Z */
+#define HAR_AOV_PRIM_INDEX  8   /* I      float(si.prim_index) */
+#define HAR_AOV_SHAPE_INDEX 9   /* I      1-based position of the hit instance -- without one, of the hit shape -- in the scene's shape list (the scalar branch, :288-297); the
+                                 *        list of a HarSceneDesc is its top-level meshes followed by its instances */
+/* channels of the list types[0 .. n_aovs) (HOST); fails on an unknown type and on more than 32 entries */
+int har_aov_channel_count(uint32_t n_aovs, const uint32_t *types, uint32_t *count);
+/* AOVIntegratorImpl::sample, array-valued: n rays in (DEVICE, SoA as for har_ray_intersect), `out` = DEVICE, C x n floats (channel-major), C = har_aov_channel_count.
+ * `active` (n bytes, NULL = all): a masked lane traces nothing and writes zeros. */
+int har_aov_sample(HarScene scene, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active, uint32_t n_aovs, const uint32_t *types,
+                   float *out, void *stream);
+/* The same function on the HOST (no GPU): the scene is lowered as har_render_scalar does, the rays are traced with the host compilation of the traversal code and
+ * every lane runs the per-lane AOV code the kernels run.  All pointers HOST. */
+int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active, uint32_t n_aovs,
+                        const uint32_t *types, float *out);
+/* The AOV pass of AOVIntegrator::render (aov.cpp:389-470: one more SamplingIntegrator pass with the same sampler seed): lanes [lane_begin, lane_end) (0, 0 = all) of the
+ * wavefront of render() at `seed` / `spp` -- the same lanes, film positions and camera rays as there -- accumulate into `aov_film` (DEVICE, H x W x (C + 1): the C
+ * channels, then the reconstruction filter's weight; accumulated, not cleared, not developed).  `integrator` gives the chunk size (chunk_lanes) and the film window
+ * (har_integrator_set_film_window: rows of (C + 1) floats per pixel); hide_emitters does not apply (the inner integrator is built from empty properties, :108).
+ * The camera rays are traced by this pass's own per-lane kernel.  A render that needs several passes (samples_per_pass, more than 2^32 - 1 lanes) is refused.
+ * With har_integrator_set_profiling the pass's launches are timed as trace_closest (ms[1]), shade (ms[2]: the fill) and splat (ms[4]) of har_render_timing. */
+int har_render_aovs(HarScene scene, HarIntegrator integrator, const HarSensor *sensor, uint32_t seed, uint32_t spp, uint64_t lane_begin, uint64_t lane_end,
+                    uint32_t n_aovs, const uint32_t *types, float *aov_film, void *stream);
+
 
 /* ------------------------------------------------------------------------
  *  Host-side plugin lowering (no GPU involved).  A Transform4f is 32 floats:

@@ -168,6 +168,10 @@ SIGNATURES = {
     "har_render_stats": (C.c_int, [vp, C.POINTER(HarStats)]),
     "har_integrator_set_profiling": (C.c_int, [vp, C.c_int]),
     "har_render_timing": (C.c_int, [vp, f32p, u32p]),
+    "har_aov_channel_count": (C.c_int, [C.c_uint32, u32p, u32p]),
+    "har_aov_sample": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u32p, vp, vp]),
+    "har_aov_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, vp, C.c_uint32, u32p, f32p]),
+    "har_render_aovs": (C.c_int, [vp, vp, C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, u32p, vp, vp]),
     "har_transform_translate": (C.c_int, [f32p, f32p]),
     "har_transform_scale": (C.c_int, [f32p, f32p]),
     "har_transform_rotate": (C.c_int, [f32p, C.c_float, f32p]),

@@ -41,6 +41,8 @@ def variants():
 
 def _render_scalar(scene, integrator, sensor, seed, spp, threads=0, block_size=0):
     """SamplingIntegrator::render, non-JIT branch (integrator.cpp:190-274) through har_render_scalar: developed image as a numpy array"""
+    if integrator.type == 'aov':
+        raise RuntimeError("scalar_rgb: the `aov` integrator is not implemented by the scalar_rgb variant (hip_ad_rgb only)")
     if integrator.type != 'path':
         raise RuntimeError("scalar_rgb: only the `path` integrator is part of the config-1 plumbing path")
     if integrator.hide_emitters or sensor.film().alpha or integrator.samples_per_pass is not None:
@@ -434,7 +436,7 @@ def _cube(props):
 # ObjectType of every plugin this variant has (include/mitsuba/core/object.h: ObjectType; PluginManager::create_object checks it, plugin.cpp:258-263).
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
-    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
+    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
     'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
@@ -1501,6 +1503,173 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
 
 
 Integrator.render_forward = _render_forward
+
+
+# AOV types of the `aov` integrator: name -> (HAR_AOV_* value, channel suffixes) (aov.cpp:117-168)
+_AOV_TYPES = {'albedo': (0, 'RGB'), 'depth': (1, 'T'), 'position': (2, 'XYZ'), 'uv': (3, 'UV'), 'geo_normal': (4, 'XYZ'), 'sh_normal': (5, 'XYZ'),
+              'dp_du': (6, 'XYZ'), 'dp_dv': (7, 'XYZ'), 'prim_index': (8, 'I'), 'shape_index': (9, 'I')}
+
+
+def _parse_aovs(spec):
+    """AOVIntegratorImpl(aovs_spec) (aov.cpp:108-173): "<name>:<type>, ..." -> ([HAR_AOV_* values], [channel names])"""
+    types = []; names = []
+    for token in [t for t in str(spec).replace(',', ' ').split(' ') if t]:
+        item = token.split(':')
+        if len(item) != 2 or not item[0] or not item[1]:
+            raise RuntimeError("Invalid AOV specification: require <name>:<type> pair")
+        if item[1] in ('duv_dx', 'duv_dy'):      # need ray differentials, which the sensors of this variant do not carry
+            raise RuntimeError("aov: AOV type \"%s\" is not implemented by hip_ad_rgb" % item[1])
+        if item[1] not in _AOV_TYPES:
+            raise RuntimeError("Invalid AOV type \"%s\"!" % item[1])
+        value, suffixes = _AOV_TYPES[item[1]]
+        types.append(value); names += ["%s.%s" % (item[0], c) for c in suffixes]
+    return types, names
+
+
+class AOVIntegrator(Integrator):
+    """AOVIntegrator (src/integrators/aov.cpp): per-pixel depth / position / normals / albedo / uv / partials / ids next to the images of its child integrators."""
+
+    def __init__(self, props, named=None):
+        self.type = 'aov'
+        for k, v in props.items():
+            kind = _object_kind(v)
+            if isinstance(v, dict) and v.get('type') == 'aov' or isinstance(v, AOVIntegrator):
+                raise RuntimeError("aov: a nested `aov` integrator is not implemented by hip_ad_rgb")
+            if kind is not None and kind != 'integrator':
+                raise RuntimeError("Child objects must be of type 'SamplingIntegrator'!")          # aov.cpp:358-360
+        # SamplingIntegrator / Integrator properties (integrator.cpp:26-33,128-147): hide_emitters is read by the base class and does not reach the AOV pass, whose inner
+        # integrator is built from empty properties (aov.cpp:108); chunk_lanes is the hip_ad_rgb extension of `path`
+        _check_props('aov', props, ('aovs', 'hide_emitters', 'block_size', 'chunk_lanes'), unsupported=(('timeout', -1.0), ('samples_per_pass', None)),
+                     free_children=True, children=('integrator',), slot_kind=())
+        if 'aovs' not in props:
+            raise RuntimeError("Property \"aovs\" has not been specified!")                          # aov.cpp:373
+        if not isinstance(props['aovs'], str):
+            raise RuntimeError("The property \"aovs\" has the wrong type (expected string)")
+        self.children = []; self.child_names = []
+        for k, v in props.items():
+            if k in ('type', 'id', 'aovs', 'hide_emitters', 'block_size', 'chunk_lanes', 'timeout', 'samples_per_pass'):
+                continue
+            obj = _resolve(v, named if named is not None else {}, k) if isinstance(v, dict) else v
+            if not isinstance(obj, Integrator):
+                raise RuntimeError("Child objects must be of type 'SamplingIntegrator'!")
+            self.children.append(obj); self.child_names.append(k)
+        self.aov_types, self._own_names = _parse_aovs(props['aovs'])
+        self.channels = len(self._own_names)
+        self.max_depth = -1; self.rr_depth = 5; self.hide_emitters = bool(props.get('hide_emitters', False)); self.samples_per_pass = None
+        self.chunk_lanes = int(props.get('chunk_lanes', 0))
+        self.replay_cache = True; self.material_queues = False; self.packet_tracing = None
+        self._h = None
+
+    def _handle(self):
+        if self._h is None:             # carries the chunk size, the film window and the profiling events of the AOV pass
+            h = C.c_void_p()
+            check(lib().har_integrator_create(0, -1, 5, self.chunk_lanes, C.byref(h)))
+            self._h = h
+        return self._h
+
+    def aov_names(self):
+        """AOVIntegrator::aov_names (aov.cpp:357-382): per child <name>.R/.G/.B/.A and its own AOVs, then this integrator's"""
+        out = []
+        for name, child in zip(self.child_names, self.children):
+            out += ["%s.%s" % (name, c) for c in 'RGBA']
+            out += ["%s.%s" % (name, n) for n in (child.aov_names() if hasattr(child, 'aov_names') else [])]
+        return out + list(self._own_names)
+
+    def _types(self):
+        return (C.c_uint32 * max(1, len(self.aov_types)))(*self.aov_types)
+
+    def render_aov_film(self, scene, sensor=0, seed=0, spp=0, lanes=None, film=None, film_window=None):
+        """Raw accumulation of the AOV pass (har_render_aovs): H x W x (C + 1) -- the C channels of aov_names(), then the filter weight -- for lanes [begin, end)
+        (all when None) of the wavefront render() traces at this seed; not developed.  `film_window` as in render_film."""
+        torch = _torch(); dev = _device()
+        sensor = self._sensor(scene, sensor)
+        if spp:
+            sensor.sampler().set_sample_count(spp)
+        spp = sensor.sampler().sample_count()
+        w, h = sensor.film().crop_size()
+        if film is None:
+            film = torch.zeros((h if film_window is None else int(film_window[1]), w, self.channels + 1), dtype=torch.float32, device=dev)
+        lb, le = lanes if lanes else (0, 0)
+        if film_window is not None:
+            if film.shape[0] < film_window[1]:
+                raise RuntimeError("render_aov_film(): the film holds %d rows, the window %d" % (film.shape[0], film_window[1]))
+            check(lib().har_integrator_set_film_window(self._handle(), int(film_window[0]), int(film_window[1])))
+        try:
+            check(lib().har_render_aovs(scene._handle(), self._handle(), C.byref(sensor.har), (sensor.sampler().m_base_seed + int(seed)) & 0xffffffff, spp, lb, le,
+                                        len(self.aov_types), self._types(), _ptr(film), _stream()))
+        finally:
+            if film_window is not None:
+                check(lib().har_integrator_set_film_window(self._handle(), 0, 0))
+        return film
+
+    def render(self, scene, sensor=0, seed=0, spp=0, develop=True, evaluate=True):
+        """AOVIntegrator::render (aov.cpp:389-470): the children render with the same seed / spp, the AOV pass is one more pass over the same lanes; merge_channels
+        (:591-617): every child's developed image (3 channels, 4 on an `rgba` film) in order, then the AOV channels / W.  develop=False: the raw AOV film."""
+        torch = _torch()
+        if _variant == SCALAR_VARIANT:
+            raise RuntimeError("scalar_rgb: the `aov` integrator is not implemented by the scalar_rgb variant (hip_ad_rgb only)")
+        sensor = self._sensor(scene, sensor)
+        film = self.render_aov_film(scene, sensor, seed, spp)
+        if not develop:
+            out = film
+        else:
+            images = [c.render(scene, sensor, seed, spp, develop=True, evaluate=False) for c in self.children]
+            weight = film[:, :, self.channels:]
+            images.append(film[:, :, :self.channels] / torch.where(weight == 0, torch.ones_like(weight), weight))
+            out = torch.cat(images, dim=2)
+        if evaluate:
+            torch.cuda.current_stream().synchronize()
+        return out
+
+    def sample(self, scene, *args, active=True):
+        """AOVIntegratorImpl::sample (aov.cpp:175-306), array-valued: the C x n AOV values of the rays `ray` (mi.Ray3f; a sampler argument before it is accepted and
+        not used -- the function draws nothing); masked and missed lanes are zero."""
+        torch = _torch(); dev = _device()
+        ray = args[-1]; n = len(ray)
+        out = torch.empty((self.channels, n), dtype=torch.float32, device=dev)
+        mask = _mask(active, n)          # kept alive across the call (see Integrator.sample)
+        check(lib().har_aov_sample(scene._handle(), n, _ptr(ray.o), _ptr(ray.d), _ptr(ray.maxt), _ptr(mask), len(self.aov_types), self._types(), _ptr(out), _stream()))
+        del mask
+        return out
+
+    def sample_host(self, scene, o, d, maxt, active=None):
+        """the same function on the host (har_aov_sample_host; no GPU): o, d = 3 x n, maxt = n numpy arrays -> C x n"""
+        o = np.ascontiguousarray(_f32(o)); d = np.ascontiguousarray(_f32(d)); maxt = np.ascontiguousarray(_f32(maxt)); n = maxt.shape[0]
+        out = np.zeros((self.channels, n), np.float32)
+        act = None if active is None else np.ascontiguousarray(np.asarray(active).astype(np.uint8))
+        desc = scene.desc()
+        check(lib().har_aov_sample_host(C.byref(desc), n, _fp(o), _fp(d), _fp(maxt), act.ctypes.data_as(C.c_void_p) if act is not None else None,
+                                        len(self.aov_types), self._types(), _fp(out)))
+        return out
+
+    def _child_slices(self, sensor):
+        per = 4 if sensor.film().alpha else 3
+        return [(i * per, (i + 1) * per) for i in range(len(self.children))], per * len(self.children)
+
+    def render_backward(self, scene, params, grad_in, sensor=0, seed=0, spp=0, lanes=None, weight_film=None):
+        """split_channels (aov.cpp:620-637): every child gets its slice of the image gradient, the parameter gradients are summed over the children.  Gradients THROUGH
+        the AOV channels are not implemented: a non-zero gradient on them is an error, never a silently incomplete result."""
+        torch = _torch()
+        sensor = self._sensor(scene, sensor)
+        grad_in = torch.as_tensor(grad_in, dtype=torch.float32, device=_device())
+        slices, first_aov = self._child_slices(sensor)
+        if grad_in.shape[-1] != first_aov + self.channels:
+            raise RuntimeError("aov.render_backward(): the gradient has %d channels, the image %d" % (grad_in.shape[-1], first_aov + self.channels))
+        if bool((grad_in[..., first_aov:] != 0).any().item()):
+            raise RuntimeError("aov: gradients through the AOV channels (%s) are not implemented by hip_ad_rgb -- the incoming gradient on them is not zero; "
+                               "take the loss on the children's radiance channels only" % ", ".join(self._own_names))
+        total = {}
+        for child, (a, b) in zip(self.children, slices):
+            g = child.render_backward(scene, params, grad_in[..., a:b].contiguous(), sensor, seed, spp, lanes=lanes, weight_film=weight_film)
+            for k, v in g.items():
+                total[k] = v if k not in total else total[k] + v
+        return total
+
+    def render_forward(self, *args, **kwargs):
+        raise RuntimeError("render_forward(): the `aov` integrator is not implemented by hip_ad_rgb for forward-mode derivatives; use its `prb` child")
+
+    def render_film(self, *args, **kwargs):
+        raise RuntimeError("render_film(): the `aov` integrator has no {R, G, B, W} film; use render_aov_film() or its children")
 
 
 class Bitmap:
@@ -2797,6 +2966,8 @@ class DeviceGroup:
         integrator = integrator or scene.integrator()
         if integrator is None:
             raise Exception('No integrator specified!')
+        if integrator.type == 'aov':
+            raise RuntimeError("DeviceGroup: the `aov` integrator is not implemented by hip_ad_rgb for device groups")
         _device()
         self.scene, self.integrator, self.devices = scene, integrator, [int(d) for d in devices]
         d = scene.desc(); h = C.c_void_p()
@@ -3022,6 +3193,7 @@ for _name, _fn in {
     'scene': _mk_scene,
     'path': lambda p, n, k: Integrator(p),
     'prb': lambda p, n, k: Integrator(p),
+    'aov': lambda p, n, k: AOVIntegrator(p, n),
     'perspective': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),      # EVERY child object through the registry
     'orthographic': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
     'hdrfilm': lambda p, n, k: Film(p),
@@ -3095,15 +3267,17 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
     # on for THIS call's backward pass only -- the caller's integrator keeps its own properties (optimising vertex positions first and alpha
     # second with one integrator must not leave `shape_gradients` on for the second render)
     overrides = {}
-    if integrator.type == 'prb':
+    ad_targets = [integrator] if integrator.type == 'prb' else [c for c in integrator.children if c.type == 'prb'] if integrator.type == 'aov' else []
+    if ad_targets:
+        integrator_ad = ad_targets[0]
         shape_keys = [k for k in keys if k in scene._position_keys() or k in scene._instance_keys() or k in scene._rect_keys()]
-        if shape_keys and integrator.shape_gradients is not True:
-            overrides['shape_gradients'] = sorted(set(list(integrator.shape_gradients or [])) | set(shape_keys))
-        if any(k in scene._bsdf_param_keys() for k in keys) and not integrator.bsdf_parameter_gradients:
+        if shape_keys and integrator_ad.shape_gradients is not True:
+            overrides['shape_gradients'] = sorted(set(list(integrator_ad.shape_gradients or [])) | set(shape_keys))
+        if any(k in scene._bsdf_param_keys() for k in keys) and not integrator_ad.bsdf_parameter_gradients:
             overrides['bsdf_parameter_gradients'] = True
-        if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator.light_texel_gradients:
+        if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator_ad.light_texel_gradients:
             overrides['light_texel_gradients'] = True
-        if any(v[0] == "emit" for k, v in scene._param_keys().items() if k in keys) and not integrator.emitter_gradients:
+        if any(v[0] == "emit" for k, v in scene._param_keys().items() if k in keys) and not integrator_ad.emitter_gradients:
             overrides['emitter_gradients'] = True
 
     class _RenderOp(torch.autograd.Function):
@@ -3115,14 +3289,16 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
 
         @staticmethod
         def backward(ctx, grad_out):
-            saved = {k: getattr(integrator, k) for k in overrides}
+            saved = [{k: getattr(t, k) for k in overrides} for t in ad_targets]
             try:
-                for k, v in overrides.items():
-                    setattr(integrator, k, v)
+                for t in ad_targets:
+                    for k, v in overrides.items():
+                        setattr(t, k, v)
                 grads = integrator.render_backward(scene, params, grad_out, sensor, seed_grad, spp_grad)
             finally:
-                for k, v in saved.items():
-                    setattr(integrator, k, v)
+                for t, old in zip(ad_targets, saved):
+                    for k, v in old.items():
+                        setattr(t, k, v)
             missing = [k for k in keys if k not in grads]
             if missing:       # e.g. emitter radiance with emitter_gradients=False, vertex positions without shape_gradients
                 raise RuntimeError("mi.render(): the `prb` integrator cannot differentiate %s (integrator properties `emitter_gradients`, "

@@ -13,6 +13,7 @@
 #include "har_scene_host.h"
 #include "har_refit_launch.h"
 #include "har_vertex_update.h"
+#include "har_aov_launch.h"
 
 #include <algorithm>
 #include <cstddef>
@@ -180,6 +181,8 @@ struct HarIntegratorImpl {
     float *alpha_film = nullptr;          /* user buffer (DEVICE, H x W x 4: channel 3 accumulates w * alpha) of har_integrator_set_alpha_film, or null */
     uint32_t film_row0 = 0, film_rows = 0; /* har_integrator_set_film_window: the film buffers of har_render hold rows [film_row0, film_row0 + film_rows) of the crop window (0 rows = all) */
     float *alpha_lane = nullptr;          /* alpha value per lane of the chunk */
+    /* AOV pass (har_render_aovs): hit records and channel-major values of one chunk -- blocks of their own, not part of the path tracer's workspace */
+    struct AovWorkspace { float4 *h0 = nullptr; uint2 *h1 = nullptr; float *val = nullptr; int *status = nullptr; size_t lanes = 0, floats = 0; } aov;
     uint32_t *skip_counters = nullptr;    /* hide_emitters: count + cursor of the two continuation lists of skip_area_emitters */
     uint32_t *pk_list = nullptr, *pk_counters = nullptr;      /* wave-shared descent of the camera rays (k_trace_packet): the packets left to the per-lane kernel, their count + cursor */
     // workspace
@@ -1626,6 +1629,10 @@ int har_integrator_destroy(HarIntegrator I) {
     if (!I) return 0;
     (void) hipDeviceSynchronize();
     I->free_ws();
+    if (I->aov.status || I->aov.h0 || I->aov.val) {
+        (void) hipDeviceSynchronize();
+        dev_free(I->aov.h0, true); dev_free(I->aov.h1, true); dev_free(I->aov.val, true); dev_free(I->aov.status, true);
+    }
     prof_destroy(I);
     if (I->twin) { I->twin->free_ws(); prof_destroy(I->twin); }
     if (I->ev_fork) (void) hipEventDestroy(I->ev_fork);
@@ -1748,7 +1755,7 @@ static int dual_join(HarIntegrator I, hipStream_t s) {
 
 /* film window (har_integrator_set_film_window): the rows the lanes [lb, le) can splat into -- their pixel rows in the sample grid, moved by the sample border, widened by
  * the reconstruction filter's footprint (film_footprint, har_path.h) -- must lie inside the window; the kernels then get the address row 0 WOULD have */
-static int apply_film_window(HarIntegrator I, const HarSensor *sensor, uint32_t spp, uint64_t lb, uint64_t le, float *&film) {
+static int apply_film_window(HarIntegrator I, const HarSensor *sensor, uint32_t spp, uint64_t lb, uint64_t le, float *&film, uint32_t channels = 4) {
     if (!I->film_rows) return 0;
     DSensor C; std::string e;
     if (!lower_sensor(*sensor, C, e)) return fail(e);
@@ -1763,7 +1770,7 @@ static int apply_film_window(HarIntegrator I, const HarSensor *sensor, uint32_t 
     if (y0 <= y1 && (y0 < (int64_t) I->film_row0 || y1 >= (int64_t) I->film_row0 + I->film_rows))
         return fail("har_integrator_set_film_window: the lanes splat into film rows [" + std::to_string(y0) + ", " + std::to_string(y1) + "], the window holds [" +
                     std::to_string(I->film_row0) + ", " + std::to_string(I->film_row0 + I->film_rows - 1) + "]");
-    film -= (size_t) I->film_row0 * C.crop_w * 4;
+    film -= (size_t) I->film_row0 * C.crop_w * channels;
     return 0;
 }
 
@@ -2246,6 +2253,96 @@ int har_render_timing(HarIntegrator I, float ms[8], uint32_t launches[8]) {
     const double f = frames ? (double) frames : 1.0;
     for (int k = 0; k < 8; ++k) { ms[k] = (float) (m[k] / f); launches[k] = (uint32_t) (l[k] / f + 0.5); }
     ms[7] = (float) frames;
+    return 0;
+}
+
+/* ------------------------------------------------------------------ AOV integrator (src/integrators/aov.cpp; kernels in har_aov.hip, per-lane code in har_aov.h) */
+static int lower_aov_spec(uint32_t n_aovs, const uint32_t *types, AovSpec &spec) {
+    const char *e = aov_spec_lower(n_aovs, types, spec);
+    return e ? fail(e) : 0;
+}
+
+int har_aov_channel_count(uint32_t n_aovs, const uint32_t *types, uint32_t *count) {
+    AovSpec spec;
+    if (!count) return fail("null argument");
+    if (lower_aov_spec(n_aovs, types, spec)) return 1;
+    *count = spec.channels;
+    return 0;
+}
+
+static bool aov_deep_stack(const HarSceneImpl *S) { return S->hs.stack_need() + HAR_STACK_MARGIN > (uint32_t) HAR_LDS_STACK_SMALL; }
+
+int har_aov_sample(HarScene S, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active, uint32_t n_aovs, const uint32_t *types, float *out,
+                   void *stream) {
+    if (!S) return fail("null scene");
+    AovSpec spec;
+    if (lower_aov_spec(n_aovs, types, spec)) return 1;
+    if (n == 0 || spec.channels == 0) return 0;
+    if (!o || !d || !maxt || !out) return fail("null ray / output array");
+    hipStream_t s = (hipStream_t) stream;
+    float4 *h0 = nullptr; uint2 *h1 = nullptr; int *st = nullptr;
+    HIP_TRY(dev_alloc((void **) &st, sizeof(int)));
+    if (dev_alloc((void **) &h0, (size_t) n * sizeof(float4)) != hipSuccess || dev_alloc((void **) &h1, (size_t) n * sizeof(uint2)) != hipSuccess) {
+        dev_free(st); dev_free(h0); return fail("har_aov_sample: out of device memory");
+    }
+    int rc = 0;
+    if (hipMemsetAsync(st, 0, sizeof(int), s) != hipSuccess) rc = fail("har_aov_sample: hipMemsetAsync failed");
+    if (!rc) {
+        launch_aov_trace_rays(s, S->ds, aov_deep_stack(S), n, o, d, maxt, active, h0, h1, st);
+        launch_aov_fill_rays(s, S->ds, spec, S->hs.top_mesh_count, n, d, active, h0, h1, out);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) rc = fail(std::string("har_aov_sample: ") + hipGetErrorString(e));
+    }
+    if (!rc) rc = read_status(st, s);              /* synchronises the stream: the blocks below are idle when they are freed */
+    else (void) hipStreamSynchronize(s);
+    dev_free(st); dev_free(h0); dev_free(h1);
+    return rc;
+}
+
+int har_render_aovs(HarScene S, HarIntegrator I, const HarSensor *sensor, uint32_t seed, uint32_t spp, uint64_t lb, uint64_t le, uint32_t n_aovs, const uint32_t *types,
+                    float *film, void *stream) {
+    if (!S || !I || !sensor) return fail("null scene / integrator / sensor");
+    if (!film) return fail("null film");
+    AovSpec spec;
+    if (lower_aov_spec(n_aovs, types, spec)) return 1;
+    uint32_t spp_pass = spp, n_passes = 1, grid_w = 0, grid_h = 0;
+    if (sample_grid(sensor, grid_w, grid_h)) return 1;
+    if (pass_layout(I, grid_w, grid_h, spp, spp_pass, n_passes)) return 1;
+    if (n_passes > 1) return fail("har_render_aovs: a render in several passes (samples_per_pass, more than 2^32 - 1 lanes) is not implemented by hip_ad_rgb for the aov integrator");
+    DSensor C; uint32_t log_spp;
+    if (check_common(S, I, sensor, spp, lb, le, C, log_spp)) return 1;
+    if (I->film_rows && apply_film_window(I, sensor, spp, lb, le, film, spec.channels + 1u)) return 1;
+    if (le == lb) return 0;
+    hipStream_t s = (hipStream_t) stream;
+    const uint32_t chunk = (uint32_t) std::min<uint64_t>(I->chunk, (std::max<uint64_t>(le - lb, 2048) + 2047) / 2048 * 2048);
+    HarIntegratorImpl::AovWorkspace &W = I->aov;
+    if (!W.status) { HIP_TRY(dev_alloc((void **) &W.status, sizeof(int))); }
+    if (W.lanes < chunk) {
+        if (W.h0 || W.h1) { (void) hipDeviceSynchronize(); dev_free(W.h0, true); dev_free(W.h1, true); W.h0 = nullptr; W.h1 = nullptr; W.lanes = 0; }
+        HIP_TRY(dev_alloc((void **) &W.h0, (size_t) chunk * sizeof(float4)));
+        HIP_TRY(dev_alloc((void **) &W.h1, (size_t) chunk * sizeof(uint2)));
+        W.lanes = chunk;
+    }
+    const size_t floats = (size_t) chunk * std::max<uint32_t>(spec.channels, 1u);
+    if (W.floats < floats) {
+        if (W.val) { (void) hipDeviceSynchronize(); dev_free(W.val, true); W.val = nullptr; W.floats = 0; }
+        HIP_TRY(dev_alloc((void **) &W.val, floats * sizeof(float)));
+        W.floats = floats;
+    }
+    HIP_TRY(hipMemsetAsync(W.status, 0, sizeof(int), s));
+    I->last_stream = s; I->twin_used = false;
+    if (prof_begin(I, s)) return 1;
+    const bool deep = aov_deep_stack(S);
+    for (uint64_t base = lb; base < le; base += chunk) {
+        const uint32_t n = (uint32_t) std::min<uint64_t>(chunk, le - base);
+        launch_aov_trace_lanes(s, S->ds, deep, C, seed, spp, log_spp, (uint32_t) base, n, W.h0, W.h1, W.status);
+        prof_mark(I, s, CLS_TRACE);
+        launch_aov_fill_lanes(s, S->ds, spec, S->hs.top_mesh_count, C, seed, spp, log_spp, (uint32_t) base, n, W.h0, W.h1, W.val, (size_t) chunk);
+        prof_mark(I, s, CLS_SHADE);
+        launch_splat_channels(s, C, seed, spp, log_spp, (uint32_t) base, n, W.val, (size_t) chunk, spec.channels, film);
+        prof_mark(I, s, CLS_SPLAT);
+    }
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -16,6 +16,7 @@
 #include "../../include/hip_ad_rgb.h"
 #include "har_cpu.h"
 #include "har_path.h"
+#include "har_aov.h"
 #include "har_scene_host.h"
 
 #include <algorithm>
@@ -260,4 +261,34 @@ extern "C" int har_render_scalar(const HarSceneDesc *desc, const HarSensor *sens
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_render_scalar: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_render_scalar: ") + ex.what()); }
+}
+
+/* AOVIntegratorImpl::sample (src/integrators/aov.cpp:175-306) on the host: the scene lowered as above, accel_trace for the closest hit, aov_lane (har_aov.h) -- the
+ * function the kernels of har_aov.hip run -- for the channels.  The twin of har_aov_sample: a test of the feature without a GPU, and the other side of the
+ * device / host bit comparison. */
+extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active, uint32_t n_aovs,
+                                   const uint32_t *types, float *out) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        AovSpec spec;
+        if (const char *e = aov_spec_lower(n_aovs, types, spec)) return har_set_error(e);
+        if (n == 0 || spec.channels == 0) return 0;
+        if (!o || !d || !maxt || !out) return har_set_error("null ray / output array");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        if (B.hs.stack_need() > (uint32_t) ScalarStack::Capacity) return har_set_error("scene too deep for the scalar traversal stack");
+        B.bind();
+        const DScene &S = B.ds;
+        int status = 0;
+        for (uint32_t i = 0; i < n; ++i) {
+            const Vec3 O(o[i], o[n + i], o[2 * (size_t) n + i]), D(d[i], d[n + i], d[2 * (size_t) n + i]);
+            const bool act = !(active && !active[i]);
+            Hit hit; hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
+            if (act) { ScalarStack stack; accel_trace<false>(S.accel, O, D, maxt[i], hit, stack, status); }
+            aov_lane(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+        }
+        if (status) return har_set_error("har_aov_sample_host: traversal stack overflow");
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_aov_sample_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_aov_sample_host: ") + ex.what()); }
 }

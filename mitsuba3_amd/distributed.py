@@ -141,6 +141,8 @@ def render_distributed(scene, integrator=None, sensor=0, seed=0, spp=0, develop=
     "band": every rank owns the rows its band can reach (band + filter reach + sample border; har_integrator_set_film_window), ONE gather, `dst` adds the bands --
     the default from BAND_FILM_MIN_BYTES up (BASELINE config 5: 256 MiB film -> 32 MiB + halo per rank at eight ranks)."""
     integrator = integrator or scene.integrator()
+    if getattr(integrator, "type", None) == "aov":
+        raise RuntimeError("render_distributed: the `aov` integrator is not implemented by hip_ad_rgb for distributed renders")
     s = scene.sensors()[sensor] if isinstance(sensor, int) else sensor
     if spp:
         s.sampler().set_sample_count(spp)
@@ -197,6 +199,8 @@ def render_backward_distributed(scene, grad_in, integrator=None, sensor=0, seed=
     makes W[px] complete everywhere (the adjoint of develop needs every rank's samples), every rank replays its band, and the gradient
     buffers are all-reduced.  Returns {key: gradient tensor}, identical on every rank."""
     integrator = integrator or scene.integrator()
+    if getattr(integrator, "type", None) == "aov":
+        raise RuntimeError("render_distributed: the `aov` integrator is not implemented by hip_ad_rgb for distributed renders")
     s = scene.sensors()[sensor] if isinstance(sensor, int) else sensor
     if spp:
         s.sampler().set_sample_count(spp)
