@@ -362,6 +362,18 @@ int har_bsdf_sample(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, ui
 /* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237) */
 int har_sensor_sample_ray(const HarSensor *sensor, uint32_t n, const float *pos_x,
                           const float *pos_y, float *o, float *d, float *maxt, void *stream);
+/* BatchSensor (src/sensors/batch.cpp): `n_children` child sensors share one film n_children times as wide as theirs; the x coordinate of the film position picks the
+ * child (batch.cpp:138-145: index = min(uint(pos_x * n), n - 1), position on the child's film = (pos_x * n - uint(pos_x * n), pos_y)) and the ray is that child's
+ * sample_ray.  Every HarSensor of `children` is the child lowered for ITS film -- the batch film's width / n_children by its height, full crop window
+ * (batch.cpp:122-124); a child with a crop window is refused.  Children may be perspective or orthographic.
+ *   har_integrator_set_batch_sensors: the children of the batch sensor the integrator renders next (copied to the device in `stream` order); the `sensor` argument of
+ *     har_render / har_render_backward / har_render_forward / har_render_aovs then describes the batch sensor's wide film (size, filter; its camera part is unused; no
+ *     crop window, no sample border; the width must be divisible by n).  n = 0 clears the table: `sensor` is an ordinary camera again.
+ *   har_batch_sample_ray: BatchSensor::sample_ray over n film positions (DEVICE arrays, as har_sensor_sample_ray);
+ *   har_batch_sample_ray_host: the same per-lane code compiled for the host, all pointers HOST -- no GPU needed; the two agree bit for bit. */
+int har_integrator_set_batch_sensors(HarIntegrator integrator, const HarSensor *children, uint32_t n, void *stream);
+int har_batch_sample_ray(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, float *o, float *d, float *maxt, void *stream);
+int har_batch_sample_ray_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, float *o, float *d, float *maxt);
 /* ImageBlock::put (src/render/imageblock.cpp:187-540): film is H x W x 4 {R,G,B,W} */
 int har_film_put(const HarSensor *sensor, uint32_t n, const float *pos_x, const float *pos_y,
                  const float *values4 /*[n][4]*/, float *film, void *stream);

@@ -148,6 +148,9 @@ SIGNATURES = {
     "har_mesh_compute_normals": (C.c_int, [C.c_uint32, vp, C.c_uint32, vp]),
     "har_mesh_free": (None, [vp]),
     "har_sensor_sample_ray": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "har_integrator_set_batch_sensors": (C.c_int, [vp, C.POINTER(HarSensor), C.c_uint32, vp]),
+    "har_batch_sample_ray": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "har_batch_sample_ray_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p]),
     "har_film_put": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, vp, vp, vp, vp, vp]),
     "har_film_develop": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp]),
     "har_film_develop_format": (C.c_int, [vp, C.c_uint32, C.c_uint32, C.c_int, vp, vp]),

@@ -45,6 +45,7 @@ def _render_scalar(scene, integrator, sensor, seed, spp, threads=0, block_size=0
         raise RuntimeError("scalar_rgb: the `aov` integrator is not implemented by the scalar_rgb variant (hip_ad_rgb only)")
     if integrator.type != 'path':
         raise RuntimeError("scalar_rgb: only the `path` integrator is part of the config-1 plumbing path")
+    _refuse_batch(sensor, "scalar_rgb (har_render_scalar)")
     if integrator.hide_emitters or sensor.film().alpha or integrator.samples_per_pass is not None:
         raise RuntimeError("scalar_rgb: hide_emitters, rgba films and samples_per_pass are not part of the config-1 plumbing path")
     if spp:
@@ -436,7 +437,7 @@ def _cube(props):
 # ObjectType of every plugin this variant has (include/mitsuba/core/object.h: ObjectType; PluginManager::create_object checks it, plugin.cpp:258-263).
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
-    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
+    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
     'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
@@ -779,6 +780,96 @@ class Sensor:
         o = torch.empty((3, n), dtype=torch.float32, device=dev); d = torch.empty_like(o); mt = torch.empty(n, dtype=torch.float32, device=dev)
         check(lib().har_sensor_sample_ray(C.byref(self.har), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
         return Ray3f(o, d, mt), torch.ones(n, device=dev)
+
+
+class BatchSensor(Sensor):
+    """BatchSensor (src/sensors/batch.cpp): N child sensors share one film N times as wide as theirs; the x coordinate of a film position picks the child
+    (batch.cpp:138-145).  `har` describes the wide film (size, filter) -- its camera part is unused; `children_har()` is the table har_integrator_set_batch_sensors takes."""
+
+    def __init__(self, props):
+        self.props = dict(props)
+        self.kind = 'batch'
+        # Sensor(props) (sensor.cpp:24-97) + props.objects() (batch.cpp:94-109): sensors, and shapes that carry one -- no shape of hip_ad_rgb does
+        _check_props('batch', props, ('to_world', 'film', 'sampler', 'shutter_open', 'shutter_close'), children=('film', 'sampler', 'sensor', 'shape'),
+                     slots={'film': ('film',), 'sampler': ('sampler',)}, slot_kind=())
+        film = next((v for v in props.values() if isinstance(v, Film)), props.get('film'))
+        sampler = next((v for v in props.values() if isinstance(v, Sampler)), props.get('sampler'))
+        self.m_film = film if isinstance(film, Film) else Film(film)
+        self.m_sampler = sampler if isinstance(sampler, Sampler) else Sampler(sampler)
+        self.to_world = props.get('to_world', ScalarTransform4f())
+        self.near_clip = 1e-2; self.far_clip = 1e4
+        self.m_sensors = []; self.child_names = []
+        for k, v in props.items():
+            if isinstance(v, BatchSensor):
+                raise RuntimeError("batch: a nested `batch` sensor (child \"%s\") is not implemented by hip_ad_rgb" % k)
+            if isinstance(v, Sensor):
+                # batch.cpp:277-279: the child's id, or sensor<i> for an unnamed one (anonymous XML children are `_arg_<n>` here)
+                self.child_names.append("sensor%d" % len(self.m_sensors) if k.startswith('_arg_') else k)
+                self.m_sensors.append(v)
+            elif _object_kind(v) == 'shape':                  # batch.cpp:97-107
+                raise RuntimeError("BatchSensor: shapes can only be specified as children if a sensor is associated with them!")
+        n = len(self.m_sensors)
+        if n == 0:                                               # batch.cpp:111-112
+            raise RuntimeError("BatchSensor: at least one child sensor must be specified!")
+        f = self.m_film
+        if f.width // n * n != f.width:                          # batch.cpp:114-119
+            raise RuntimeError("BatchSensor: the horizontal resolution (currently %u) must be divisible by the number of child sensors (%u)!" % (f.width, n))
+        # the reference hands the children position samples of the crop-adjusted wide film and divides a crop window between them; refused rather than restated
+        if f.crop_offset_ != (0, 0) or f.crop_size_ != (f.width, f.height):
+            raise RuntimeError("batch: a crop window on the batch sensor's film is not implemented by hip_ad_rgb")
+        if f.sample_border_:
+            raise RuntimeError("batch: `sample_border` on the batch sensor's film is not implemented by hip_ad_rgb")
+        for name, c in zip(self.child_names, self.m_sensors):
+            cf = c.m_film
+            if cf.crop_offset_ != (0, 0) or cf.crop_size_ != (cf.width, cf.height):
+                raise RuntimeError("batch: a crop window on the film of child sensor \"%s\" is not implemented by hip_ad_rgb" % name)
+            # batch.cpp:122-124: film()->set_size(sub_size, size.y) -- which resets the crop window to the whole film (film.cpp:82-88) -- then parameters_changed()
+            cf.width = f.width // n; cf.height = f.height; cf.crop_size_ = (cf.width, cf.height); cf.crop_offset_ = (0, 0)
+            c.update()
+        self.update()
+
+    def update(self):
+        f = self.m_film
+        s = _capi.HarSensor()
+        if lib().har_perspective_sensor(_fp(ScalarTransform4f().data), 45.0, b'x', self.near_clip, self.far_clip, f.width, f.height, 0, 0, f.width, f.height,
+                                        f.rfilter, f.stddev, C.byref(s)):
+            raise RuntimeError("invalid film parameters of the batch sensor")
+        s.rfilter_param1 = f.rf_param1
+        s.sample_border = 0
+        self.har = s
+
+    def sensors(self):
+        return list(self.m_sensors)
+
+    def children_har(self):
+        """the children's records as one ctypes array (har_integrator_set_batch_sensors / har_batch_sample_ray), taken anew on every call: params.update() re-lowers a child in place"""
+        return (_capi.HarSensor * len(self.m_sensors))(*[c.har for c in self.m_sensors])
+
+    def x_fov(self):
+        raise RuntimeError("batch: the batch sensor has no field of view of its own; see its children")
+
+    def sample_ray(self, time, sample1, sample2, sample3=None):
+        """BatchSensor::sample_ray (batch.cpp:132-159): sample2 is the position on the wide film in [0,1]^2, tensor [2, n]."""
+        torch = _torch(); dev = _device()
+        p = torch.as_tensor(sample2, dtype=torch.float32, device=dev).reshape(2, -1).contiguous(); n = p.shape[1]
+        o = torch.empty((3, n), dtype=torch.float32, device=dev); d = torch.empty_like(o); mt = torch.empty(n, dtype=torch.float32, device=dev)
+        ch = self.children_har()
+        check(lib().har_batch_sample_ray(ch, len(ch), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
+        return Ray3f(o, d, mt), torch.ones(n, device=dev)
+
+    def sample_ray_host(self, sample2):
+        """the same on the host (har_batch_sample_ray_host; no GPU): sample2 = 2 x n numpy array -> (o 3 x n, d 3 x n, maxt n)"""
+        p = np.ascontiguousarray(np.asarray(sample2, np.float32).reshape(2, -1)); n = p.shape[1]
+        px = np.ascontiguousarray(p[0]); py = np.ascontiguousarray(p[1])
+        o = np.empty((3, n), np.float32); d = np.empty((3, n), np.float32); mt = np.empty(n, np.float32)
+        ch = self.children_har()
+        check(lib().har_batch_sample_ray_host(ch, len(ch), n, _fp(px), _fp(py), _fp(o), _fp(d), _fp(mt)))
+        return o, d, mt
+
+
+def _refuse_batch(sensor, what):
+    if getattr(sensor, 'kind', None) == 'batch':
+        raise RuntimeError("batch: the batch sensor is not implemented by %s in hip_ad_rgb; render it with mi.render / Integrator.render on one device" % what)
 
 
 # include/mitsuba/render/ior.h:24-48
@@ -1219,6 +1310,20 @@ class Integrator:
             self.samples_per_pass = int(self.samples_per_pass)
         self._h = None
 
+    def _bind_sensor(self, sensor):
+        """the child table of a batch sensor goes to the library integrator before the render call that names its wide film (har_integrator_set_batch_sensors);
+        a plain sensor rendered next clears it.  The table is compared by value: params.update() re-lowers children in place."""
+        bound = self.__dict__.get('_batch_bound')
+        if getattr(sensor, 'kind', None) == 'batch':
+            ch = sensor.children_har()
+            sig = bytes(ch)
+            if bound != sig:
+                check(lib().har_integrator_set_batch_sensors(self._handle(), ch, len(ch), _stream()))
+                self._batch_bound = sig
+        elif bound is not None:
+            check(lib().har_integrator_set_batch_sensors(self._handle(), None, 0, None))
+            self._batch_bound = None
+
     def _handle(self):
         if self._h is None:
             h = C.c_void_p()
@@ -1270,7 +1375,9 @@ class Integrator:
         return dict(paths=st.paths, vertices=st.vertices, closest_rays=st.closest_rays, shadow_rays=st.shadow_rays)
 
     def _sensor(self, scene, sensor):
-        return scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+        sensor = scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+        self._bind_sensor(sensor)
+        return sensor
 
     def render_film(self, scene, sensor=0, seed=0, spp=0, lanes=None, film=None, alpha_film=None, film_window=None):
         """Raw {R,G,B,W} accumulation of lanes [begin, end) (all when None); no develop.  `alpha_film` (H x W x 4 zeros): also accumulate
@@ -2361,7 +2468,13 @@ class Scene:
         orthographic.cpp:95), '<emitter>.position' of a point light (point.cpp:86), '<emitter>.to_world' of spot and directional lights (spot.cpp:117,
         directional.cpp:96) -- 4 x 4 matrices / a 3-vector; params.update() re-lowers the sensor or the scene"""
         keys = {}
+        sensors = []
         for k, s in zip(self.sensor_keys, self.m_sensors):
+            if s.kind == 'batch':        # BatchSensor::traverse (batch.cpp:273-282): the children under their names, each with its own sensor's entries
+                sensors += [(k + "." + name, c) for name, c in zip(s.child_names, s.m_sensors)]
+            else:
+                sensors.append((k, s))
+        for k, s in sensors:
             keys[k + ".to_world"] = ("sensor", s)
             if s.kind != 'orthographic':          # PerspectiveCamera::traverse (perspective.cpp:155-160)
                 keys[k + ".x_fov"] = ("x_fov", s)
@@ -2990,6 +3103,7 @@ class DeviceGroup:
     def render(self, sensor=0, seed=0, spp=0, develop=True):
         torch = _torch()
         s = self.scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+        _refuse_batch(s, "DeviceGroup (har_multi_render)")
         if getattr(s.film(), "alpha", False):
             raise RuntimeError("DeviceGroup.render(): the group's film has no alpha channel; an `rgba` film renders with render_distributed or mi.render")
         if spp:
@@ -3011,6 +3125,7 @@ class DeviceGroup:
             raise RuntimeError("render_backward(): only the `prb` integrator implements the adjoint pass in hip_ad_rgb")
         torch = _torch()
         s = self.scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+        _refuse_batch(s, "DeviceGroup (har_multi_render_backward)")
         if spp:
             s.sampler().set_sample_count(spp)
         spp = s.sampler().sample_count()
@@ -3196,6 +3311,7 @@ for _name, _fn in {
     'aov': lambda p, n, k: AOVIntegrator(p, n),
     'perspective': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),      # EVERY child object through the registry
     'orthographic': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
+    'batch': lambda p, n, k: BatchSensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),

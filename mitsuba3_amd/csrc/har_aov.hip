@@ -49,6 +49,16 @@ __global__ __launch_bounds__(kBlock) void k_aov_trace(DScene S, DSensor C, uint3
     h1[i] = make_uint2(hit.shape, hit.inst);
 }
 
+/* camera rays of the lanes of a BATCH sensor's render (k_raygen_batch's rays), SoA with stride n: the AOV pass of a batch sensor then runs the _rays flavours of the
+ * kernels below on them, which keeps the single-sensor flavours as they are */
+__global__ __launch_bounds__(kBlock) void k_aov_batch_rays(DSensor C, DBatch batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
+                                                           float *o, float *d, float *maxt) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    LaneSample ls; const PathState st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, &batch);
+    o[i] = st.o.x; o[n + i] = st.o.y; o[2 * (size_t) n + i] = st.o.z; d[i] = st.d.x; d[n + i] = st.d.y; d[2 * (size_t) n + i] = st.d.z; maxt[i] = st.maxt;
+}
+
 /* AOVIntegratorImpl::sample per lane: the channels of `spec`, channel-major (aov[c * stride + i]) so that these stores and the splat's loads coalesce */
 template <bool LANES>
 __global__ __launch_bounds__(kBlock) void k_aov_fill(DScene S, AovSpec spec, uint32_t top_meshes, DSensor C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
@@ -168,6 +178,10 @@ void launch_aov_trace_lanes(hipStream_t s, const DScene &S, bool deep, const DSe
                             float4 *h0, uint2 *h1, int *status) {
     if (deep) hipLaunchKernelGGL((k_aov_trace<HAR_LDS_STACK_DEPTH, true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, nullptr, nullptr, h0, h1, status);
     else hipLaunchKernelGGL((k_aov_trace<HAR_LDS_STACK_SMALL, true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, nullptr, nullptr, h0, h1, status);
+}
+void launch_aov_batch_rays(hipStream_t s, const DSensor &C, const DBatch &batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
+                           float *o, float *d, float *maxt) {
+    hipLaunchKernelGGL(k_aov_batch_rays, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, batch, seed, spp, log_spp, lane_base, n, o, d, maxt);
 }
 void launch_aov_trace_rays(hipStream_t s, const DScene &S, bool deep, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active,
                            float4 *h0, uint2 *h1, int *status) {

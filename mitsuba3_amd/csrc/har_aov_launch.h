@@ -13,6 +13,9 @@ void launch_aov_trace_lanes(hipStream_t s, const DScene &S, bool deep, const DSe
                             float4 *h0, uint2 *h1, int *status);
 void launch_aov_trace_rays(hipStream_t s, const DScene &S, bool deep, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active,
                            float4 *h0, uint2 *h1, int *status);
+/* the camera rays of lanes [lane_base, lane_base + n) of a batch sensor's render, SoA with stride n (for the _rays launches) */
+void launch_aov_batch_rays(hipStream_t s, const DSensor &C, const DBatch &batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
+                           float *o, float *d, float *maxt);
 /* k_aov_fill: aov_lane() per lane, channel-major: aov[c * stride + i] */
 void launch_aov_fill_lanes(hipStream_t s, const DScene &S, const AovSpec &spec, uint32_t top_meshes, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp,
                            uint32_t lane_base, uint32_t n, const float4 *h0, const uint2 *h1, float *aov, size_t stride);

@@ -177,6 +177,10 @@ struct HarIntegratorImpl {
      * (measured on the 1M-triangle scene, 67 M lanes: 16 M-lane chunks 708, 32 M 758, one 64 M chunk 783 Mpaths/s) */
     uint32_t max_depth = 0, rr_depth = 5, chunk = 1u << 26;
     bool hide_emitters = false;           /* Integrator property (integrator.cpp:29) */
+    /* har_integrator_set_batch_sensors: the child cameras of a batch sensor (DEVICE table, a block of its own) -- batch.n != 0: the `sensor` of the render calls is the
+     * batch sensor's wide film and the camera rays come from the table (k_raygen_batch) */
+    DBatch batch{ nullptr, 0u }; DCamera *batch_cams = nullptr; uint32_t batch_cap = 0;
+    float *aov_rays = nullptr; size_t aov_rays_cap = 0;      /* AOV pass of a batch sensor: the chunk's camera rays (7 floats per lane) */
     bool forward_mode = false;            /* har_render_forward in progress: the adjoint kernels read tangents and accumulate differential radiance */
     float *alpha_film = nullptr;          /* user buffer (DEVICE, H x W x 4: channel 3 accumulates w * alpha) of har_integrator_set_alpha_film, or null */
     uint32_t film_row0 = 0, film_rows = 0; /* har_integrator_set_film_window: the film buffers of har_render hold rows [film_row0, film_row0 + film_rows) of the crop window (0 rows = all) */
@@ -547,7 +551,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
      * bounce-0 wavefront nobody else reads (no alpha / validity flags, no material queues, no tape); the passes of a multi-pass forward render resume their samplers from the pass state in both kernels.  HAR_FIRST_VERTEX=0 switches it off (A/B) */
     static const bool first_env = !(getenv("HAR_FIRST_VERTEX") && atoi(getenv("HAR_FIRST_VERTEX")) == 0);
     static const int mq_env0 = getenv("HAR_MATERIAL_QUEUES") ? atoi(getenv("HAR_MATERIAL_QUEUES")) : -1;
-    const bool first_regen = first_env && ((mode == MODE_PATH && cache_mode == 0) || (mode == MODE_PRB_PRIMAL && rec_w && I->adj && !I->forward_mode && !ps.rng)) && !rays && !valid_lane && !(I->alpha_film && I->alpha_lane) &&
+    const bool first_regen = first_env && ((mode == MODE_PATH && cache_mode == 0) || (mode == MODE_PRB_PRIMAL && rec_w && I->adj && !I->forward_mode && !ps.rng)) && !rays && !valid_lane && !(I->alpha_film && I->alpha_lane) && !I->batch.n &&
                              !(mq_env0 < 0 ? I->material_queues : mq_env0 != 0);
     if (tape_r) launch_tape_begin(s, C, seed, spp, log_spp, lane_base, n, I->shard_cap, I->result, I->adj, I->tape_la[0], I->tape_lb[0]);
     else if (rays) launch_raygen_rays(s, seed, lane_base, n, rays->n_total, rays->first, rays->o, rays->d, rays->maxt, rays->state, rays->active, I->shard_cap, I->st[0], I->result, cnt_alive(I, 0));
@@ -555,7 +559,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
      * image in I->adj (possibly of a smaller film), which must not be gathered here */
     /* the adjoint image goes to the adjoint raygen (dL per lane; not in forward mode: dL accumulates there) and to the primal raygen of the record tape (dL for its emission terms) */
     else launch_raygen(mode, s, C, seed, spp, log_spp, lane_base, n, I->shard_cap, tape_w ? I->tape_st[0] : I->st[0], I->result, cnt_alive(I, 0),
-                       (I->forward_mode || (mode == MODE_PRB_PRIMAL && !rec_w)) ? nullptr : I->adj, I->dL, ps, first_regen);
+                       (I->forward_mode || (mode == MODE_PRB_PRIMAL && !rec_w)) ? nullptr : I->adj, I->dL, ps, first_regen, I->batch.n ? &I->batch : nullptr);
     prof_mark(I, s, CLS_RAYGEN);
     const bool fwd = mode == MODE_PRB_ADJOINT && I->forward_mode;
     ShadeParams P{ seed, I->max_depth, I->rr_depth, ((mode != MODE_PATH && I->grad_emitters) ? HAR_SHADE_EMITTER_GRADS : 0u)      /* (the primal pass of a backward step too: it traces the shadow rays of samples that only carry a radiance gradient, shade_lane) */ | (I->hide_emitters ? HAR_SHADE_HIDE_EMITTERS : 0u) |
@@ -781,6 +785,11 @@ int check_common(HarSceneImpl *S, HarIntegratorImpl *I, const HarSensor *sensor,
     if (!lower_sensor(*sensor, C, e)) return fail(e);
     if (C.rfilter != 0 && 2 * (uint32_t) ceilf(C.radius - .5f) + 1 > HAR_MAX_FILTER_TAPS) return fail("reconstruction filter radius too large (max 9 taps)");
     if (spp == 0) return fail("spp must be > 0");
+    if (I->batch.n) {        /* batch.cpp:114-119; a crop window / sample border on the batch film is refused (the reference would divide the crop window between the children) */
+        if (C.crop_x || C.crop_y || C.crop_w != sensor->film_width || C.crop_h != sensor->film_height || C.border)
+            return fail("batch sensor: a crop window or sample_border on the batch film is not implemented by hip_ad_rgb");
+        if (C.crop_w % I->batch.n) return fail("BatchSensor: the horizontal resolution (currently " + std::to_string(C.crop_w) + ") must be divisible by the number of child sensors (" + std::to_string(I->batch.n) + ")!");
+    }
     uint64_t total = (uint64_t) C.samp_w * C.samp_h * spp;
     /* 2^32 wavefront limit of JIT variants (integrator.cpp:276-294, common.py:358-363) */
     if (total > 0xffffffffull) return fail("the rendering task exceeds 2^32 - 1 Monte Carlo samples; render in several passes");
@@ -1594,6 +1603,51 @@ int har_sensor_sample_ray(const HarSensor *sensor, uint32_t n, const float *px, 
     HIP_TRY(hipGetLastError());
     return 0;
 }
+/* the camera part of each child, lowered for its own (sub-)film; children with a crop window are refused */
+static int lower_batch_children(const HarSensor *children, uint32_t n, std::vector<DCamera> &cams) {
+    if (!children && n) return fail("null child sensors");
+    cams.resize(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        DSensor C; std::string e;
+        if (!lower_sensor(children[i], C, e)) return fail("batch sensor, child " + std::to_string(i) + ": " + e);
+        if (C.crop_x || C.crop_y || C.crop_w != children[i].film_width || C.crop_h != children[i].film_height)
+            return fail("batch sensor, child " + std::to_string(i) + ": a crop window on a child's film is not implemented by hip_ad_rgb");
+        cams[i] = har::batch_camera(C);
+    }
+    return 0;
+}
+int har_integrator_set_batch_sensors(HarIntegrator I, const HarSensor *children, uint32_t n, void *stream) {
+    if (!I) return fail("null integrator");
+    if (n == 0) { I->batch = DBatch{ nullptr, 0u }; return 0; }
+    std::vector<DCamera> cams;
+    if (lower_batch_children(children, n, cams)) return 1;
+    if (I->batch_cap < n) {
+        (void) hipDeviceSynchronize();      /* renders in flight may still read the old table */
+        dev_free(I->batch_cams, true); I->batch_cams = nullptr; I->batch_cap = 0; I->batch = DBatch{ nullptr, 0u };
+        HIP_TRY(dev_alloc((void **) &I->batch_cams, (size_t) n * sizeof(DCamera)));
+        I->batch_cap = n;
+    }
+    /* in stream order behind the renders that read the previous table; the host copy lives until the copy has run */
+    HIP_TRY(hipMemcpyAsync(I->batch_cams, cams.data(), (size_t) n * sizeof(DCamera), hipMemcpyHostToDevice, (hipStream_t) stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
+    I->batch = DBatch{ I->batch_cams, n };
+    return 0;
+}
+int har_batch_sample_ray(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt, void *stream) {
+    if (n_children == 0) return fail("BatchSensor: at least one child sensor must be specified!");
+    std::vector<DCamera> cams;
+    if (lower_batch_children(children, n_children, cams)) return 1;
+    if (n == 0) return 0;
+    if (!px || !py || !o || !d || !maxt) return fail("null input / output arrays");
+    DCamera *dc = nullptr;
+    HIP_TRY(dev_alloc((void **) &dc, cams.size() * sizeof(DCamera)));
+    hipError_t err = hipMemcpyAsync(dc, cams.data(), cams.size() * sizeof(DCamera), hipMemcpyHostToDevice, (hipStream_t) stream);
+    if (err == hipSuccess) { launch_api_batch_ray((hipStream_t) stream, DBatch{ dc, n_children }, n, px, py, o, d, maxt); err = hipGetLastError(); }
+    if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t) stream);
+    dev_free(dc);
+    HIP_TRY(err);
+    return 0;
+}
 int har_film_put(const HarSensor *sensor, uint32_t n, const float *px, const float *py, const float *values4, float *film, void *stream) {
     DSensor C; std::string e;
     if (!sensor || !lower_sensor(*sensor, C, e)) return fail(e.empty() ? "null sensor" : e);
@@ -1633,6 +1687,7 @@ int har_integrator_destroy(HarIntegrator I) {
         (void) hipDeviceSynchronize();
         dev_free(I->aov.h0, true); dev_free(I->aov.h1, true); dev_free(I->aov.val, true); dev_free(I->aov.status, true);
     }
+    if (I->batch_cams || I->aov_rays) { (void) hipDeviceSynchronize(); dev_free(I->batch_cams, true); dev_free(I->aov_rays, true); }
     prof_destroy(I);
     if (I->twin) { I->twin->free_ws(); prof_destroy(I->twin); }
     if (I->ev_fork) (void) hipEventDestroy(I->ev_fork);
@@ -1739,7 +1794,7 @@ static uint64_t dual_split(HarIntegrator I, uint64_t lb, uint64_t le, hipStream_
     HarIntegratorImpl *T = I->twin;
     T->type = I->type; T->max_depth = I->max_depth; T->rr_depth = I->rr_depth; T->chunk = I->chunk; T->samples_per_pass = I->samples_per_pass;
     T->grad_emitters = I->grad_emitters; T->grad_bsdf_params = I->grad_bsdf_params; T->grad_light_texels = I->grad_light_texels; T->profiling = I->profiling; T->hide_emitters = I->hide_emitters;
-    T->alpha_film = I->alpha_film;
+    T->alpha_film = I->alpha_film; T->batch = I->batch;
     if (T->use_cache != I->use_cache) { (void) hipDeviceSynchronize(); T->free_ws(); T->use_cache = I->use_cache; }
     if (hipEventRecord(I->ev_fork, s) != hipSuccess || hipStreamWaitEvent(I->side_stream, I->ev_fork, 0) != hipSuccess) return le;
     I->twin_used = true;
@@ -2333,8 +2388,25 @@ int har_render_aovs(HarScene S, HarIntegrator I, const HarSensor *sensor, uint32
     I->last_stream = s; I->twin_used = false;
     if (prof_begin(I, s)) return 1;
     const bool deep = aov_deep_stack(S);
+    if (I->batch.n && I->aov_rays_cap < chunk) {
+        if (I->aov_rays) { (void) hipDeviceSynchronize(); dev_free(I->aov_rays, true); I->aov_rays = nullptr; I->aov_rays_cap = 0; }
+        HIP_TRY(dev_alloc((void **) &I->aov_rays, (size_t) chunk * 7 * sizeof(float)));
+        I->aov_rays_cap = chunk;
+    }
     for (uint64_t base = lb; base < le; base += chunk) {
         const uint32_t n = (uint32_t) std::min<uint64_t>(chunk, le - base);
+        if (I->batch.n) {        /* batch sensor: the lanes' camera rays from the child table, then the array-valued flavours of the pass (channel stride n) */
+            float *ro = I->aov_rays, *rd = ro + 3 * (size_t) n, *rt = rd + 3 * (size_t) n;
+            launch_aov_batch_rays(s, C, I->batch, seed, spp, log_spp, (uint32_t) base, n, ro, rd, rt);
+            prof_mark(I, s, CLS_RAYGEN);
+            launch_aov_trace_rays(s, S->ds, deep, n, ro, rd, rt, nullptr, W.h0, W.h1, W.status);
+            prof_mark(I, s, CLS_TRACE);
+            launch_aov_fill_rays(s, S->ds, spec, S->hs.top_mesh_count, n, rd, nullptr, W.h0, W.h1, W.val);
+            prof_mark(I, s, CLS_SHADE);
+            launch_splat_channels(s, C, seed, spp, log_spp, (uint32_t) base, n, W.val, (size_t) n, spec.channels, film);
+            prof_mark(I, s, CLS_SPLAT);
+            continue;
+        }
         launch_aov_trace_lanes(s, S->ds, deep, C, seed, spp, log_spp, (uint32_t) base, n, W.h0, W.h1, W.status);
         prof_mark(I, s, CLS_TRACE);
         launch_aov_fill_lanes(s, S->ds, spec, S->hs.top_mesh_count, C, seed, spp, log_spp, (uint32_t) base, n, W.h0, W.h1, W.val, (size_t) chunk);

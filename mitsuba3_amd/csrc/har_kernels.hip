@@ -273,10 +273,11 @@ __device__ __forceinline__ uint32_t shard_slot(uint32_t i, uint32_t shard_cap) {
     return (tile % HAR_SHARDS) * shard_cap + (tile / HAR_SHARDS) * kBlock + (i % kBlock);
 }
 
-template <int MODE, bool LITE = false>      /* LITE: only the ray (a0, a1) is stored -- the first shading kernel rebuilds the rest of the state (ShadeParams::sensor) */
-__global__ __launch_bounds__(kBlock) void k_raygen(DSensor C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
-                                                   uint32_t n, uint32_t shard_cap, WaveState out, float4 *result, uint32_t *count,
-                                                   const float *adj, float4 *dL, PassState ps) {
+/* the body of k_raygen and k_raygen_batch; `batch`: the child cameras of a batch sensor, a null constant in k_raygen (the batch code folds away there) */
+template <int MODE, bool LITE>
+__device__ __forceinline__ void raygen_body(const DSensor &C, const DBatch *batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                   uint32_t n, uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count,
+                                                   const float *adj, float4 *dL, const PassState &ps) {
     uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i < HAR_SHARDS) {            /* lanes dealt to shard i */
         const uint32_t tiles = (n + kBlock - 1) / kBlock, rem = n % kBlock;
@@ -290,9 +291,9 @@ __global__ __launch_bounds__(kBlock) void k_raygen(DSensor C, uint32_t seed, uin
     PathState st;
     if (ps.rng) {
         float j[2];
-        st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, ps.pass ? ps.rng + i : nullptr, j);
+        st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, ps.pass ? ps.rng + i : nullptr, j, batch);
         ps.jitter[i] = make_float2(j[0], j[1]);
-    } else st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls);
+    } else st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, batch);
     if (LITE) { const uint32_t slot = shard_slot(i, shard_cap); out.a0[slot] = make_float4(st.o.x, st.o.y, st.o.z, st.maxt); out.a1[slot] = make_float4(st.d.x, st.d.y, st.d.z, st.prev_bsdf_pdf); }
     else store_state(out, shard_slot(i, shard_cap), st);
     if (MODE != MODE_PRB_ADJOINT) result[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -314,6 +315,22 @@ __global__ __launch_bounds__(kBlock) void k_raygen(DSensor C, uint32_t seed, uin
         }
         dL[i] = make_float4(g.x, g.y, g.z, 0.f);
     }
+}
+
+template <int MODE, bool LITE = false>      /* LITE: only the ray (a0, a1) is stored -- the first shading kernel rebuilds the rest of the state (ShadeParams::sensor) */
+__global__ __launch_bounds__(kBlock) void k_raygen(DSensor C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                   uint32_t n, uint32_t shard_cap, WaveState out, float4 *result, uint32_t *count,
+                                                   const float *adj, float4 *dL, PassState ps) {
+    raygen_body<MODE, LITE>(C, nullptr, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+}
+/* k_raygen for a batch sensor: C is its wide film, `batch` the child cameras its rays come from (DBatch, har_scene.h).  A kernel of its own, so that the single-sensor
+ * kernel keeps its registers.  Always the full path state (no LITE: the first shading launch of a batch render reads the state instead of rebuilding it, so the shading
+ * kernels need no flavour of their own) */
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_raygen_batch(DSensor C, DBatch batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                         uint32_t n, uint32_t shard_cap, WaveState out, float4 *result, uint32_t *count,
+                                                         const float *adj, float4 *dL, PassState ps) {
+    raygen_body<MODE, false>(C, &batch, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
 }
 
 /* start of the adjoint pass in tape mode (TapeArrays): lane i of the chunk sits in slot shard_slot(i) of bounce 0's wavefront; its L is the primal pass's
@@ -2104,6 +2121,13 @@ __global__ void k_api_sensor_ray(DSensor C, uint32_t n, const float *px, const f
     Vec3 O, D; float mt; sensor_sample_ray(C, px[i], py[i], O, D, mt);
     o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
 }
+/* BatchSensor::sample_ray over caller-supplied film positions (har_batch_sample_ray) */
+__global__ void k_api_batch_ray(DBatch B, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    Vec3 O, D; float mt; batch_sample_ray(B, px[i], py[i], O, D, mt);
+    o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
+}
 __global__ void k_api_film_put(DSensor C, uint32_t n, const float *px, const float *py, const float *values4, float *film) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2126,8 +2150,15 @@ __global__ void k_api_film_put(DSensor C, uint32_t n, const float *px, const flo
 static inline uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 void launch_raygen(int mode, hipStream_t s, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
-                   uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count, const float *adj, float4 *dL, const PassState &ps, bool lite) {
+                   uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count, const float *adj, float4 *dL, const PassState &ps, bool lite, const DBatch *batch) {
     dim3 g(blocks_for(n)), b(kBlock);
+    if (batch && batch->n) {
+        const DBatch B = *batch;
+        if (mode == MODE_PRB_ADJOINT) hipLaunchKernelGGL(k_raygen_batch<MODE_PRB_ADJOINT>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        else if (mode == MODE_PRB_PRIMAL && adj) hipLaunchKernelGGL(k_raygen_batch<MODE_PRB_PRIMAL>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        else hipLaunchKernelGGL(k_raygen_batch<MODE_PATH>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        return;
+    }
     if (lite && mode == MODE_PRB_PRIMAL && adj) hipLaunchKernelGGL((k_raygen<MODE_PRB_PRIMAL, true>), g, b, 0, s, C, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
     else if (lite && mode == MODE_PATH) hipLaunchKernelGGL((k_raygen<MODE_PATH, true>), g, b, 0, s, C, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
     else if (mode == MODE_PRB_ADJOINT) hipLaunchKernelGGL(k_raygen<MODE_PRB_ADJOINT>, g, b, 0, s, C, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
@@ -2394,6 +2425,9 @@ void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const
 }
 void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
     hipLaunchKernelGGL(k_api_sensor_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, o, d, maxt);
+}
+void launch_api_batch_ray(hipStream_t s, const DBatch &B, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+    hipLaunchKernelGGL(k_api_batch_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, B, n, px, py, o, d, maxt);
 }
 void launch_api_film_put(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *values4, float *film) {
     hipLaunchKernelGGL(k_api_film_put, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, values4, film);

@@ -292,3 +292,29 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
     } catch (const std::bad_alloc &) { return har_set_error("har_aov_sample_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_aov_sample_host: ") + ex.what()); }
 }
+
+/* BatchSensor::sample_ray (src/sensors/batch.cpp:132-159) on the host: batch_sample_ray (har_scene.h) -- the function k_raygen_batch runs per lane -- over the children
+ * lowered as har_integrator_set_batch_sensors lowers them.  The twin of har_batch_sample_ray. */
+extern "C" int har_batch_sample_ray_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+    try {
+        if (n_children == 0) return har_set_error("BatchSensor: at least one child sensor must be specified!");
+        if (!children) return har_set_error("null child sensors");
+        std::vector<DCamera> cams(n_children);
+        for (uint32_t i = 0; i < n_children; ++i) {
+            DSensor C; std::string e;
+            if (!lower_sensor(children[i], C, e)) return har_set_error("batch sensor, child " + std::to_string(i) + ": " + e);
+            if (C.crop_x || C.crop_y || C.crop_w != children[i].film_width || C.crop_h != children[i].film_height)
+                return har_set_error("batch sensor, child " + std::to_string(i) + ": a crop window on a child's film is not implemented by hip_ad_rgb");
+            cams[i] = batch_camera(C);
+        }
+        if (n == 0) return 0;
+        if (!px || !py || !o || !d || !maxt) return har_set_error("null input / output arrays");
+        const DBatch B{ cams.data(), n_children };
+        for (uint32_t i = 0; i < n; ++i) {
+            Vec3 O, D; float mt; batch_sample_ray(B, px[i], py[i], O, D, mt);
+            o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_batch_sample_ray_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_batch_sample_ray_host: ") + ex.what()); }
+}

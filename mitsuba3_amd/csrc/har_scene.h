@@ -87,6 +87,22 @@ struct DSensor {
     float ppo_x, ppo_y;          /* scaled principal point offset: film size * principal_point_offset / crop size (perspective.cpp:213-214) */
     uint32_t projection;         /* 0 perspective, 1 orthographic (HarSensor::projection) */
 };
+/* One child of a `batch` sensor (src/sensors/batch.cpp): the camera part of a DSensor lowered for the child's sub-film (film width / child count, full crop).  The
+ * table of children lives in device memory (DBatch); the film part of the render -- lane -> pixel map, filter, splat -- stays the batch sensor's own DSensor. */
+struct DCamera {
+    float s2c[16];
+    float to_world[16];
+    float near_clip, far_clip;
+    float ppo_x, ppo_y;
+    uint32_t projection, pad[3];
+};
+HAR_HD DCamera batch_camera(const DSensor &C) {
+    DCamera c;
+    for (int i = 0; i < 16; ++i) { c.s2c[i] = C.s2c[i]; c.to_world[i] = C.to_world[i]; }
+    c.near_clip = C.near_clip; c.far_clip = C.far_clip; c.ppo_x = C.ppo_x; c.ppo_y = C.ppo_y; c.projection = C.projection; c.pad[0] = c.pad[1] = c.pad[2] = 0u;
+    return c;
+}
+struct DBatch { const DCamera *cams; uint32_t n; };      /* n == 0: no batch, the DSensor is the camera */
 
 struct SurfInt {
     float t;
@@ -755,8 +771,9 @@ HAR_HD float textured_area_pdf_direction(const DScene &S, const DEmitter &E, Vec
     return bitmap_pdf_texture(T, S.emitter_cdf + as_u32(E.radiance[1]), tu, tv) * (dist * dist) / (E.radiance[2] * -dp);
 }
 
-/* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237) */
-HAR_HD void sensor_sample_ray(const DSensor &C, float px, float py, Vec3 &o, Vec3 &d, float &maxt) {
+/* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237); CAM: DSensor, or DCamera (a child of a batch sensor) */
+template <class CAM>
+HAR_HD void sensor_sample_ray(const CAM &C, float px, float py, Vec3 &o, Vec3 &d, float &maxt) {
     const float *M = C.s2c;
     float r0 = M[3], r1 = M[7], r2 = M[11], r3 = M[15];
     px = px + C.ppo_x; py = py + C.ppo_y;                              /* perspective.cpp:216-221 */
@@ -833,9 +850,31 @@ HAR_HD LaneSample lane_sample(const DSensor &C, uint32_t idx, uint32_t spp, uint
     L.pos_x = L.ipos_x + jx; L.pos_y = L.ipos_y + jy;
     return L;
 }
-HAR_HD void lane_camera_ray(const DSensor &C, const LaneSample &L, Vec3 &o, Vec3 &d, float &maxt) {
+/* BatchSensor::sample_ray (src/sensors/batch.cpp:138-145): the child a film position falls on and the position on that child's film.  The product and the difference
+ * are two rounded fp32 operations, as in the reference (the build keeps -ffp-contract=off); a position of 1 or beyond lands on the last child with px2 >= 1 */
+HAR_HD uint32_t batch_select(float px, uint32_t n, float &px2) {
+    const float idx_f = px * (float) n;
+    const uint32_t idx_u = (uint32_t) idx_f;
+    px2 = idx_f - (float) idx_u;
+    return idx_u < n - 1u ? idx_u : n - 1u;
+}
+/* the ray of child `batch_select(px)` of the table.  Device: the lanes of a wave are consecutive samples of consecutive pixels of a row, so all of them pick the
+ * same child except where the wave crosses a seam (or a row's end) -- the uniform wave reads the record through an index it holds in a scalar register (scalar loads,
+ * one copy of the 160-byte record per wave), the others read theirs per lane. */
+HAR_HD void batch_sample_ray(const DBatch &B, float px, float py, Vec3 &o, Vec3 &d, float &maxt) {
+    float px2;
+    const uint32_t index = batch_select(px, B.n, px2);
+#if defined(__HIP_DEVICE_COMPILE__)
+    const uint32_t first = (uint32_t) __builtin_amdgcn_readfirstlane((int) index);
+    if (__builtin_amdgcn_ballot_w64(index != first) == 0ull) { sensor_sample_ray(B.cams[first], px2, py, o, d, maxt); return; }
+#endif
+    sensor_sample_ray(B.cams[index], px2, py, o, d, maxt);
+}
+/* `batch` (optional): the children of a batch sensor -- C is then the batch sensor's wide film, whose crop window is the full film */
+HAR_HD void lane_camera_ray(const DSensor &C, const LaneSample &L, Vec3 &o, Vec3 &d, float &maxt, const DBatch *batch = nullptr) {
     float sx = 1.f / (float) C.crop_w, sy = 1.f / (float) C.crop_h;
     float ox = -(float) C.crop_x * sx, oy = -(float) C.crop_y * sy;
+    if (batch) { batch_sample_ray(*batch, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), o, d, maxt); return; }
     sensor_sample_ray(C, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), o, d, maxt);
 }
 

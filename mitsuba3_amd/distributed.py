@@ -10,7 +10,7 @@ of the weight film and the gradient buffers).  The reference has no multi-GPU pa
 import torch
 import torch.distributed as dist
 
-from .core import develop_film, _torch
+from .core import develop_film, _torch, _refuse_batch
 
 
 def lane_range(total_lanes, rank, world_size, granule=1):
@@ -144,6 +144,7 @@ def render_distributed(scene, integrator=None, sensor=0, seed=0, spp=0, develop=
     if getattr(integrator, "type", None) == "aov":
         raise RuntimeError("render_distributed: the `aov` integrator is not implemented by hip_ad_rgb for distributed renders")
     s = scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+    _refuse_batch(s, "render_distributed / render_backward_distributed")
     if spp:
         s.sampler().set_sample_count(spp)
     spp = s.sampler().sample_count()
@@ -202,6 +203,7 @@ def render_backward_distributed(scene, grad_in, integrator=None, sensor=0, seed=
     if getattr(integrator, "type", None) == "aov":
         raise RuntimeError("render_distributed: the `aov` integrator is not implemented by hip_ad_rgb for distributed renders")
     s = scene.sensors()[sensor] if isinstance(sensor, int) else sensor
+    _refuse_batch(s, "render_distributed / render_backward_distributed")
     if spp:
         s.sampler().set_sample_count(spp)
     spp = s.sampler().sample_count()
