@@ -153,10 +153,15 @@ typedef struct HarSensor {
     uint32_t sample_border;       /* Film::sample_border (src/render/film.cpp:29-32): != 0 -> the lane -> pixel map of render() runs over the crop window
                                    * enlarged by rfilter->border_size() = ceil(radius - 1/2 - 2 RayEpsilon) pixels on every side
                                    * (src/render/integrator.cpp:162-165, 322-339); the film itself keeps the crop size, splats are clipped to it */
-    float    principal_point_offset_x, principal_point_offset_y;   /* PerspectiveCamera `principal_point_offset_x / _y` (src/sensors/perspective.cpp:147-150): sample_ray adds
-                                   * film_size * offset / crop_size to the film position before it is taken to the near plane (:213-221) */
+    /* PerspectiveCamera `principal_point_offset_x / _y` (src/sensors/perspective.cpp:147-150): sample_ray adds film_size * offset / crop_size to the film position before it
+     * is taken to the near plane (:213-221).  A thin lens (projection 2) has no principal point offset -- ThinLensCamera's constructor does not query it -- and keeps its
+     * two parameters in the same two words, so the record has one size and one layout for every camera model (records are compared and copied byte-wise):
+     *   aperture_radius: radius of the lens, > 0 (thinlens.cpp:156-161);  focus_distance: distance of the plane of focus along the optical axis, > 0 (sensor.cpp:127) */
+    union { float principal_point_offset_x; float aperture_radius; };
+    union { float principal_point_offset_y; float focus_distance; };
     uint32_t projection;          /* 0 = PerspectiveCamera (src/sensors/perspective.cpp), 1 = OrthographicCamera (src/sensors/orthographic.cpp:131-157): sample_to_camera is
-                                   * the inverse of orthographic_projection (sensor.h:272-307), an affine map; rays start on the near plane and run along to_world's +z */
+                                   * the inverse of orthographic_projection (sensor.h:272-307), an affine map; rays start on the near plane and run along to_world's +z,
+                                   * 2 = ThinLensCamera (src/sensors/thinlens.cpp:219-257): sample_to_camera as for 0; aperture_radius and focus_distance above */
 } HarSensor;
 
 /* counters of one render call (all lanes), read back with har_render_stats */
@@ -374,6 +379,30 @@ int har_sensor_sample_ray(const HarSensor *sensor, uint32_t n, const float *pos_
 int har_integrator_set_batch_sensors(HarIntegrator integrator, const HarSensor *children, uint32_t n, void *stream);
 int har_batch_sample_ray(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, float *o, float *d, float *maxt, void *stream);
 int har_batch_sample_ray_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, float *o, float *d, float *maxt);
+/* Thin lens (HarSensor::projection = 2): the sensor needs an aperture sample (Sensor::needs_aperture_sample()).  render() draws it per lane right behind the pixel
+ * jitter (integrator.cpp:464-470), so the path's first draw is the stream's FIFTH number; a batch sensor draws it on every lane as soon as one child is a thin lens.
+ *   har_sensor_sample_ray_aperture / har_batch_sample_ray_aperture: sample_ray with the aperture samples `ap_x` / `ap_y` in [0,1]^2 (DEVICE arrays; null = (0.5, 0.5),
+ *     the centre of the lens); pinhole cameras ignore them.  har_sensor_sample_ray and har_batch_sample_ray are these with null aperture arrays.
+ *   ..._host: the same per-lane code compiled for the host, all pointers HOST -- no GPU needed; device and host agree bit for bit. */
+int har_sensor_sample_ray_aperture(const HarSensor *sensor, uint32_t n, const float *pos_x, const float *pos_y, const float *ap_x, const float *ap_y,
+                                   float *o, float *d, float *maxt, void *stream);
+int har_sensor_sample_ray_aperture_host(const HarSensor *sensor, uint32_t n, const float *pos_x, const float *pos_y, const float *ap_x, const float *ap_y,
+                                        float *o, float *d, float *maxt);
+int har_batch_sample_ray_aperture(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, const float *ap_x, const float *ap_y,
+                                  float *o, float *d, float *maxt, void *stream);
+int har_batch_sample_ray_aperture_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *pos_x, const float *pos_y, const float *ap_x, const float *ap_y,
+                                       float *o, float *d, float *maxt);
+/* The camera rays of lanes [lane_begin, lane_begin + n) of render() at `seed` / `spp` on the HOST: raygen_lane -- the function the ray generation kernels run -- per lane.
+ * `children` / `n_children` as for har_integrator_set_batch_sensors (0: `sensor` is the camera).  Outputs (HOST, each may be null): o, d 3 x n, maxt n, pos 2 x n the film
+ * position of the sample, state n the lane's PCG32 state behind the draws of ray generation (two for pinhole cameras, four with a thin lens).  `resume` (n states, or
+ * null): the lanes continue these states instead of their seeds -- pass > 0 of a multi-pass render. */
+int har_raygen_lanes_host(const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp, uint32_t lane_begin, uint32_t n,
+                          const uint64_t *resume, float *o, float *d, float *maxt, float *pos, uint64_t *state);
+/* The forward `path` render of hip_ad_rgb on the HOST, serially, for small films (at most 2^22 lanes): per lane raygen_lane, the closest-hit traversal, shade_lane with the
+ * JIT variants' draws and the splat of ImageBlock::put -- the functions the kernels run, compiled for the CPU.  A test instrument, never a fall-back: no hip_ad_rgb entry
+ * point calls it.  `film` (HOST, H x W x 4 of the crop window, {R, G, B, W}) is accumulated into; children / n_children as for har_raygen_lanes_host. */
+int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
+                          int32_t max_depth, int32_t rr_depth, float *film);
 /* ImageBlock::put (src/render/imageblock.cpp:187-540): film is H x W x 4 {R,G,B,W} */
 int har_film_put(const HarSensor *sensor, uint32_t n, const float *pos_x, const float *pos_y,
                  const float *values4 /*[n][4]*/, float *film, void *stream);
@@ -649,6 +678,13 @@ int har_perspective_sensor(const float to_world[32], double fov, const char *fov
                            float far_clip, uint32_t width, uint32_t height, uint32_t crop_x,
                            uint32_t crop_y, uint32_t crop_w, uint32_t crop_h, uint32_t rfilter,
                            float stddev, HarSensor *out);
+/* ThinLensCamera ctor + update_camera_transforms (src/sensors/thinlens.cpp:152-213): har_perspective_sensor's record with projection = 2, `aperture_radius` (0 becomes
+ * dr::Epsilon<float>, :158-161; negative or not finite: error 4) and `focus_distance` (> 0, else error 5); errors 1-3 as har_perspective_sensor.  The caller refuses a
+ * to_world with scale (:163-164). */
+int har_thinlens_sensor(const float to_world[32], double fov, const char *fov_axis, float near_clip,
+                        float far_clip, float aperture_radius, float focus_distance, uint32_t width, uint32_t height, uint32_t crop_x,
+                        uint32_t crop_y, uint32_t crop_w, uint32_t crop_h, uint32_t rfilter,
+                        float stddev, HarSensor *out);
 /* Rectangle::initialize (src/shapes/rectangle.cpp:108-156): 4 vertex + 2 face records baked with
  * to_world, plus m_frame.n and m_inv_surface_area for area-light sampling */
 int har_shape_rectangle(const float to_world[32], int flip_normals, float vertices[32], uint32_t faces[8],

@@ -63,14 +63,23 @@ class HarSceneDesc(C.Structure):
                 ("emitters", C.POINTER(HarEmitter)), ("emitter_count", C.c_uint32), ("pad4", C.c_uint32)]
 
 
+class _PpoXOrAperture(C.Union):          # a thin lens (projection 2) has no principal point offset: its two parameters live in the same words (hip_ad_rgb.h)
+    _fields_ = [("principal_point_offset_x", C.c_float), ("aperture_radius", C.c_float)]
+
+
+class _PpoYOrFocus(C.Union):
+    _fields_ = [("principal_point_offset_y", C.c_float), ("focus_distance", C.c_float)]
+
+
 class HarSensor(C.Structure):
+    _anonymous_ = ("_ppo_x", "_ppo_y")
     _fields_ = [("sample_to_camera", C.c_float * 16), ("to_world", C.c_float * 16),
                 ("near_clip", C.c_float), ("far_clip", C.c_float),
                 ("film_width", C.c_uint32), ("film_height", C.c_uint32),
                 ("crop_offset_x", C.c_uint32), ("crop_offset_y", C.c_uint32),
                 ("crop_width", C.c_uint32), ("crop_height", C.c_uint32),
                 ("rfilter", C.c_uint32), ("rfilter_stddev", C.c_float), ("rfilter_param1", C.c_float),
-                ("sample_border", C.c_uint32), ("principal_point_offset_x", C.c_float), ("principal_point_offset_y", C.c_float),
+                ("sample_border", C.c_uint32), ("_ppo_x", _PpoXOrAperture), ("_ppo_y", _PpoYOrFocus),
                 ("projection", C.c_uint32)]
 
 
@@ -148,6 +157,12 @@ SIGNATURES = {
     "har_mesh_compute_normals": (C.c_int, [C.c_uint32, vp, C.c_uint32, vp]),
     "har_mesh_free": (None, [vp]),
     "har_sensor_sample_ray": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "har_sensor_sample_ray_aperture": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "har_sensor_sample_ray_aperture_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "har_batch_sample_ray_aperture": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "har_batch_sample_ray_aperture_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "har_raygen_lanes_host": (C.c_int, [C.POINTER(HarSensor), C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, f32p, f32p, f32p, f32p, vp]),
+    "har_render_lanes_host": (C.c_int, [C.POINTER(HarSceneDesc), C.POINTER(HarSensor), C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, f32p]),
     "har_integrator_set_batch_sensors": (C.c_int, [vp, C.POINTER(HarSensor), C.c_uint32, vp]),
     "har_batch_sample_ray": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "har_batch_sample_ray_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p]),
@@ -186,6 +201,9 @@ SIGNATURES = {
     "har_perspective_sensor": (C.c_int, [f32p, C.c_double, C.c_char_p, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
                                          C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
                                          C.POINTER(HarSensor)]),
+    "har_thinlens_sensor": (C.c_int, [f32p, C.c_double, C.c_char_p, C.c_float, C.c_float, C.c_float, C.c_float, C.c_uint32, C.c_uint32,
+                                      C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_float,
+                                      C.POINTER(HarSensor)]),
     "har_shape_rectangle": (C.c_int, [f32p, C.c_int, f32p, u32p, f32p, f32p]),
     "har_shape_cube": (C.c_int, [f32p, f32p, u32p]),
     "har_mesh_transform": (C.c_int, [f32p, C.c_uint32, f32p, C.c_uint32, u32p, C.c_int]),

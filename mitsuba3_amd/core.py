@@ -11,6 +11,7 @@ import ctypes as C
 import math
 import os
 import re
+import warnings
 
 import numpy as np
 
@@ -46,6 +47,8 @@ def _render_scalar(scene, integrator, sensor, seed, spp, threads=0, block_size=0
     if integrator.type != 'path':
         raise RuntimeError("scalar_rgb: only the `path` integrator is part of the config-1 plumbing path")
     _refuse_batch(sensor, "scalar_rgb (har_render_scalar)")
+    if getattr(sensor, 'kind', None) == 'thinlens':
+        raise RuntimeError("scalar_rgb: the `thinlens` sensor is not implemented by the scalar_rgb variant (hip_ad_rgb only)")
     if integrator.hide_emitters or sensor.film().alpha or integrator.samples_per_pass is not None:
         raise RuntimeError("scalar_rgb: hide_emitters, rgba films and samples_per_pass are not part of the config-1 plumbing path")
     if spp:
@@ -437,7 +440,7 @@ def _cube(props):
 # ObjectType of every plugin this variant has (include/mitsuba/core/object.h: ObjectType; PluginManager::create_object checks it, plugin.cpp:258-263).
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
-    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
+    'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
     'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
@@ -685,7 +688,7 @@ class Film:
 
 
 class Sensor:
-    """PerspectiveCamera (src/sensors/perspective.cpp) and OrthographicCamera (src/sensors/orthographic.cpp)."""
+    """PerspectiveCamera (src/sensors/perspective.cpp), OrthographicCamera (src/sensors/orthographic.cpp) and ThinLensCamera (src/sensors/thinlens.cpp)."""
 
     def __init__(self, props):
         self.props = dict(props)
@@ -694,6 +697,11 @@ class Sensor:
         if self.kind == 'orthographic':
             _check_props('orthographic', props, ('to_world', 'near_clip', 'far_clip', 'film', 'sampler', 'shutter_open', 'shutter_close'), children=('film', 'sampler'),
                          slots={'film': ('film',), 'sampler': ('sampler',)}, slot_kind=())
+        elif self.kind == 'thinlens':            # thinlens.cpp:152-169: no principal point offsets; `aperture_radius` is required
+            _check_props('thinlens', props, ('to_world', 'fov', 'fov_axis', 'focal_length', 'near_clip', 'far_clip', 'film', 'sampler', 'shutter_open', 'shutter_close', 'focus_distance',
+                                             'aperture_radius'), children=('film', 'sampler'), slots={'film': ('film',), 'sampler': ('sampler',)}, slot_kind=())
+            if 'aperture_radius' not in props:
+                raise RuntimeError("Property \"aperture_radius\" has not been specified!")
         else:
             _check_props('perspective', props, ('to_world', 'fov', 'fov_axis', 'focal_length', 'near_clip', 'far_clip', 'film', 'sampler', 'shutter_open', 'shutter_close', 'focus_distance',
                                                 'principal_point_offset_x', 'principal_point_offset_y'), children=('film', 'sampler'),
@@ -709,7 +717,21 @@ class Sensor:
         if 'fov' in props and 'focal_length' in props:
             raise RuntimeError("Please specify either a focal length ('focal_length') or a field of view ('fov')!")
         self.near_clip = float(props.get('near_clip', 1e-2)); self.far_clip = float(props.get('far_clip', 1e4))
+        if self.kind == 'thinlens':
+            self.aperture_radius = float(props['aperture_radius'])
+            self.focus_distance_ = float(props.get('focus_distance', self.far_clip))        # sensor.cpp:127
+            if self.aperture_radius == 0.0:          # thinlens.cpp:158-161
+                self.aperture_radius = float(np.float32(2.0 ** -24))
+                warnings.warn("Can't have a zero aperture radius -- setting to %f" % self.aperture_radius)
         self.update()
+
+    def needs_aperture_sample(self):
+        """Sensor::needs_aperture_sample() (sensor.h): render() draws an aperture sample per lane right behind the pixel jitter"""
+        return self.kind == 'thinlens'
+
+    def focus_distance(self):
+        """ProjectiveCamera::focus_distance() (sensor.cpp:127): `focus_distance`, by default far_clip"""
+        return self.focus_distance_ if self.kind == 'thinlens' else float(self.props.get('focus_distance', self.far_clip))
 
     def update(self):
         f = self.m_film
@@ -730,13 +752,22 @@ class Sensor:
             value = float(fl[:-2] if fl.endswith('mm') else fl)
             fov = 2.0 * math.degrees(math.atan(math.sqrt(36 * 36 + 24 * 24) / (2.0 * value))); fov_axis = 'diagonal'
         s = _capi.HarSensor()
-        rc = lib().har_perspective_sensor(_fp(self.to_world.data), fov, fov_axis.encode(), self.near_clip, self.far_clip,
-                                          f.width, f.height, f.crop_offset_[0], f.crop_offset_[1], f.crop_size_[0], f.crop_size_[1],
-                                          f.rfilter, f.stddev, C.byref(s))
+        if self.kind == 'thinlens':          # ThinLensCamera::update_camera_transforms (thinlens.cpp:190-213)
+            rc = lib().har_thinlens_sensor(_fp(self.to_world.data), fov, fov_axis.encode(), self.near_clip, self.far_clip, self.aperture_radius, self.focus_distance_,
+                                           f.width, f.height, f.crop_offset_[0], f.crop_offset_[1], f.crop_size_[0], f.crop_size_[1], f.rfilter, f.stddev, C.byref(s))
+            if rc == 4:
+                raise RuntimeError("thinlens: aperture_radius must be non-negative and finite")
+            if rc == 5:
+                raise RuntimeError("thinlens: focus_distance must be positive and finite")
+        else:
+            rc = lib().har_perspective_sensor(_fp(self.to_world.data), fov, fov_axis.encode(), self.near_clip, self.far_clip,
+                                              f.width, f.height, f.crop_offset_[0], f.crop_offset_[1], f.crop_size_[0], f.crop_size_[1],
+                                              f.rfilter, f.stddev, C.byref(s))
         s.rfilter_param1 = f.rf_param1
         s.sample_border = 1 if f.sample_border_ else 0
-        # perspective.cpp:147-150: the principal point, as a fraction of the film size
-        s.principal_point_offset_x = float(self.props.get('principal_point_offset_x', 0.0)); s.principal_point_offset_y = float(self.props.get('principal_point_offset_y', 0.0))
+        if self.kind != 'thinlens':
+            # perspective.cpp:147-150: the principal point, as a fraction of the film size
+            s.principal_point_offset_x = float(self.props.get('principal_point_offset_x', 0.0)); s.principal_point_offset_y = float(self.props.get('principal_point_offset_y', 0.0))
         if rc == 2:
             raise RuntimeError("The 'fov_axis' parameter must be set to one of 'smaller', 'larger', 'diagonal', 'x', or 'y'!")
         if rc == 3:
@@ -774,12 +805,46 @@ class Sensor:
         return self.m_sampler
 
     def sample_ray(self, time, sample1, sample2, sample3=None):
-        """PerspectiveCamera::sample_ray: sample2 is the film position in [0,1]^2, tensor [2, n]."""
+        """Sensor::sample_ray: sample2 is the film position in [0,1]^2, tensor [2, n]; sample3 the aperture sample of a thin lens, tensor [2, n] (None: the centre of the
+        lens; pinhole cameras ignore it)."""
         torch = _torch(); dev = _device()
         p = torch.as_tensor(sample2, dtype=torch.float32, device=dev).reshape(2, -1).contiguous(); n = p.shape[1]
+        a = _aperture_tensor(sample3, n) if self.kind == 'thinlens' else None
         o = torch.empty((3, n), dtype=torch.float32, device=dev); d = torch.empty_like(o); mt = torch.empty(n, dtype=torch.float32, device=dev)
-        check(lib().har_sensor_sample_ray(C.byref(self.har), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
+        if a is None:
+            check(lib().har_sensor_sample_ray(C.byref(self.har), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
+        else:
+            check(lib().har_sensor_sample_ray_aperture(C.byref(self.har), n, _ptr(p[0]), _ptr(p[1]), _ptr(a[0]), _ptr(a[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
         return Ray3f(o, d, mt), torch.ones(n, device=dev)
+
+    def sample_ray_host(self, sample2, sample3=None):
+        """the same on the host (har_sensor_sample_ray_aperture_host; no GPU): sample2, sample3 = 2 x n numpy arrays -> (o 3 x n, d 3 x n, maxt n)"""
+        p = np.ascontiguousarray(np.asarray(sample2, np.float32).reshape(2, -1)); n = p.shape[1]
+        px = np.ascontiguousarray(p[0]); py = np.ascontiguousarray(p[1])
+        ax, ay = _aperture_host(sample3, n)
+        o = np.empty((3, n), np.float32); d = np.empty((3, n), np.float32); mt = np.empty(n, np.float32)
+        check(lib().har_sensor_sample_ray_aperture_host(C.byref(self.har), n, _fp(px), _fp(py), ax if ax is None else _fp(ax), ay if ay is None else _fp(ay), _fp(o), _fp(d), _fp(mt)))
+        return o, d, mt
+
+
+def _aperture_tensor(sample3, n):
+    """the aperture samples as a contiguous 2 x n device tensor, or None"""
+    if sample3 is None:
+        return None
+    torch = _torch()
+    a = torch.as_tensor(sample3, dtype=torch.float32, device=_device()).reshape(2, -1).contiguous()
+    if a.shape[1] != n:
+        raise RuntimeError("sample_ray(): sample3 (the aperture sample) must have as many entries as sample2")
+    return a
+
+
+def _aperture_host(sample3, n):
+    if sample3 is None:
+        return None, None
+    a = np.ascontiguousarray(np.asarray(sample3, np.float32).reshape(2, -1))
+    if a.shape[1] != n:
+        raise RuntimeError("sample_ray(): sample3 (the aperture sample) must have as many entries as sample2")
+    return np.ascontiguousarray(a[0]), np.ascontiguousarray(a[1])
 
 
 class BatchSensor(Sensor):
@@ -848,22 +913,38 @@ class BatchSensor(Sensor):
     def x_fov(self):
         raise RuntimeError("batch: the batch sensor has no field of view of its own; see its children")
 
+    def needs_aperture_sample(self):
+        """batch.cpp:121-125: as soon as ONE child needs an aperture sample, every lane of the batch draws one"""
+        return any(c.needs_aperture_sample() for c in self.m_sensors)
+
+    def focus_distance(self):
+        raise RuntimeError("batch: the batch sensor has no focus distance of its own; see its children")
+
     def sample_ray(self, time, sample1, sample2, sample3=None):
-        """BatchSensor::sample_ray (batch.cpp:132-159): sample2 is the position on the wide film in [0,1]^2, tensor [2, n]."""
+        """BatchSensor::sample_ray (batch.cpp:132-159): sample2 is the position on the wide film in [0,1]^2, tensor [2, n]; sample3 the aperture sample that thin-lens
+        children use."""
         torch = _torch(); dev = _device()
         p = torch.as_tensor(sample2, dtype=torch.float32, device=dev).reshape(2, -1).contiguous(); n = p.shape[1]
+        a = _aperture_tensor(sample3, n) if self.needs_aperture_sample() else None
         o = torch.empty((3, n), dtype=torch.float32, device=dev); d = torch.empty_like(o); mt = torch.empty(n, dtype=torch.float32, device=dev)
         ch = self.children_har()
-        check(lib().har_batch_sample_ray(ch, len(ch), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
+        if a is None:
+            check(lib().har_batch_sample_ray(ch, len(ch), n, _ptr(p[0]), _ptr(p[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
+        else:
+            check(lib().har_batch_sample_ray_aperture(ch, len(ch), n, _ptr(p[0]), _ptr(p[1]), _ptr(a[0]), _ptr(a[1]), _ptr(o), _ptr(d), _ptr(mt), _stream()))
         return Ray3f(o, d, mt), torch.ones(n, device=dev)
 
-    def sample_ray_host(self, sample2):
-        """the same on the host (har_batch_sample_ray_host; no GPU): sample2 = 2 x n numpy array -> (o 3 x n, d 3 x n, maxt n)"""
+    def sample_ray_host(self, sample2, sample3=None):
+        """the same on the host (har_batch_sample_ray_aperture_host; no GPU): sample2, sample3 = 2 x n numpy arrays -> (o 3 x n, d 3 x n, maxt n)"""
         p = np.ascontiguousarray(np.asarray(sample2, np.float32).reshape(2, -1)); n = p.shape[1]
         px = np.ascontiguousarray(p[0]); py = np.ascontiguousarray(p[1])
+        ax, ay = _aperture_host(sample3, n)
         o = np.empty((3, n), np.float32); d = np.empty((3, n), np.float32); mt = np.empty(n, np.float32)
         ch = self.children_har()
-        check(lib().har_batch_sample_ray_host(ch, len(ch), n, _fp(px), _fp(py), _fp(o), _fp(d), _fp(mt)))
+        if ax is None:
+            check(lib().har_batch_sample_ray_host(ch, len(ch), n, _fp(px), _fp(py), _fp(o), _fp(d), _fp(mt)))
+        else:
+            check(lib().har_batch_sample_ray_aperture_host(ch, len(ch), n, _fp(px), _fp(py), _fp(ax), _fp(ay), _fp(o), _fp(d), _fp(mt)))
         return o, d, mt
 
 
@@ -2476,7 +2557,9 @@ class Scene:
                 sensors.append((k, s))
         for k, s in sensors:
             keys[k + ".to_world"] = ("sensor", s)
-            if s.kind != 'orthographic':          # PerspectiveCamera::traverse (perspective.cpp:155-160)
+            if s.kind == 'thinlens':              # ThinLensCamera::traverse (thinlens.cpp:171-177)
+                keys[k + ".aperture_radius"] = ("aperture_radius", s); keys[k + ".focus_distance"] = ("focus_distance", s); keys[k + ".x_fov"] = ("x_fov", s)
+            elif s.kind != 'orthographic':        # PerspectiveCamera::traverse (perspective.cpp:155-160)
                 keys[k + ".x_fov"] = ("x_fov", s)
                 keys[k + ".principal_point_offset_x"] = ("ppo_x", s); keys[k + ".principal_point_offset_y"] = ("ppo_y", s)
         for i, key in enumerate(self._emitter_order):
@@ -2508,6 +2591,10 @@ class Scene:
             return np.asarray([b.x_fov()], np.float32)
         if kind in ("ppo_x", "ppo_y"):
             return np.asarray([float(b.props.get('principal_point_offset_' + kind[-1], 0.0))], np.float32)
+        if kind == "aperture_radius":
+            return np.asarray([b.aperture_radius], np.float32)
+        if kind == "focus_distance":
+            return np.asarray([b.focus_distance_], np.float32)
         if kind == "position":
             return np.asarray(self.emitters[b]["to_world"][9:12], np.float32).copy()
         if kind in ("cutoff_angle", "beam_width"):
@@ -2588,6 +2675,30 @@ class Scene:
                 raise RuntimeError("perspective: the principal point offset is not finite")
             b.props['principal_point_offset_' + kind[-1]] = v
             b.update()
+            return
+        if kind in ("aperture_radius", "focus_distance"):      # ThinLensCamera::parameters_changed -> update_camera_transforms (thinlens.cpp:179-188); the record is re-lowered
+            v = float(np.asarray(value, np.float32).reshape(-1)[0])
+            if kind == "aperture_radius":
+                if not (v >= 0.0) or not math.isfinite(v):
+                    raise RuntimeError("thinlens: aperture_radius must be non-negative and finite")
+                old = b.aperture_radius
+                b.aperture_radius = v if v != 0.0 else float(np.float32(2.0 ** -24))
+                b.props['aperture_radius'] = b.aperture_radius
+            else:
+                if not (v > 0.0) or not math.isfinite(v):
+                    raise RuntimeError("thinlens: focus_distance must be positive and finite")
+                old = b.focus_distance_
+                b.focus_distance_ = v
+                b.props['focus_distance'] = v
+            try:
+                b.update()
+            except Exception:
+                if kind == "aperture_radius":
+                    b.aperture_radius = old; b.props['aperture_radius'] = old
+                else:
+                    b.focus_distance_ = old; b.props['focus_distance'] = old
+                b.update()
+                raise
             return
         if kind == "x_fov":                  # PerspectiveCamera::parameters_changed -> update_camera_transforms (perspective.cpp:163-198): the projection follows the new angle
             fov = float(np.asarray(value, np.float32).reshape(-1)[0])
@@ -3311,6 +3422,7 @@ for _name, _fn in {
     'aov': lambda p, n, k: AOVIntegrator(p, n),
     'perspective': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),      # EVERY child object through the registry
     'orthographic': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
+    'thinlens': lambda p, n, k: Sensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
     'batch': lambda p, n, k: BatchSensor({kk: (_resolve(v, n, kk) if isinstance(v, dict) and 'type' in v else v) for kk, v in p.items()}),
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),

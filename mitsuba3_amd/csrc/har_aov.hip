@@ -49,13 +49,15 @@ __global__ __launch_bounds__(kBlock) void k_aov_trace(DScene S, DSensor C, uint3
     h1[i] = make_uint2(hit.shape, hit.inst);
 }
 
-/* camera rays of the lanes of a BATCH sensor's render (k_raygen_batch's rays), SoA with stride n: the AOV pass of a batch sensor then runs the _rays flavours of the
- * kernels below on them, which keeps the single-sensor flavours as they are */
+/* camera rays of the lanes of a BATCH sensor's render (k_raygen_batch's rays) or of a render through a thin lens (k_raygen_lens's; batch.n == 0: C is the lens), SoA with
+ * stride n: the AOV pass of such a sensor then runs the _rays flavours of the kernels below on them, which keeps the single-sensor flavours as they are */
 __global__ __launch_bounds__(kBlock) void k_aov_batch_rays(DSensor C, DBatch batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
                                                            float *o, float *d, float *maxt) {
     const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    LaneSample ls; const PathState st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, &batch);
+    LaneSample ls; PathState st;
+    if (batch.n) st = raygen_lane<true>(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, &batch);
+    else st = raygen_lane<true>(C, seed, spp, log_spp, lane_base + i, ls);
     o[i] = st.o.x; o[n + i] = st.o.y; o[2 * (size_t) n + i] = st.o.z; d[i] = st.d.x; d[n + i] = st.d.y; d[2 * (size_t) n + i] = st.d.z; maxt[i] = st.maxt;
 }
 

@@ -212,14 +212,8 @@ struct Microfacet {
             }
             slope_x = erfinv_(x); slope_y = erfinv_(fms_(2.f, sy, 1.f));
         } else {
-            /* warp::square_to_uniform_disk_concentric, warp.h:54-90 */
-            float x = fms_(2.f, sx, 1.f), y = fms_(2.f, sy, 1.f);
-            bool is_zero = x == 0.f && y == 0.f, q13 = fabsf(x) < fabsf(y);
-            float r = q13 ? y : x, rp = q13 ? x : y, phi = 0.25f * HAR_PI * rp / r;
-            if (q13) phi = 0.5f * HAR_PI - phi;
-            if (is_zero) phi = 0.f;
-            float s, c; sincos_(phi, s, c);
-            float px = r * c, py = r * s;
+            float px, py;
+            square_to_uniform_disk_concentric(sx, sy, px, py);
             float sc = 0.5f * (1.f + cos_theta_i);
             py = lerp_(safe_sqrt_(1.f - sqr_(px)), py, sc);
             float z = safe_sqrt_(1.f - fma_(py, py, px * px));

@@ -179,7 +179,7 @@ struct HarIntegratorImpl {
     bool hide_emitters = false;           /* Integrator property (integrator.cpp:29) */
     /* har_integrator_set_batch_sensors: the child cameras of a batch sensor (DEVICE table, a block of its own) -- batch.n != 0: the `sensor` of the render calls is the
      * batch sensor's wide film and the camera rays come from the table (k_raygen_batch) */
-    DBatch batch{ nullptr, 0u }; DCamera *batch_cams = nullptr; uint32_t batch_cap = 0;
+    DBatch batch{ nullptr, 0u, 0u }; DCamera *batch_cams = nullptr; uint32_t batch_cap = 0;
     float *aov_rays = nullptr; size_t aov_rays_cap = 0;      /* AOV pass of a batch sensor: the chunk's camera rays (7 floats per lane) */
     bool forward_mode = false;            /* har_render_forward in progress: the adjoint kernels read tangents and accumulate differential radiance */
     float *alpha_film = nullptr;          /* user buffer (DEVICE, H x W x 4: channel 3 accumulates w * alpha) of har_integrator_set_alpha_film, or null */
@@ -551,7 +551,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
      * bounce-0 wavefront nobody else reads (no alpha / validity flags, no material queues, no tape); the passes of a multi-pass forward render resume their samplers from the pass state in both kernels.  HAR_FIRST_VERTEX=0 switches it off (A/B) */
     static const bool first_env = !(getenv("HAR_FIRST_VERTEX") && atoi(getenv("HAR_FIRST_VERTEX")) == 0);
     static const int mq_env0 = getenv("HAR_MATERIAL_QUEUES") ? atoi(getenv("HAR_MATERIAL_QUEUES")) : -1;
-    const bool first_regen = first_env && ((mode == MODE_PATH && cache_mode == 0) || (mode == MODE_PRB_PRIMAL && rec_w && I->adj && !I->forward_mode && !ps.rng)) && !rays && !valid_lane && !(I->alpha_film && I->alpha_lane) && !I->batch.n &&
+    const bool first_regen = first_env && ((mode == MODE_PATH && cache_mode == 0) || (mode == MODE_PRB_PRIMAL && rec_w && I->adj && !I->forward_mode && !ps.rng)) && !rays && !valid_lane && !(I->alpha_film && I->alpha_lane) && !I->batch.n && C.projection != 2u /* thin lens: k_raygen_lens stores the full state, as k_raygen_batch does */ &&
                              !(mq_env0 < 0 ? I->material_queues : mq_env0 != 0);
     if (tape_r) launch_tape_begin(s, C, seed, spp, log_spp, lane_base, n, I->shard_cap, I->result, I->adj, I->tape_la[0], I->tape_lb[0]);
     else if (rays) launch_raygen_rays(s, seed, lane_base, n, rays->n_total, rays->first, rays->o, rays->d, rays->maxt, rays->state, rays->active, I->shard_cap, I->st[0], I->result, cnt_alive(I, 0));
@@ -1595,54 +1595,53 @@ int har_bsdf_sample(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32
     HIP_TRY(hipGetLastError());
     return 0;
 }
-int har_sensor_sample_ray(const HarSensor *sensor, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt, void *stream) {
+int har_sensor_sample_ray_aperture(const HarSensor *sensor, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt, void *stream) {
     DSensor C; std::string e;
     if (!sensor || !lower_sensor(*sensor, C, e)) return fail(e.empty() ? "null sensor" : e);
     if (n == 0) return 0;
-    launch_api_sensor_ray((hipStream_t) stream, C, n, px, py, o, d, maxt);
+    if (!px || !py || !o || !d || !maxt || (!ax != !ay)) return fail("null input / output arrays");
+    launch_api_sensor_ray((hipStream_t) stream, C, n, px, py, ax, ay, o, d, maxt);
     HIP_TRY(hipGetLastError());
     return 0;
 }
-/* the camera part of each child, lowered for its own (sub-)film; children with a crop window are refused */
-static int lower_batch_children(const HarSensor *children, uint32_t n, std::vector<DCamera> &cams) {
-    if (!children && n) return fail("null child sensors");
-    cams.resize(n);
-    for (uint32_t i = 0; i < n; ++i) {
-        DSensor C; std::string e;
-        if (!lower_sensor(children[i], C, e)) return fail("batch sensor, child " + std::to_string(i) + ": " + e);
-        if (C.crop_x || C.crop_y || C.crop_w != children[i].film_width || C.crop_h != children[i].film_height)
-            return fail("batch sensor, child " + std::to_string(i) + ": a crop window on a child's film is not implemented by hip_ad_rgb");
-        cams[i] = har::batch_camera(C);
-    }
-    return 0;
+int har_sensor_sample_ray(const HarSensor *sensor, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt, void *stream) {
+    return har_sensor_sample_ray_aperture(sensor, n, px, py, nullptr, nullptr, o, d, maxt, stream);
+}
+static int lower_batch_children(const HarSensor *children, uint32_t n, std::vector<DCamera> &cams, uint32_t &aperture) {
+    std::string e;
+    return har::lower_batch_children(children, n, cams, aperture, e) ? 0 : fail(e);
 }
 int har_integrator_set_batch_sensors(HarIntegrator I, const HarSensor *children, uint32_t n, void *stream) {
     if (!I) return fail("null integrator");
-    if (n == 0) { I->batch = DBatch{ nullptr, 0u }; return 0; }
-    std::vector<DCamera> cams;
-    if (lower_batch_children(children, n, cams)) return 1;
+    if (n == 0) { I->batch = DBatch{ nullptr, 0u, 0u }; return 0; }
+    std::vector<DCamera> cams; uint32_t aperture = 0u;
+    if (lower_batch_children(children, n, cams, aperture)) return 1;
     if (I->batch_cap < n) {
         (void) hipDeviceSynchronize();      /* renders in flight may still read the old table */
-        dev_free(I->batch_cams, true); I->batch_cams = nullptr; I->batch_cap = 0; I->batch = DBatch{ nullptr, 0u };
+        dev_free(I->batch_cams, true); I->batch_cams = nullptr; I->batch_cap = 0; I->batch = DBatch{ nullptr, 0u, 0u };
         HIP_TRY(dev_alloc((void **) &I->batch_cams, (size_t) n * sizeof(DCamera)));
         I->batch_cap = n;
     }
     /* in stream order behind the renders that read the previous table; the host copy lives until the copy has run */
     HIP_TRY(hipMemcpyAsync(I->batch_cams, cams.data(), (size_t) n * sizeof(DCamera), hipMemcpyHostToDevice, (hipStream_t) stream));
     HIP_TRY(hipStreamSynchronize((hipStream_t) stream));
-    I->batch = DBatch{ I->batch_cams, n };
+    I->batch = DBatch{ I->batch_cams, n, aperture };
     return 0;
 }
 int har_batch_sample_ray(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt, void *stream) {
+    return har_batch_sample_ray_aperture(children, n_children, n, px, py, nullptr, nullptr, o, d, maxt, stream);
+}
+int har_batch_sample_ray_aperture(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, const float *ax, const float *ay,
+                                  float *o, float *d, float *maxt, void *stream) {
     if (n_children == 0) return fail("BatchSensor: at least one child sensor must be specified!");
-    std::vector<DCamera> cams;
-    if (lower_batch_children(children, n_children, cams)) return 1;
+    std::vector<DCamera> cams; uint32_t aperture = 0u;
+    if (lower_batch_children(children, n_children, cams, aperture)) return 1;
     if (n == 0) return 0;
-    if (!px || !py || !o || !d || !maxt) return fail("null input / output arrays");
+    if (!px || !py || !o || !d || !maxt || (!ax != !ay)) return fail("null input / output arrays");
     DCamera *dc = nullptr;
     HIP_TRY(dev_alloc((void **) &dc, cams.size() * sizeof(DCamera)));
     hipError_t err = hipMemcpyAsync(dc, cams.data(), cams.size() * sizeof(DCamera), hipMemcpyHostToDevice, (hipStream_t) stream);
-    if (err == hipSuccess) { launch_api_batch_ray((hipStream_t) stream, DBatch{ dc, n_children }, n, px, py, o, d, maxt); err = hipGetLastError(); }
+    if (err == hipSuccess) { launch_api_batch_ray((hipStream_t) stream, DBatch{ dc, n_children, aperture }, n, px, py, ax, ay, o, d, maxt); err = hipGetLastError(); }
     if (err == hipSuccess) err = hipStreamSynchronize((hipStream_t) stream);
     dev_free(dc);
     HIP_TRY(err);
@@ -2388,14 +2387,15 @@ int har_render_aovs(HarScene S, HarIntegrator I, const HarSensor *sensor, uint32
     I->last_stream = s; I->twin_used = false;
     if (prof_begin(I, s)) return 1;
     const bool deep = aov_deep_stack(S);
-    if (I->batch.n && I->aov_rays_cap < chunk) {
+    const bool aov_rays = I->batch.n || C.projection == 2u;      /* batch sensor / thin lens: the camera rays are made first (k_aov_batch_rays), then the array-valued flavours run */
+    if (aov_rays && I->aov_rays_cap < chunk) {
         if (I->aov_rays) { (void) hipDeviceSynchronize(); dev_free(I->aov_rays, true); I->aov_rays = nullptr; I->aov_rays_cap = 0; }
         HIP_TRY(dev_alloc((void **) &I->aov_rays, (size_t) chunk * 7 * sizeof(float)));
         I->aov_rays_cap = chunk;
     }
     for (uint64_t base = lb; base < le; base += chunk) {
         const uint32_t n = (uint32_t) std::min<uint64_t>(chunk, le - base);
-        if (I->batch.n) {        /* batch sensor: the lanes' camera rays from the child table, then the array-valued flavours of the pass (channel stride n) */
+        if (aov_rays) {        /* the lanes' camera rays from the child table / through the lens, then the array-valued flavours of the pass (channel stride n) */
             float *ro = I->aov_rays, *rd = ro + 3 * (size_t) n, *rt = rd + 3 * (size_t) n;
             launch_aov_batch_rays(s, C, I->batch, seed, spp, log_spp, (uint32_t) base, n, ro, rd, rt);
             prof_mark(I, s, CLS_RAYGEN);

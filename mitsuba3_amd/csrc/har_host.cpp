@@ -209,6 +209,21 @@ int har_perspective_sensor(const float to_world[32], double fov, const char *fov
     return 0;
 }
 
+int har_thinlens_sensor(const float to_world[32], double fov, const char *fov_axis_, float near_clip, float far_clip, float aperture_radius, float focus_distance,
+                        uint32_t width, uint32_t height, uint32_t cx, uint32_t cy, uint32_t cw, uint32_t ch, uint32_t rfilter, float stddev, HarSensor *out) {
+    /* ThinLensCamera::update_camera_transforms (thinlens.cpp:190-193) builds the perspective camera's sample_to_camera */
+    if (!out) return 1;
+    if (!(aperture_radius >= 0.f) || !std::isfinite(aperture_radius)) return 4;      /* (before anything is written: a refused call leaves *out as it was) */
+    if (!(focus_distance > 0.f) || !std::isfinite(focus_distance)) return 5;
+    HarSensor s = *out;                         /* (har_perspective_sensor leaves `sample_border` to the caller) */
+    if (int rc = har_perspective_sensor(to_world, fov, fov_axis_, near_clip, far_clip, width, height, cx, cy, cw, ch, rfilter, stddev, &s)) return rc;
+    *out = s;
+    out->projection = 2u;
+    out->aperture_radius = aperture_radius == 0.f ? 5.9604644775390625e-08f /* dr::Epsilon<float> = 2^-24 (thinlens.cpp:158-161) */ : aperture_radius;
+    out->focus_distance = focus_distance;
+    return 0;
+}
+
 int har_orthographic_sensor(const float to_world[32], float near_clip, float far_clip, uint32_t width, uint32_t height, uint32_t cx, uint32_t cy, uint32_t cw, uint32_t ch,
                             uint32_t rfilter, float stddev, HarSensor *out) {
     if (!out || !to_world || width == 0 || height == 0) return 1;

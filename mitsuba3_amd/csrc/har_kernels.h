@@ -131,7 +131,8 @@ struct ShapeTargets { const int32_t *offset; float *grad; uint32_t n_verts; cons
 void launch_raygen(int mode, hipStream_t s, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
                    uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count, const float *adj, float4 *dL, const PassState &ps = PassState{ nullptr, nullptr, 0 },
                    bool lite = false,       /* lite: only the rays are stored (k_raygen<.., LITE>; the first shading launch then carries HAR_SHADE_FIRST_VERTEX) */
-                   const DBatch *batch = nullptr);      /* batch: the child cameras of a batch sensor (k_raygen_batch; never lite) */
+                   const DBatch *batch = nullptr);      /* batch: the child cameras of a batch sensor (k_raygen_batch; never lite).  A thin lens -- C.projection == 2, or
+                                                         * batch->aperture -- goes to k_raygen_lens (never lite either) */
 /* har_integrator_sample: the wavefront of n caller-supplied rays (SoA arrays of n_total rays, this chunk starts at `first`), see k_raygen_rays */
 void launch_raygen_rays(hipStream_t s, uint32_t seed, uint32_t lane_base, uint32_t n, uint32_t n_total, uint32_t first, const float *o, const float *d, const float *maxt,
                         const uint64_t *state, const uint8_t *active, uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count);
@@ -203,8 +204,9 @@ void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, con
                               float *value, float *pdf);
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp);
-void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt);
-void launch_api_batch_ray(hipStream_t s, const DBatch &B, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt);
+/* ax / ay: the aperture samples of a thin lens (null = (0.5, 0.5), the centre of the lens; pinhole cameras ignore them) */
+void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt);
+void launch_api_batch_ray(hipStream_t s, const DBatch &B, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt);
 void launch_api_film_put(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *values4, float *film);
 
 } // namespace har

@@ -273,8 +273,9 @@ __device__ __forceinline__ uint32_t shard_slot(uint32_t i, uint32_t shard_cap) {
     return (tile % HAR_SHARDS) * shard_cap + (tile / HAR_SHARDS) * kBlock + (i % kBlock);
 }
 
-/* the body of k_raygen and k_raygen_batch; `batch`: the child cameras of a batch sensor, a null constant in k_raygen (the batch code folds away there) */
-template <int MODE, bool LITE>
+/* the body of k_raygen, k_raygen_batch and k_raygen_lens; `batch`: the child cameras of a batch sensor, a null constant in k_raygen (the batch code folds away there);
+ * LENS: raygen_lane's flavour that knows the thin lens */
+template <int MODE, bool LITE, bool LENS = false>
 __device__ __forceinline__ void raygen_body(const DSensor &C, const DBatch *batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
                                                    uint32_t n, uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count,
                                                    const float *adj, float4 *dL, const PassState &ps) {
@@ -291,9 +292,9 @@ __device__ __forceinline__ void raygen_body(const DSensor &C, const DBatch *batc
     PathState st;
     if (ps.rng) {
         float j[2];
-        st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, ps.pass ? ps.rng + i : nullptr, j, batch);
+        st = raygen_lane<LENS>(C, seed, spp, log_spp, lane_base + i, ls, ps.pass ? ps.rng + i : nullptr, j, batch);
         ps.jitter[i] = make_float2(j[0], j[1]);
-    } else st = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, batch);
+    } else st = raygen_lane<LENS>(C, seed, spp, log_spp, lane_base + i, ls, nullptr, nullptr, batch);
     if (LITE) { const uint32_t slot = shard_slot(i, shard_cap); out.a0[slot] = make_float4(st.o.x, st.o.y, st.o.z, st.maxt); out.a1[slot] = make_float4(st.d.x, st.d.y, st.d.z, st.prev_bsdf_pdf); }
     else store_state(out, shard_slot(i, shard_cap), st);
     if (MODE != MODE_PRB_ADJOINT) result[i] = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -331,6 +332,18 @@ __global__ __launch_bounds__(kBlock) void k_raygen_batch(DSensor C, DBatch batch
                                                          uint32_t n, uint32_t shard_cap, WaveState out, float4 *result, uint32_t *count,
                                                          const float *adj, float4 *dL, PassState ps) {
     raygen_body<MODE, false>(C, &batch, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+}
+
+/* k_raygen for renders through a thin lens: C is a `thinlens` sensor (batch.n == 0), or the wide film of a batch sensor one of whose children is one.  A kernel of its
+ * own for the same reason as k_raygen_batch: the pinhole kernels keep their registers and their sampler streams.  Always the full path state -- the first shading
+ * launch reads the state (whose sampler stands behind FOUR draws) instead of rebuilding it, so k_shade needs no thin-lens flavour. */
+template <int MODE>
+__global__ __launch_bounds__(kBlock) void k_raygen_lens(DSensor C, DBatch batch, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                        uint32_t n, uint32_t shard_cap, WaveState out, float4 *result, uint32_t *count,
+                                                        const float *adj, float4 *dL, PassState ps) {
+    /* two copies of the body under a uniform branch: a pointer chosen at run time would put the table's descriptor into scratch */
+    if (batch.n) raygen_body<MODE, false, true>(C, &batch, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+    else raygen_body<MODE, false, true>(C, nullptr, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
 }
 
 /* start of the adjoint pass in tape mode (TapeArrays): lane i of the chunk sits in slot shard_slot(i) of bounce 0's wavefront; its L is the primal pass's
@@ -2115,17 +2128,17 @@ __global__ void k_api_bsdf_sample(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t
     if (stype) stype[i] = b.type;
     if (scomp) scomp[i] = b.comp;
 }
-__global__ void k_api_sensor_ray(DSensor C, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+__global__ void k_api_sensor_ray(DSensor C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Vec3 O, D; float mt; sensor_sample_ray(C, px[i], py[i], O, D, mt);
+    Vec3 O, D; float mt; camera_sample_ray<true>(C, px[i], py[i], ax ? ax[i] : .5f, ay ? ay[i] : .5f, O, D, mt);
     o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
 }
 /* BatchSensor::sample_ray over caller-supplied film positions (har_batch_sample_ray) */
-__global__ void k_api_batch_ray(DBatch B, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+__global__ void k_api_batch_ray(DBatch B, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    Vec3 O, D; float mt; batch_sample_ray(B, px[i], py[i], O, D, mt);
+    Vec3 O, D; float mt; batch_sample_ray<true>(B, px[i], py[i], O, D, mt, ax ? ax[i] : .5f, ay ? ay[i] : .5f);
     o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
 }
 __global__ void k_api_film_put(DSensor C, uint32_t n, const float *px, const float *py, const float *values4, float *film) {
@@ -2152,6 +2165,13 @@ static inline uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock
 void launch_raygen(int mode, hipStream_t s, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
                    uint32_t shard_cap, const WaveState &out, float4 *result, uint32_t *count, const float *adj, float4 *dL, const PassState &ps, bool lite, const DBatch *batch) {
     dim3 g(blocks_for(n)), b(kBlock);
+    if ((batch && batch->n) ? batch->aperture != 0u : C.projection == 2u) {      /* a thin lens in the render: four draws before the first vertex */
+        const DBatch B = (batch && batch->n) ? *batch : DBatch{ nullptr, 0u, 0u };
+        if (mode == MODE_PRB_ADJOINT) hipLaunchKernelGGL(k_raygen_lens<MODE_PRB_ADJOINT>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        else if (mode == MODE_PRB_PRIMAL && adj) hipLaunchKernelGGL(k_raygen_lens<MODE_PRB_PRIMAL>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        else hipLaunchKernelGGL(k_raygen_lens<MODE_PATH>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
+        return;
+    }
     if (batch && batch->n) {
         const DBatch B = *batch;
         if (mode == MODE_PRB_ADJOINT) hipLaunchKernelGGL(k_raygen_batch<MODE_PRB_ADJOINT>, g, b, 0, s, C, B, seed, spp, log_spp, lane_base, n, shard_cap, out, result, count, adj, dL, ps);
@@ -2423,11 +2443,11 @@ void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
     hipLaunchKernelGGL(k_api_bsdf_sample, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
 }
-void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
-    hipLaunchKernelGGL(k_api_sensor_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, o, d, maxt);
+void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
+    hipLaunchKernelGGL(k_api_sensor_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, ax, ay, o, d, maxt);
 }
-void launch_api_batch_ray(hipStream_t s, const DBatch &B, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
-    hipLaunchKernelGGL(k_api_batch_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, B, n, px, py, o, d, maxt);
+void launch_api_batch_ray(hipStream_t s, const DBatch &B, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
+    hipLaunchKernelGGL(k_api_batch_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, B, n, px, py, ax, ay, o, d, maxt);
 }
 void launch_api_film_put(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *values4, float *film) {
     hipLaunchKernelGGL(k_api_film_put, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, values4, film);

@@ -227,6 +227,19 @@ HAR_HD void coordinate_system(Vec3 n, Vec3 &s, Vec3 &t) {
     t = Vec3(b, fma_(n.y, n.y * a, sign), -n.y);
 }
 
+/* warp::square_to_uniform_disk_concentric, include/mitsuba/core/warp.h:54-90 (the GGX visible-normal sampler, the thin lens aperture) */
+HAR_HD void square_to_uniform_disk_concentric(float sx, float sy, float &px, float &py) {
+    float x = fms_(2.f, sx, 1.f), y = fms_(2.f, sy, 1.f);
+    bool is_zero = (x == 0.f) && (y == 0.f), q13 = fabsf(x) < fabsf(y);
+    float r = q13 ? y : x, rp = q13 ? x : y;
+    float phi = 0.25f * HAR_PI * rp / r;
+    if (q13) phi = 0.5f * HAR_PI - phi;
+    if (is_zero) phi = 0.f;
+    float s, c;
+    sincos_(phi, s, c);
+    px = r * c; py = r * s;
+}
+
 /* warp::square_to_cosine_hemisphere, include/mitsuba/core/warp.h:54-90,412-423 */
 HAR_HD Vec3 square_to_cosine_hemisphere(float sx, float sy) {
     float x = fms_(2.f, sx, 1.f), y = fms_(2.f, sy, 1.f);

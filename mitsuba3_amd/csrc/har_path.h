@@ -79,7 +79,10 @@ struct ShadeResult {
 };
 #define HAR_EXTRA_GROUPS 5
 
-/* raygen: SamplingIntegrator::render_sample up to the camera ray (integrator.cpp:448-483) */
+/* raygen: SamplingIntegrator::render_sample up to the camera ray (integrator.cpp:448-483).  LENS: the sensor, or a child of the batch table, may be a thin lens -- then
+ * the lane draws the aperture sample right behind the jitter (needs_aperture_sample(), integrator.cpp:464-470), pass > 0 of a multi-pass render included; pinhole sensors
+ * draw nothing extra.  Only the kernels of thin-lens renders are built with LENS (k_raygen_lens, k_aov_batch_rays). */
+template <bool LENS = false>
 HAR_HD PathState raygen_lane(const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane, LaneSample &ls,
                              const uint64_t *resume = nullptr, float *jitter = nullptr, const DBatch *batch = nullptr) {
     PathState st;
@@ -89,7 +92,9 @@ HAR_HD PathState raygen_lane(const DSensor &C, uint32_t seed, uint32_t spp, uint
     float jx = pcg32_next_float(st.rng, inc), jy = pcg32_next_float(st.rng, inc);
     if (jitter) { jitter[0] = jx; jitter[1] = jy; }
     ls = lane_sample(C, lane, spp, log_spp, jx, jy);
-    lane_camera_ray(C, ls, st.o, st.d, st.maxt, batch);
+    float ax = .5f, ay = .5f;
+    if (LENS && (batch ? batch->aperture != 0u : C.projection == 2u)) { ax = pcg32_next_float(st.rng, inc); ay = pcg32_next_float(st.rng, inc); }
+    lane_camera_ray<LENS>(C, ls, st.o, st.d, st.maxt, batch, ax, ay);
     st.throughput = Vec3(1.f); st.lane = lane; st.prev_p = Vec3(0.f); st.prev_bsdf_pdf = 1.f; st.flags = 1u << 16; st.eta = 1.f;
     return st;
 }

@@ -104,11 +104,11 @@ std::vector<Block> spiral(uint32_t w, uint32_t h, uint32_t off_x, uint32_t off_y
 }
 
 /* PathIntegrator::sample, scalar variant, on the host-compiled path code: radiance + valid_ray */
-Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o, Vec3 d, float maxt, bool &valid_ray, int &status) {
+Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o, Vec3 d, float maxt, bool &valid_ray, int &status, uint32_t lane = 0u) {
     Vec3 result(0.f);
     valid_ray = S.env_emitter >= 0;                               /* path.cpp:114-115 (hide_emitters is refused by the caller) */
     if (P.max_depth == 0) return result;                          /* path.cpp:102-103 */
-    PathState st; st.o = o; st.d = d; st.maxt = maxt; st.throughput = Vec3(1.f); st.rng = rng; st.lane = 0; st.prev_p = Vec3(0.f); st.prev_bsdf_pdf = 1.f;
+    PathState st; st.o = o; st.d = d; st.maxt = maxt; st.throughput = Vec3(1.f); st.rng = rng; st.lane = lane; st.prev_p = Vec3(0.f); st.prev_bsdf_pdf = 1.f;
     st.flags = 1u << 16; st.eta = 1.f;
     for (;;) {
         Hit hit; ScalarStack stack;
@@ -143,6 +143,7 @@ extern "C" int har_render_scalar(const HarSceneDesc *desc, const HarSensor *sens
         B.bind();
         DSensor C;
         if (!lower_sensor(*sensor, C, e)) return har_set_error(e);
+        if (C.projection == 2u) return har_set_error("scalar_rgb: the `thinlens` sensor is not implemented by the scalar_rgb variant (hip_ad_rgb only)");
         const DScene &S = B.ds;
         const uint32_t W = C.crop_w, H = C.crop_h;
         /* Film::sample_border: the spiral runs over the enlarged film, every block is shifted back by the border (integrator.cpp:162-165, 248-249) */
@@ -197,6 +198,7 @@ extern "C" int har_render_scalar(const HarSceneDesc *desc, const HarSensor *sens
                         const float spx = pos_x + jx, spy = pos_y + jy;
                         const float sx = 1.f / (float) W, sy = 1.f / (float) H;
                         Vec3 o, d; float maxt;
+                        /* the pinhole models only: projection 2 was refused above (sensor_sample_ray would read the lens parameters as principal point offsets) */
                         sensor_sample_ray(C, fma_(spx, sx, -(float) C.crop_x * sx), fma_(spy, sy, -(float) C.crop_y * sy), o, d, maxt);
                         P.seed = bseed + i;                       /* the stream's increment is a function of (seed value, lane 0) */
                         bool valid = false;
@@ -295,26 +297,120 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
 
 /* BatchSensor::sample_ray (src/sensors/batch.cpp:132-159) on the host: batch_sample_ray (har_scene.h) -- the function k_raygen_batch runs per lane -- over the children
  * lowered as har_integrator_set_batch_sensors lowers them.  The twin of har_batch_sample_ray. */
-extern "C" int har_batch_sample_ray_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+static int lower_batch_children_host(const HarSensor *children, uint32_t n_children, std::vector<DCamera> &cams, uint32_t &aperture) {
+    if (n_children == 0) return har_set_error("BatchSensor: at least one child sensor must be specified!");
+    std::string e;
+    return lower_batch_children(children, n_children, cams, aperture, e) ? 0 : har_set_error(e);
+}
+extern "C" int har_batch_sample_ray_aperture_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, const float *ax, const float *ay,
+                                                  float *o, float *d, float *maxt) {
     try {
-        if (n_children == 0) return har_set_error("BatchSensor: at least one child sensor must be specified!");
-        if (!children) return har_set_error("null child sensors");
-        std::vector<DCamera> cams(n_children);
-        for (uint32_t i = 0; i < n_children; ++i) {
-            DSensor C; std::string e;
-            if (!lower_sensor(children[i], C, e)) return har_set_error("batch sensor, child " + std::to_string(i) + ": " + e);
-            if (C.crop_x || C.crop_y || C.crop_w != children[i].film_width || C.crop_h != children[i].film_height)
-                return har_set_error("batch sensor, child " + std::to_string(i) + ": a crop window on a child's film is not implemented by hip_ad_rgb");
-            cams[i] = batch_camera(C);
-        }
+        std::vector<DCamera> cams; uint32_t aperture = 0u;
+        if (lower_batch_children_host(children, n_children, cams, aperture)) return 1;
         if (n == 0) return 0;
-        if (!px || !py || !o || !d || !maxt) return har_set_error("null input / output arrays");
-        const DBatch B{ cams.data(), n_children };
+        if (!px || !py || !o || !d || !maxt || (!ax != !ay)) return har_set_error("null input / output arrays");
+        const DBatch B{ cams.data(), n_children, aperture };
         for (uint32_t i = 0; i < n; ++i) {
-            Vec3 O, D; float mt; batch_sample_ray(B, px[i], py[i], O, D, mt);
+            Vec3 O, D; float mt; batch_sample_ray<true>(B, px[i], py[i], O, D, mt, ax ? ax[i] : .5f, ay ? ay[i] : .5f);
             o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
         }
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_batch_sample_ray_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_batch_sample_ray_host: ") + ex.what()); }
+}
+extern "C" int har_batch_sample_ray_host(const HarSensor *children, uint32_t n_children, uint32_t n, const float *px, const float *py, float *o, float *d, float *maxt) {
+    return har_batch_sample_ray_aperture_host(children, n_children, n, px, py, nullptr, nullptr, o, d, maxt);
+}
+
+/* Sensor::sample_ray of one camera on the host: camera_sample_ray (har_scene.h) -- what k_api_sensor_ray and, through raygen_lane, the ray generation kernels run per
+ * lane.  The twin of har_sensor_sample_ray_aperture. */
+extern "C" int har_sensor_sample_ray_aperture_host(const HarSensor *sensor, uint32_t n, const float *px, const float *py, const float *ax, const float *ay,
+                                                   float *o, float *d, float *maxt) {
+    try {
+        DSensor C; std::string e;
+        if (!sensor || !lower_sensor(*sensor, C, e)) return har_set_error(e.empty() ? "null sensor" : e);
+        if (n == 0) return 0;
+        if (!px || !py || !o || !d || !maxt || (!ax != !ay)) return har_set_error("null input / output arrays");
+        for (uint32_t i = 0; i < n; ++i) {
+            Vec3 O, D; float mt; camera_sample_ray<true>(C, px[i], py[i], ax ? ax[i] : .5f, ay ? ay[i] : .5f, O, D, mt);
+            o[i] = O.x; o[n + i] = O.y; o[2 * (size_t) n + i] = O.z; d[i] = D.x; d[n + i] = D.y; d[2 * (size_t) n + i] = D.z; maxt[i] = mt;
+        }
+        return 0;
+    } catch (const std::exception &ex) { return har_set_error(std::string("har_sensor_sample_ray_aperture_host: ") + ex.what()); }
+}
+
+/* The forward `path` render of hip_ad_rgb on the host, lane by lane and serially: raygen_lane, the closest-hit traversal and shade_lane<MODE_PATH> with the JIT variants'
+ * draws (every lane of the wavefront draws its emitter samples), the splat of ImageBlock::put's coalesced branch (film_footprint).  A test instrument for small films: it
+ * runs the functions the kernels run, in the order the wavefront runs them per lane, without a GPU.  `film`: H x W x 4 of the crop window, accumulated into. */
+extern "C" int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
+                                     int32_t max_depth, int32_t rr_depth, float *film) {
+    try {
+        if (!desc || !sensor || !film) return har_set_error("null argument");
+        if (spp == 0) return har_set_error("spp must be > 0");
+        if (max_depth < 0 && max_depth != -1) return har_set_error("\"max_depth\" must be set to -1 (infinite) or a value >= 0");
+        if (rr_depth <= 0) return har_set_error("\"rr_depth\" must be set to a value greater than zero!");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        if (B.hs.stack_need() > (uint32_t) ScalarStack::Capacity) return har_set_error("scene too deep for the scalar traversal stack");
+        B.bind();
+        DSensor C;
+        if (!lower_sensor(*sensor, C, e)) return har_set_error(e);
+        std::vector<DCamera> cams; uint32_t aperture = 0u;
+        if (n_children && lower_batch_children_host(children, n_children, cams, aperture)) return 1;
+        if (n_children && (C.crop_x || C.crop_y || C.crop_w != sensor->film_width || C.crop_h != sensor->film_height || C.border || C.crop_w % n_children))
+            return har_set_error("batch sensor: the wide film must have no crop window or sample border, and a width divisible by the child count");
+        const uint64_t total = (uint64_t) C.samp_w * C.samp_h * spp;
+        if (total > (1u << 22)) return har_set_error("har_render_lanes_host: a serial host render for small films (at most 2^22 lanes)");
+        const DBatch T{ cams.data(), n_children, aperture };
+        uint32_t log_spp = 0xffffffffu; for (uint32_t k = 0; k < 32; ++k) if ((1u << k) == spp) log_spp = k;
+        ShadeParams P{ seed, (uint32_t) max_depth, (uint32_t) rr_depth, 0u };
+        int status = 0;
+        for (uint32_t lane = 0; lane < (uint32_t) total; ++lane) {
+            LaneSample ls;
+            const PathState st = raygen_lane<true>(C, seed, spp, log_spp, lane, ls, nullptr, nullptr, n_children ? &T : nullptr);
+            uint64_t rng = st.rng; bool valid = false;
+            const Vec3 rgb = sample_scalar(B.ds, P, rng, st.o, st.d, st.maxt, valid, status, lane);
+            const float v[4] = { rgb.x, rgb.y, rgb.z, 1.f };
+            Footprint F; film_footprint(C, ls, F);
+            for (uint32_t ys = 0; ys < F.count; ++ys)
+                for (uint32_t xs = 0; xs < F.count; ++xs) {
+                    const uint32_t x = F.x0 + xs, y = F.y0 + ys;
+                    if (!(x < C.crop_w && y < C.crop_h)) continue;
+                    const float w = F.wx[xs] * F.wy[ys];
+                    float *p = film + 4 * ((size_t) y * C.crop_w + x);
+                    for (int k = 0; k < 4; ++k) p[k] += v[k] * w;
+                }
+        }
+        if (status) return har_set_error("host render: traversal stack overflow");
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_render_lanes_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_render_lanes_host: ") + ex.what()); }
+}
+
+/* raygen_lane on the host over a lane range: the rays, film positions and sampler states the ray generation kernels produce (k_raygen for pinhole cameras,
+ * k_raygen_batch, k_raygen_lens) */
+extern "C" int har_raygen_lanes_host(const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp, uint32_t lane_begin, uint32_t n,
+                                     const uint64_t *resume, float *o, float *d, float *maxt, float *pos, uint64_t *state) {
+    try {
+        DSensor C; std::string e;
+        if (!sensor || !lower_sensor(*sensor, C, e)) return har_set_error(e.empty() ? "null sensor" : e);
+        if (spp == 0) return har_set_error("spp must be > 0");
+        std::vector<DCamera> cams; uint32_t aperture = 0u;
+        if (n_children && lower_batch_children_host(children, n_children, cams, aperture)) return 1;
+        if (n_children && (C.crop_x || C.crop_y || C.crop_w != sensor->film_width || C.crop_h != sensor->film_height || C.border || C.crop_w % n_children))
+            return har_set_error("batch sensor: the wide film must have no crop window or sample border, and a width divisible by the child count");
+        if ((uint64_t) lane_begin + n > (uint64_t) C.samp_w * C.samp_h * spp) return har_set_error("lane range beyond the render's lanes");
+        const DBatch B{ cams.data(), n_children, aperture };
+        uint32_t log_spp = 0xffffffffu; for (uint32_t k = 0; k < 32; ++k) if ((1u << k) == spp) log_spp = k;
+        for (uint32_t i = 0; i < n; ++i) {
+            LaneSample ls;
+            const PathState st = raygen_lane<true>(C, seed, spp, log_spp, lane_begin + i, ls, resume ? resume + i : nullptr, nullptr, n_children ? &B : nullptr);
+            if (o) { o[i] = st.o.x; o[n + i] = st.o.y; o[2 * (size_t) n + i] = st.o.z; }
+            if (d) { d[i] = st.d.x; d[n + i] = st.d.y; d[2 * (size_t) n + i] = st.d.z; }
+            if (maxt) maxt[i] = st.maxt;
+            if (pos) { pos[i] = ls.pos_x; pos[n + i] = ls.pos_y; }
+            if (state) state[i] = st.rng;
+        }
+        return 0;
+    } catch (const std::exception &ex) { return har_set_error(std::string("har_raygen_lanes_host: ") + ex.what()); }
 }

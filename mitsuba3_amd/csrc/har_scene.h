@@ -84,8 +84,11 @@ struct DSensor {
     float rf_p0, rf_p1;          /* filter parameters (HarSensor::rfilter_stddev / rfilter_param1) */
     float radius;
     float coeff[10];             /* GaussianFilter::m_coeff (LLVM branch) */
-    float ppo_x, ppo_y;          /* scaled principal point offset: film size * principal_point_offset / crop size (perspective.cpp:213-214) */
-    uint32_t projection;         /* 0 perspective, 1 orthographic (HarSensor::projection) */
+    /* scaled principal point offset: film size * principal_point_offset / crop size (perspective.cpp:213-214); a thin lens has none and keeps its aperture radius and
+     * focus distance there (thinlens.cpp:156-161, sensor.cpp:127), as HarSensor does: the record -- a kernel argument, and a member of ShadeParams -- keeps its size */
+    union { float ppo_x; float aperture_radius; };
+    union { float ppo_y; float focus_distance; };
+    uint32_t projection;         /* 0 perspective, 1 orthographic, 2 thin lens (HarSensor::projection) */
 };
 /* One child of a `batch` sensor (src/sensors/batch.cpp): the camera part of a DSensor lowered for the child's sub-film (film width / child count, full crop).  The
  * table of children lives in device memory (DBatch); the film part of the render -- lane -> pixel map, filter, splat -- stays the batch sensor's own DSensor. */
@@ -94,15 +97,19 @@ struct DCamera {
     float to_world[16];
     float near_clip, far_clip;
     float ppo_x, ppo_y;
-    uint32_t projection, pad[3];
+    uint32_t projection;
+    float aperture_radius, focus_distance;
+    uint32_t pad;
 };
 HAR_HD DCamera batch_camera(const DSensor &C) {
     DCamera c;
     for (int i = 0; i < 16; ++i) { c.s2c[i] = C.s2c[i]; c.to_world[i] = C.to_world[i]; }
-    c.near_clip = C.near_clip; c.far_clip = C.far_clip; c.ppo_x = C.ppo_x; c.ppo_y = C.ppo_y; c.projection = C.projection; c.pad[0] = c.pad[1] = c.pad[2] = 0u;
+    const bool lens = C.projection == 2u;
+    c.near_clip = C.near_clip; c.far_clip = C.far_clip; c.ppo_x = lens ? 0.f : C.ppo_x; c.ppo_y = lens ? 0.f : C.ppo_y; c.projection = C.projection;
+    c.aperture_radius = lens ? C.aperture_radius : 0.f; c.focus_distance = lens ? C.focus_distance : 0.f; c.pad = 0u;
     return c;
 }
-struct DBatch { const DCamera *cams; uint32_t n; };      /* n == 0: no batch, the DSensor is the camera */
+struct DBatch { const DCamera *cams; uint32_t n; uint32_t aperture; };      /* n == 0: no batch, the DSensor is the camera; aperture != 0: a child is a thin lens -- every lane draws an aperture sample */
 
 struct SurfInt {
     float t;
@@ -771,7 +778,9 @@ HAR_HD float textured_area_pdf_direction(const DScene &S, const DEmitter &E, Vec
     return bitmap_pdf_texture(T, S.emitter_cdf + as_u32(E.radiance[1]), tu, tv) * (dist * dist) / (E.radiance[2] * -dp);
 }
 
-/* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237); CAM: DSensor, or DCamera (a child of a batch sensor) */
+/* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237); CAM: DSensor, or DCamera (a child of a batch sensor).  For projection 0 and 1 ONLY: in a
+ * DSensor of projection 2 the words of ppo_x / ppo_y hold the lens parameters.  Callers that may meet a thin lens go through camera_sample_ray<true>; the others
+ * (k_raygen, k_shade's first-vertex rebuild, the scalar driver) are never handed one: launch_raygen, run_chunk and har_render_scalar send it elsewhere or refuse it. */
 template <class CAM>
 HAR_HD void sensor_sample_ray(const CAM &C, float px, float py, Vec3 &o, Vec3 &d, float &maxt) {
     const float *M = C.s2c;
@@ -800,6 +809,42 @@ HAR_HD void sensor_sample_ray(const CAM &C, float px, float py, Vec3 &o, Vec3 &d
     d = dw;
     o = Vec3(T[3], T[7], T[11]) + dw * near_t;
     maxt = far_t - near_t;
+}
+
+/* ThinLensCamera::sample_ray (src/sensors/thinlens.cpp:219-257): the film position goes to the near plane, from there to the plane of focus; the ray leaves the point
+ * (ax, ay) -> concentric disk * aperture_radius of the lens towards that point.  Unlike the pinhole models the origins of a pixel's rays differ. */
+template <class CAM>
+HAR_HD void thinlens_sample_ray(const CAM &C, float px, float py, float ax, float ay, Vec3 &o, Vec3 &d, float &maxt) {
+    const float *M = C.s2c;
+    float r0 = M[3], r1 = M[7], r2 = M[11], r3 = M[15];
+    r0 = fma_(M[0], px, r0); r1 = fma_(M[4], px, r1); r2 = fma_(M[8], px, r2);  r3 = fma_(M[12], px, r3);
+    r0 = fma_(M[1], py, r0); r1 = fma_(M[5], py, r1); r2 = fma_(M[9], py, r2);  r3 = fma_(M[13], py, r3);
+    r0 = fma_(M[2], 0.f, r0); r1 = fma_(M[6], 0.f, r1); r2 = fma_(M[10], 0.f, r2); r3 = fma_(M[14], 0.f, r3);
+    const float iw = rcp_(r3);
+    const Vec3 near_p(r0 * iw, r1 * iw, r2 * iw);
+    float lx, ly; square_to_uniform_disk_concentric(ax, ay, lx, ly);
+    lx = C.aperture_radius * lx; ly = C.aperture_radius * ly;                       /* aperture_p = (lx, ly, 0) */
+    const float fs = C.focus_distance / near_p.z;
+    const Vec3 focus_p(near_p.x * fs, near_p.y * fs, near_p.z * fs);
+    const Vec3 dl = normalize3(Vec3(focus_p.x - lx, focus_p.y - ly, focus_p.z - 0.f));
+    const float *T = C.to_world;
+    Vec3 ow(fma_(T[0], lx, T[3]), fma_(T[4], lx, T[7]), fma_(T[8], lx, T[11]));
+    ow = Vec3(fma_(T[1], ly, ow.x), fma_(T[5], ly, ow.y), fma_(T[9], ly, ow.z));
+    ow = Vec3(fma_(T[2], 0.f, ow.x), fma_(T[6], 0.f, ow.y), fma_(T[10], 0.f, ow.z));
+    Vec3 dw(T[0] * dl.x, T[4] * dl.x, T[8] * dl.x);
+    dw = Vec3(fma_(T[1], dl.y, dw.x), fma_(T[5], dl.y, dw.y), fma_(T[9], dl.y, dw.z));
+    dw = Vec3(fma_(T[2], dl.z, dw.x), fma_(T[6], dl.z, dw.y), fma_(T[10], dl.z, dw.z));
+    const float inv_z = rcp_(dl.z);
+    const float near_t = C.near_clip * inv_z, far_t = C.far_clip * inv_z;
+    d = dw;
+    o = ow + dw * near_t;
+    maxt = far_t - near_t;
+}
+/* sample_ray of any camera model; LENS = false leaves the thin lens out of kernels that never see one (they keep their registers) */
+template <bool LENS, class CAM>
+HAR_HD void camera_sample_ray(const CAM &C, float px, float py, float ax, float ay, Vec3 &o, Vec3 &d, float &maxt) {
+    if (LENS && C.projection == 2u) { thinlens_sample_ray(C, px, py, ax, ay, o, d, maxt); return; }
+    sensor_sample_ray(C, px, py, o, d, maxt);
 }
 
 /* GaussianFilter::eval, LLVM branch: max(estrin(x^2, coeff), 0) (src/rfilters/gaussian.cpp:57-101) */
@@ -861,21 +906,23 @@ HAR_HD uint32_t batch_select(float px, uint32_t n, float &px2) {
 /* the ray of child `batch_select(px)` of the table.  Device: the lanes of a wave are consecutive samples of consecutive pixels of a row, so all of them pick the
  * same child except where the wave crosses a seam (or a row's end) -- the uniform wave reads the record through an index it holds in a scalar register (scalar loads,
  * one copy of the 160-byte record per wave), the others read theirs per lane. */
-HAR_HD void batch_sample_ray(const DBatch &B, float px, float py, Vec3 &o, Vec3 &d, float &maxt) {
+template <bool LENS = false>      /* LENS: children may be thin lenses, (ax, ay) is the aperture sample (pinhole children ignore it) */
+HAR_HD void batch_sample_ray(const DBatch &B, float px, float py, Vec3 &o, Vec3 &d, float &maxt, float ax = .5f, float ay = .5f) {
     float px2;
     const uint32_t index = batch_select(px, B.n, px2);
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t first = (uint32_t) __builtin_amdgcn_readfirstlane((int) index);
-    if (__builtin_amdgcn_ballot_w64(index != first) == 0ull) { sensor_sample_ray(B.cams[first], px2, py, o, d, maxt); return; }
+    if (__builtin_amdgcn_ballot_w64(index != first) == 0ull) { camera_sample_ray<LENS>(B.cams[first], px2, py, ax, ay, o, d, maxt); return; }
 #endif
-    sensor_sample_ray(B.cams[index], px2, py, o, d, maxt);
+    camera_sample_ray<LENS>(B.cams[index], px2, py, ax, ay, o, d, maxt);
 }
 /* `batch` (optional): the children of a batch sensor -- C is then the batch sensor's wide film, whose crop window is the full film */
-HAR_HD void lane_camera_ray(const DSensor &C, const LaneSample &L, Vec3 &o, Vec3 &d, float &maxt, const DBatch *batch = nullptr) {
+template <bool LENS = false>
+HAR_HD void lane_camera_ray(const DSensor &C, const LaneSample &L, Vec3 &o, Vec3 &d, float &maxt, const DBatch *batch = nullptr, float ax = .5f, float ay = .5f) {
     float sx = 1.f / (float) C.crop_w, sy = 1.f / (float) C.crop_h;
     float ox = -(float) C.crop_x * sx, oy = -(float) C.crop_y * sy;
-    if (batch) { batch_sample_ray(*batch, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), o, d, maxt); return; }
-    sensor_sample_ray(C, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), o, d, maxt);
+    if (batch) { batch_sample_ray<LENS>(*batch, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), o, d, maxt, ax, ay); return; }
+    camera_sample_ray<LENS>(C, fma_(L.pos_x, sx, ox), fma_(L.pos_y, sy, oy), ax, ay, o, d, maxt);
 }
 
 } // namespace har

@@ -714,20 +714,42 @@ static bool lower_sensor_filter(const HarSensor &in, DSensor &out, std::string &
 bool lower_sensor(const HarSensor &in, DSensor &out, std::string &err) {
     if (in.crop_width == 0 || in.crop_height == 0) { err = "empty crop window"; return false; }
     if (in.rfilter > 5) { err = "unsupported reconstruction filter (box, gaussian, tent, mitchell, catmullrom and lanczos are implemented)"; return false; }
-    if (in.projection > 1) { err = "unsupported sensor projection (0 = perspective, 1 = orthographic)"; return false; }
+    if (in.projection > 2) { err = "unsupported sensor projection (0 = perspective, 1 = orthographic, 2 = thin lens)"; return false; }
     out.projection = in.projection;
+    if (in.projection == 2) {
+        if (!(in.aperture_radius > 0.f) || !std::isfinite(in.aperture_radius)) { err = "thin lens: aperture_radius must be positive and finite"; return false; }
+        if (!(in.focus_distance > 0.f) || !std::isfinite(in.focus_distance)) { err = "thin lens: focus_distance must be positive and finite"; return false; }
+    }
     std::memcpy(out.s2c, in.sample_to_camera, 64); std::memcpy(out.to_world, in.to_world, 64);
     out.near_clip = in.near_clip; out.far_clip = in.far_clip;
     out.crop_x = in.crop_offset_x; out.crop_y = in.crop_offset_y; out.crop_w = in.crop_width; out.crop_h = in.crop_height;
     out.rfilter = in.rfilter;
     std::memset(out.coeff, 0, sizeof(out.coeff));
     out.rf_p0 = in.rfilter_stddev; out.rf_p1 = in.rfilter_param1;
-    out.ppo_x = (float) in.film_width * in.principal_point_offset_x / (float) in.crop_width;
-    out.ppo_y = (float) in.film_height * in.principal_point_offset_y / (float) in.crop_height;
+    if (in.projection == 2) { out.aperture_radius = in.aperture_radius; out.focus_distance = in.focus_distance; }      /* (the words of ppo_x / ppo_y) */
+    else {
+        out.ppo_x = (float) in.film_width * in.principal_point_offset_x / (float) in.crop_width;
+        out.ppo_y = (float) in.film_height * in.principal_point_offset_y / (float) in.crop_height;
+    }
     if (!lower_sensor_filter(in, out, err)) return false;
     /* ReconstructionFilter::init_discretization (rfilter.cpp:22): border_size = ceil(radius - 1/2 - 2 RayEpsilon) */
     out.border = in.sample_border ? (uint32_t) std::max(0, (int) std::ceil(out.radius - .5f - 2.f * HAR_RAY_EPS)) : 0u;
     out.samp_w = out.crop_w + 2u * out.border; out.samp_h = out.crop_h + 2u * out.border;
+    return true;
+}
+
+bool lower_batch_children(const HarSensor *children, uint32_t n, std::vector<DCamera> &cams, uint32_t &aperture, std::string &err) {
+    if (!children && n) { err = "null child sensors"; return false; }
+    cams.resize(n); aperture = 0u;
+    for (uint32_t i = 0; i < n; ++i) {
+        DSensor C; std::string e;
+        if (!lower_sensor(children[i], C, e)) { err = "batch sensor, child " + std::to_string(i) + ": " + e; return false; }
+        if (C.crop_x || C.crop_y || C.crop_w != children[i].film_width || C.crop_h != children[i].film_height) {
+            err = "batch sensor, child " + std::to_string(i) + ": a crop window on a child's film is not implemented by hip_ad_rgb"; return false;
+        }
+        cams[i] = batch_camera(C);
+        if (C.projection == 2u) aperture = 1u;      /* one thin lens: every lane draws an aperture sample (batch.cpp:121-125) */
+    }
     return true;
 }
 

@@ -112,5 +112,7 @@ double refit_blas_host(HostScene &hs, BlasInfo &blas);
 
 /* GaussianFilter ctor (src/rfilters/gaussian.cpp:48-93) + sensor repack */
 bool lower_sensor(const HarSensor &in, DSensor &out, std::string &err);
+/* the children of a batch sensor: the camera part of each, lowered for its own (sub-)film -- a child with a crop window is refused; `aperture`: a child is a thin lens */
+bool lower_batch_children(const HarSensor *children, uint32_t n, std::vector<DCamera> &cams, uint32_t &aperture, std::string &err);
 
 } // namespace har
