@@ -616,6 +616,11 @@ int har_integrator_set_material_queues(HarIntegrator integrator, int enable);
  * incoherent fall back to the per-ray kernel.  mode -1 (default): automatic (renders with spp a multiple of 64); 0: off; 1: on for every first launch, also for
  * the rays of har_integrator_sample (testing). */
 int har_integrator_set_packet_tracing(HarIntegrator integrator, int mode);
+/* Seeded start of the per-ray closest-hit launches on a two-level scene with a few top-level triangles (the walls of a box around instanced content): every ray
+ * of a fetch batch is first tested brute force against those triangles, then walks the instance level only, with that hit as its tmax.  Same intersections bit
+ * for bit.  mode -1 (default): the scene's choice (1 .. 16 top-level triangles and the build's default); 0: off; 1: on for every two-level scene with top-level
+ * geometry.  The environment variable HAR_TOP_SEED=0/1, read when a scene / an integrator is created, overrides both. */
+int har_integrator_set_top_seed(HarIntegrator integrator, int mode);
 int har_render_timing(HarIntegrator integrator, float ms[8], uint32_t launches[8]);
 
 /* ------------------------------------------------------------------------

@@ -83,6 +83,13 @@ HAR_HD void pad_box(float lo[3], float hi[3]) {
     for (int a = 0; a < 3; ++a) { lo[a] -= pad; hi[a] += pad; }
 }
 
+#define HAR_TOP_SEED_BIT 4u
+#ifndef HAR_TOP_SEED_MAX
+#define HAR_TOP_SEED_MAX 16       /* most top-level triangles a scene may have for the automatic seeded start */
+#endif
+#ifndef HAR_TOP_SEED_DEFAULT
+#define HAR_TOP_SEED_DEFAULT 1    /* automatic choice for eligible scenes: on (headline frame 61.4 -> 59.0 ms, profiles/r07_ab_top_seed.txt); 0: only when forced */
+#endif
 struct Accel {
     const Node8   *nodes;
     const TriRec  *tris;
@@ -99,8 +106,15 @@ struct Accel {
      * scene -- are better walked AFTER the TLAS: half of the benchmark scene's shadow rays are occluded by an instance and then never pay the walls' node
      * visits (k_resolve 29.9 -> 26.5 ms), and a closest-hit ray that met an instance reaches the walls with tmax in front of them.  Many top-level
      * triangles (terrain under instanced trees) keep the top-level-first order, which enters the TLAS with tmax at the nearest top-level hit.
-     * bit 0: any-hit rays walk the TLAS first, bit 1: closest-hit rays do. */
+     * bit 0: any-hit rays walk the TLAS first, bit 1: closest-hit rays do, bit 2: top_seed() below. */
     uint32_t top_last;
+    /* closest-hit rays of the persistent per-lane kernel are SEEDED (round 7): the few top-level triangles of a "box around instanced content" scene are tested brute
+     * force for a whole fetch batch at once (top_seed_hit: all lanes active, wave-uniform records) and the ray starts at the TLAS root with that hit and its t as tmax
+     * (Traversal::begin_seeded) -- the state it has today after walking the top-level BLAS first, without the divergent node visits and leaf tests of that walk.
+     * Set when the structure is lowered (build_tlas): has_tlas, top-level geometry, 1 <= top_count <= HAR_TOP_SEED_MAX; HAR_TOP_SEED / the integrator's `top_seed` force it.
+     * The flag is bit 2 of the top_last word and not a member of its own: a new member moves mesh_info and every kernel argument behind an Accel, i.e. it would
+     * change the code object of every kernel that takes one. */
+    HAR_HD bool top_seed() const { return (top_last & HAR_TOP_SEED_BIT) != 0u; }
     /* per mesh {first face of the mesh in the packed face / shading-triangle arrays, material word}: what a finished closest-hit ray adds to its hit record so that the
      * shading kernel starts its geometry and BSDF loads from the record instead of from a dependent load of the mesh record (HAR_HIT_MATINFO, har_kernels.h).
      * material word: bits 0-19 BSDF record, 20-21 mesh flags (vertex normals, texcoords), 22 carries an emitter, 24-27 material class (HAR_MAT_*) */
@@ -449,6 +463,19 @@ struct Traversal {
         }
     }
 
+    /* SEEDED begin (Accel::top_seed; two-level scenes with top-level geometry only): `seed` is the closest hit among the top-level triangles (top_seed_hit) or empty
+     * (t = inf).  The ray starts at the TLAS root with it -- exactly the state after the top-level BLAS has been walked first; that phase is skipped.  The result is
+     * the one of either order: hit_update's tie rule and the t <= tmax acceptance do not depend on the order of the candidates, and an instance always beats
+     * top-level geometry on equal t, so of the seed only t (and inst = none) takes part in the walk. */
+    HAR_HD void begin_seeded(const Accel &A, Vec3 o, Vec3 d, float maxt, const Hit &seed) {
+        o_w = o; d_w = d; top_pending = false; top_last = false;
+        hit = seed;
+        tmax = (seed.t != HAR_INF ? seed.t : maxt) + 0.f;     /* -0 -> +0: see tri_visit_at */
+        R = ray_setup(o, d);
+        in_tlas = true; cur_inst = 0xffffffffu; found = false;
+        ng_x = A.root; ng_y = 0x80000000u; tg_x = 0; tg_y = 0; sp = 0; inst_sp = -1; parked = 0;
+    }
+
     /* ---- node phase: at most one node visit */
     template <typename Stack, typename Probe>
     HAR_HD bool phase_node(const Accel &A, Stack &stack, int &status, Probe &probe) {
@@ -620,6 +647,31 @@ struct Traversal {
         }
     }
 };
+
+/* The seed of Traversal::begin_seeded: the top-level triangles A.tris[top_first .. top_first + top_count) brute force, with the exact test and the tie rule of
+ * accel_trace_naive's first block.  The trip count and the record addresses are the same for every lane: on the device the records are read through the
+ * constant address space, which lets the compiler use scalar loads (it does for words 4-10 and reads words 0-3 with one vector load from a wave-uniform
+ * address; no per-lane address arithmetic either way: profiles/r07_ab_top_seed.txt).  The records only change between launches (vertex updates rewrite them
+ * in kernels of their own). */
+HAR_HD void top_seed_hit(const Accel &A, Vec3 o, Vec3 d, float maxt, Hit &hit) {
+    hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
+    float tmax = maxt;
+    for (uint32_t i = A.top_first; i < A.top_first + A.top_count; ++i) {
+#if defined(__HIP_DEVICE_COMPILE__)
+        typedef const __attribute__((address_space(4))) float4 *ConstF4;
+        const ConstF4 tp = (ConstF4) (A.tris + i);
+        const float4 a = tp[0], b = tp[1], c = tp[2];
+        const float f[12] = { a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w, c.x, c.y, c.z, c.w };
+#else
+        const float *f = reinterpret_cast<const float *>(A.tris + i);
+#endif
+        float t, u, v;
+        if (moeller_trumbore(o, d, tmax, Vec3(f[0], f[1], f[2]), Vec3(f[3], f[4], f[5]), Vec3(f[6], f[7], f[8]), t, u, v)) {
+            hit_update(hit, t, u, v, as_u32(f[9]), as_u32(f[10]), 0xffffffffu);
+            tmax = hit.t;
+        }
+    }
+}
 
 /* Scene::ray_intersect_naive (scene.cpp:240-244): brute force over every triangle record */
 template <bool AnyHit>

@@ -219,6 +219,7 @@ struct HarIntegratorImpl {
     float *inst_user = nullptr; uint32_t inst_count = 0; int32_t *d_inst_slot = nullptr; float *grad_inst = nullptr;
     bool material_queues = false;         /* har_integrator_set_material_queues */
     int packet_tracing = -1;              /* har_integrator_set_packet_tracing: -1 automatic, 0 off, 1 every first closest-hit launch */
+    int top_seed = -1, top_seed_env = -1; /* har_integrator_set_top_seed: -1 the scene's choice (Accel::top_seed), 0 off, 1 on; HAR_TOP_SEED as read when the integrator was created (it wins) */
     int bw_tape_max = 2; uint32_t bw_chunk_max = 0xffffffffu;      /* render_backward: what the last out-of-memory fallback settled on (tape kind, chunk lanes) */
     uint64_t bw_job_key = 0; uint32_t bw_calls_since_stepdown = 0;   /* ... for which job (scene, film, lanes), and how many calls ago */
     uint32_t *mq_idx = nullptr, *mq_count = nullptr;      /* per-material shading queues (MaterialQueues): HAR_MAT_CLASSES index lists of ws_lanes entries, their counters */
@@ -496,6 +497,15 @@ int ensure_texel_queues(HarSceneImpl *S, HarIntegratorImpl *I) {
  * 33 M 42.50 / 41.90, 67 M 77.07 / 77.30; with the asynchronous join (second item set + `result2`) and 64-ray fetches 2 M 4.11, 8 M 12.60, 16 M 23.66, 33 M 42.06, 67 M still
  * neutral (78.05 / 78.37).  A single large wavefront keeps one stream and sequential launches (its kernels are timed one by one for the bench
  * line).  Not with the HBM stack spill (both traversal kernels would share it) nor with hide_emitters.  HAR_OVERLAP = 0 / 1 forces it off / on (A/B). */
+/* the acceleration structure as this integrator's closest-hit launches see it: Accel::top_seed is the scene's choice (build_tlas) unless the integrator's `top_seed`
+ * property or HAR_TOP_SEED (as read when the integrator was created) forces it.  On needs a two-level scene with top-level geometry. */
+static Accel seeded_accel(const HarIntegratorImpl *I, const Accel &scene_accel) {
+    Accel A = scene_accel;
+    const int mode = I->top_seed_env >= 0 ? I->top_seed_env : I->top_seed;
+    if (mode == 0) A.top_last &= ~HAR_TOP_SEED_BIT;
+    else if (mode == 1 && A.has_tlas && A.top_root != HAR_NO_NODE && A.top_count >= 1u) A.top_last |= HAR_TOP_SEED_BIT;
+    return A;
+}
 static bool overlap_applies(const HarSceneImpl *S, const HarIntegratorImpl *I, uint64_t n) {
     static const int overlap_env = getenv("HAR_OVERLAP") ? atoi(getenv("HAR_OVERLAP")) : -1;
     static const bool force_spill = getenv("HAR_FORCE_STACK_SPILL") != nullptr;
@@ -639,7 +649,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
                 prof_mark(I, s, CLS_TRACE);             /* two launches of the closest-hit class: the packets, then the rays of the packets that gave up */
                 launch_trace_closest(s, tgrid, spill, S->ds.accel, pl.count, pl.cursor, I->shard_cap, st_in, h0, h1, I->status, &pl);
             } else
-            launch_trace_closest(s, tgrid, spill, S->ds.accel, cnt_alive(I, b), cur_trace(I, b), I->shard_cap, st_in, h0, h1, I->status);
+            launch_trace_closest(s, tgrid, spill, seeded_accel(I, S->ds.accel), cnt_alive(I, b), cur_trace(I, b), I->shard_cap, st_in, h0, h1, I->status);
             prof_mark(I, s, CLS_TRACE);
             if (I->stagger_record && b == 0) { HIP_TRY(hipEventRecord(I->ev_stagger, s)); I->stagger_record = false; }
         }
@@ -1675,6 +1685,7 @@ int har_integrator_create(int type, int32_t max_depth, int32_t rr_depth, uint32_
     HarIntegratorImpl *I = new HarIntegratorImpl();
     I->type = type; I->max_depth = (uint32_t) max_depth; I->rr_depth = (uint32_t) rr_depth;
     if (chunk_lanes) I->chunk = std::max<uint32_t>(2048u, (chunk_lanes + 2047u) / 2048u * 2048u);
+    if (const char *e = getenv("HAR_TOP_SEED")) I->top_seed_env = atoi(e) != 0 ? 1 : 0;      /* per integrator, not cached: one process can hold both kinds */
     *out = I;
     return 0;
 }
@@ -1793,7 +1804,7 @@ static uint64_t dual_split(HarIntegrator I, uint64_t lb, uint64_t le, hipStream_
     HarIntegratorImpl *T = I->twin;
     T->type = I->type; T->max_depth = I->max_depth; T->rr_depth = I->rr_depth; T->chunk = I->chunk; T->samples_per_pass = I->samples_per_pass;
     T->grad_emitters = I->grad_emitters; T->grad_bsdf_params = I->grad_bsdf_params; T->grad_light_texels = I->grad_light_texels; T->profiling = I->profiling; T->hide_emitters = I->hide_emitters;
-    T->alpha_film = I->alpha_film; T->batch = I->batch;
+    T->alpha_film = I->alpha_film; T->batch = I->batch; T->top_seed = I->top_seed; T->top_seed_env = I->top_seed_env;
     if (T->use_cache != I->use_cache) { (void) hipDeviceSynchronize(); T->free_ws(); T->use_cache = I->use_cache; }
     if (hipEventRecord(I->ev_fork, s) != hipSuccess || hipStreamWaitEvent(I->side_stream, I->ev_fork, 0) != hipSuccess) return le;
     I->twin_used = true;
@@ -2253,6 +2264,14 @@ int har_render_stats(HarIntegrator I, HarStats *out) {
         if (read_status(I->twin->status, s)) return 1;
         out->paths += t[0]; out->vertices += t[1]; out->closest_rays += t[2]; out->shadow_rays += t[3];
     }
+    return 0;
+}
+
+int har_integrator_set_top_seed(HarIntegrator I, int mode) {
+    if (!I) return fail("null integrator");
+    if (mode < -1 || mode > 1) return fail("har_integrator_set_top_seed: mode must be -1 (automatic), 0 (off) or 1 (on)");
+    I->top_seed = mode;
+    if (I->twin) I->twin->top_seed = mode;
     return 0;
 }
 

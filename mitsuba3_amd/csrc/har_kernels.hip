@@ -502,9 +502,12 @@ __global__ void k_sample_out(uint32_t n, uint32_t n_total, uint32_t first, const
 #define HAR_TRAV_ORDER 0    /* measured: 0 (node, leaf, pop) 687, 2: 660, 1: 643 Mpaths/s on the 1M-tri scene */
 #endif
 
-template <bool ANY, bool RETIRE, typename WaveStack, bool FLAT, typename Take, typename Done, typename Retire>
+/* `fetched(first, end)`: called by the whole wave (wave-uniform arguments) when it has drawn the rays [first, end) from the shard's cursor, before any lane takes one of
+ * them -- the seeded closest-hit kernel's prologue (k_trace_closest<.., SEED>); branch-free refill path only */
+struct NoFetched { __device__ __forceinline__ void operator()(uint32_t, uint32_t) const { } };
+template <bool ANY, bool RETIRE, typename WaveStack, bool FLAT, typename Take, typename Done, typename Retire, typename Fetched = NoFetched>
 __device__ __forceinline__ void trace_persistent(const Accel &A, uint32_t *cursor, uint32_t n, WaveStack &stack, int *status,
-                                                 Take take, Done done, Retire retire) {
+                                                 Take take, Done done, Retire retire, Fetched fetched = Fetched()) {
     const uint32_t lane = threadIdx.x & 63u;
     /* rays per fetch: 128 in the bulk; when the shard holds no more rays than its waves have lanes (late bounces, small jobs) every lane gets
      * ONE ray -- such launches are latency chains of single rays, and two rays per lane would double them */
@@ -532,7 +535,7 @@ __device__ __forceinline__ void trace_persistent(const Accel &A, uint32_t *curso
                 if (lane == 0) b = atomicAdd(cursor, fetch);
                 b = (uint32_t) __builtin_amdgcn_readfirstlane((int) b);
                 if (b >= n) exhausted = true;
-                else { pool_next = b; pool_end = min(b + fetch, n); }
+                else { pool_next = b; pool_end = min(b + fetch, n); fetched(pool_next, pool_end); }
             }
             const uint32_t avail = pool_end - pool_next;
             if (avail == 0u && n_idle == 64u) break;
@@ -634,7 +637,17 @@ __device__ __forceinline__ void trace_persistent(const Accel &A, uint32_t *curso
 #endif
 /* LIST: the launch walks the rays of the 64-ray packets named in `list` (per shard: list[shard * list_stride + k] = first ray of the packet within the shard) --
  * the packets k_trace_packet gave up on -- instead of the whole wavefront: work item idx is ray list[idx / 64] + idx % 64, `count` holds the number of PACKETS */
-template <bool SPILL, bool FLAT = false, bool LIST = false>
+/* SEED (Accel::top_seed; k_trace_closest<false, false, false, true>, the only instantiation): when a wave has drawn a batch of rays from its shard's cursor, and before its lanes take
+ * them one by one, all 64 lanes test one ray of the batch each against the scene's few top-level triangles (top_seed_hit: uniform trip count, records at wave-uniform
+ * addresses) and store the COMPLETE hit record of that result -- or the miss record -- into the ray's slot of the hit buffer; a 128-ray batch takes two passes.  The lane that
+ * later takes the ray reads back t only and starts at the TLAS root (Traversal::begin_seeded); a ray that finds no instance at or in front of its seed stores nothing
+ * when it retires -- its record is already there.
+ * Ordering.  The record of ray r is written by one lane of this wave in the prologue, read (t) by another lane of the SAME wave at take, and possibly overwritten by that
+ * lane at retire; no other wave touches r (a batch belongs to the wave that drew it), and h0 / h1 are this launch's output, which nothing else reads before it ends.  A
+ * wave's vector memory instructions enter its CU's memory pipeline in program order and the prologue precedes both later accesses in program order; what has to be
+ * ruled out is the COMPILER moving the take's load or the retire's store of one lane across the prologue's store of another (it sees different lanes' addresses as
+ * unrelated).  The workgroup-scope release / acquire fence pair after the prologue does that, and waits for the stores where the target needs it. */
+template <bool SPILL, bool FLAT = false, bool LIST = false, bool SEED = false>
 __global__ __launch_bounds__(kBlock, HAR_TRACE_MIN_WAVES) void k_trace_closest(Accel A, const uint32_t *count, uint32_t *cursor, uint32_t shard_cap, const float4 *a0,
                                                           const float4 *a1, float4 *h0, uint2 *h1, int *status, uint2 *spill, const uint32_t *list, uint32_t list_stride,
                                                           const uint32_t *shard_count) {
@@ -651,12 +664,17 @@ __global__ __launch_bounds__(kBlock, HAR_TRACE_MIN_WAVES) void k_trace_closest(A
         /* branch-free (trace_persistent's refill merges the state with selects): a work item past the shard's last ray begins a copy of that ray and says `false` */
         const uint32_t r0 = ray_of(idx), r = LIST ? min(r0, n_rays - 1u) : r0;
         float4 o = a0[base + r], d = a1[base + r];
+        if constexpr (SEED) {
+            Hit seed; seed.t = h0[HIT0(base + r)].x; seed.u = 0.f; seed.v = 0.f; seed.prim = 0; seed.shape = 0; seed.inst = 0xffffffffu;     /* the prologue's record: only t matters (begin_seeded) */
+            T.begin_seeded(A, Vec3(o.x, o.y, o.z), Vec3(d.x, d.y, d.z), o.w < 0.f ? HAR_LARGEST : o.w, seed);
+        } else
         T.begin(A, Vec3(o.x, o.y, o.z), Vec3(d.x, d.y, d.z), o.w < 0.f ? HAR_LARGEST : o.w, (A.top_last & 2u) != 0u);
         return !LIST || r0 < n_rays;
     };
     auto store = [&](uint32_t idx, const Trav &T) {
         const uint32_t r = ray_of(idx);
         if (LIST && r >= n_rays) return;
+        if (SEED && T.hit.inst == 0xffffffffu) return;      /* still the seed (or a miss): the prologue has stored this record */
         h0[HIT0(base + r)] = make_float4(T.hit.t, T.hit.u, T.hit.v, __uint_as_float(T.hit.prim));
 #if HAR_HIT_INTERLEAVED      /* the second half as ONE 16-byte store: the ray's 32-byte sector is written completely (no byte-masked partial write) */
 #if HAR_HIT_MATINFO
@@ -670,17 +688,54 @@ __global__ __launch_bounds__(kBlock, HAR_TRACE_MIN_WAVES) void k_trace_closest(A
         h1[HIT1(base + r)] = make_uint2(T.hit.shape, T.hit.inst);
 #endif
     };
+    /* the same record for ray r from a bare Hit (the prologue's seed) */
+    auto store_hit = [&](uint32_t r, const Hit &hit) {
+        h0[HIT0(base + r)] = make_float4(hit.t, hit.u, hit.v, __uint_as_float(hit.prim));
+#if HAR_HIT_INTERLEAVED
+#if HAR_HIT_MATINFO
+        MeshInfo mi{ 0u, 0u };
+        if (hit.t != HAR_INF) mi = A.mesh_info[hit.shape];
+        *reinterpret_cast<uint4 *>(h1 + HIT1(base + r)) = make_uint4(hit.shape, hit.inst, mi.foff + hit.prim, mi.matinfo);
+#else
+        *reinterpret_cast<uint4 *>(h1 + HIT1(base + r)) = make_uint4(hit.shape, hit.inst, 0u, 0u);
+#endif
+#else
+        h1[HIT1(base + r)] = make_uint2(hit.shape, hit.inst);
+#endif
+    };
+    /* the SEED prologue of a freshly drawn batch [first, end): see the comment above the function */
+    auto seed_batch = [&](uint32_t first, uint32_t end) {
+        const uint32_t lane = threadIdx.x & 63u;
+        for (uint32_t p = first; p < end; p += 64u) {
+            const uint32_t r = min(p + lane, end - 1u);          /* a lane past the end repeats the last ray and stores nothing */
+            const float4 o = a0[base + r], d = a1[base + r];
+            Hit seed;
+            top_seed_hit(A, Vec3(o.x, o.y, o.z), Vec3(d.x, d.y, d.z), o.w < 0.f ? HAR_LARGEST : o.w, seed);
+            if (p + lane < end) store_hit(r, seed);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+    };
 #if HAR_CLOSEST_RETIRE
     /* hits are committed at refill time by all lanes that finished since the last refill (one store instruction for >= HAR_REFILL_IDLE lanes)
      * instead of by each lane in the iteration it finishes in (a store instruction + address arithmetic issued for one or two lanes) */
+    if constexpr (SEED) {
+        static_assert(!SPILL && !FLAT && !LIST && WaveStack::kSelectRefill, "the seeded flavour exists for the two-level per-lane kernel on the branch-free refill path");
+        trace_persistent<false, true, WaveStack, FLAT>(A, cursor + shard * HAR_COUNTER_STRIDE, n, stack, status, take,
+            [&](uint32_t, const Trav &) { },
+            [&](bool pred, uint32_t idx, const Trav &T) { if (pred) store(idx, T); }, seed_batch);
+    } else
     trace_persistent<false, true, WaveStack, FLAT>(A, cursor + shard * HAR_COUNTER_STRIDE, n, stack, status, take,
         [&](uint32_t, const Trav &) { },
         [&](bool pred, uint32_t idx, const Trav &T) { if (pred) store(idx, T); });
 #else
+    static_assert(!SEED, "the seeded flavour needs HAR_CLOSEST_RETIRE");
     trace_persistent<false, false, WaveStack, FLAT>(A, cursor + shard * HAR_COUNTER_STRIDE, n, stack, status, take, store,
         [&](bool, uint32_t, const Trav &) { });
 #endif
 }
+/* the seeded flavour exists where the branch-free refill and the refill-time commit do (the defaults) */
+#define HAR_TOP_SEED_KERNEL (HAR_REFILL_SELECT && !HAR_EXTRA_ROUNDS && HAR_CLOSEST_RETIRE)
 
 /* ------------------------------------------------------------- trace_packet */
 /*
@@ -2201,6 +2256,13 @@ void launch_trace_closest(hipStream_t s, uint32_t grid, uint2 *spill, const Acce
     /* scenes without a TLAS run the FLAT instantiation of the traversal (har_accel.h): no instance blocks, no world-space ray copy */
 #define HAR_LAUNCH_TC(SP, FL, LI) hipLaunchKernelGGL((k_trace_closest<SP, FL, LI>), dim3(grid), dim3(kBlock), 0, s, A, count, cursor, shard_cap, in.a0, in.a1, h0, h1, status, spill, list, stride, shard_count)
     const bool flat = !A.has_tlas && flat_kernels();
+#if HAR_TOP_SEED_KERNEL
+    /* Accel::top_seed: the seeded flavour of the plain two-level per-lane launch (no list, LDS stack) */
+    if (!pl && !spill && A.has_tlas && A.top_root != HAR_NO_NODE && A.top_count >= 1u && A.top_seed()) {
+        hipLaunchKernelGGL((k_trace_closest<false, false, false, true>), dim3(grid), dim3(kBlock), 0, s, A, count, cursor, shard_cap, in.a0, in.a1, h0, h1, status, spill, list, stride, shard_count);
+        return;
+    }
+#endif
     if (pl) { if (spill) HAR_LAUNCH_TC(true, false, true); else if (flat) HAR_LAUNCH_TC(false, true, true); else HAR_LAUNCH_TC(false, false, true); }
     else    { if (spill) HAR_LAUNCH_TC(true, false, false); else if (flat) HAR_LAUNCH_TC(false, true, false); else HAR_LAUNCH_TC(false, false, false); }
 #undef HAR_LAUNCH_TC

@@ -536,7 +536,15 @@ bool build_tlas(HostScene &hs, std::string &err) {
      * threshold (triangles), HAR_TOP_LAST: force the bit mask (A/B: 0 = round-2 order, 1 = any-hit only, 3 = both) */
     static const uint32_t top_last_max = getenv("HAR_TOP_LAST_MAX") ? (uint32_t) atoi(getenv("HAR_TOP_LAST_MAX")) : 256u;
     static const int top_last_forced = getenv("HAR_TOP_LAST") ? atoi(getenv("HAR_TOP_LAST")) : -1;
-    hs.top_last = top_last_forced >= 0 ? (uint32_t) top_last_forced : (!top.empty && top.tri_count <= top_last_max ? 3u : 0u);
+    hs.top_last = (top_last_forced >= 0 ? (uint32_t) top_last_forced : (!top.empty && top.tri_count <= top_last_max ? 3u : 0u)) & 3u;
+    /* Accel::top_seed (bit 2 of the word): closest-hit rays of the persistent kernel start at the TLAS root with the brute-force hit among the top-level triangles.
+     * Eligible: top-level geometry of 1 .. HAR_TOP_SEED_MAX triangles; the automatic choice is HAR_TOP_SEED_DEFAULT.  HAR_TOP_SEED=0 / 1 forces it off / on (on: any
+     * scene with top-level geometry); the variable is read at every build, so that one process can hold scenes of both kinds. */
+    const char *seed_env = getenv("HAR_TOP_SEED");
+    const bool seed_eligible = !top.empty && top.tri_count >= 1u && top.tri_count <= (uint32_t) HAR_TOP_SEED_MAX;
+    const bool seed_on = seed_env ? (atoi(seed_env) != 0 && !top.empty && top.tri_count >= 1u) : (HAR_TOP_SEED_DEFAULT != 0 && seed_eligible);
+    hs.top_seed_eligible = seed_eligible;
+    if (seed_on) hs.top_last |= HAR_TOP_SEED_BIT;
     for (uint32_t i = 0; i < n_inst; ++i) {
         const BlasInfo &g = hs.blas_groups[hs.inst_group[i]];
         if (g.empty) continue;

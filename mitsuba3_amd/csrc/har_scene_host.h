@@ -55,7 +55,8 @@ struct HostScene {
     bool has_tlas = false;
     Bvh8Stats stats;
     uint32_t blas_depth = 0, tlas_depth = 0;   /* traversal stack need = blas_depth + (has_tlas ? tlas_depth + 1 : 0) */
-    uint32_t top_last = 0;     /* Accel::top_last */
+    uint32_t top_last = 0;     /* Accel::top_last (bit 2: Accel::top_seed) */
+    bool top_seed_eligible = false;   /* 1 <= top_count <= HAR_TOP_SEED_MAX (build_tlas) */
     uint32_t top_root = 0xffffffffu, top_first = 0, top_count = 0;   /* two-level scenes: BLAS of the top-level geometry (Accel::top_root) */
     uint32_t stack_need() const { return blas_depth + (has_tlas ? tlas_depth + 1 : 0); }
     /* ---- what the incremental updates need (har_scene_update_instances / _vertices; Scene::parameters_changed -> m_accel.rebuild for the dirty shapes only,
