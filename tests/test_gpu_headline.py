@@ -168,6 +168,28 @@ def test_material_queues_equal_the_generic_kernel(mi, O):
             assert rel_l2(b, a) < 1e-4, k
 
 
+@pytest.mark.parametrize("setting, res, spp", [("material_queues", 512, 4), ("packet_tracing", 128, 64)])
+def test_two_stream_halves_share_the_settings(mi, setting, res, spp):
+    """a job of 2^20 lanes -- the smallest that is cut into two halves on two streams; `hide_emitters` switches the shadow-ray overlap off, which would keep
+    it on one -- with `material_queues` / `packet_tracing` on against off: the second half runs on the integrator's twin, which gets the settings as one
+    value.  Either setting gives the same paths and hit records as its default: equal path and vertex counts, images equal up to the order of the film's
+    float atomics (the tolerance of test_material_queues_equal_the_generic_kernel for the same comparison)"""
+    assert res * res * spp == 1 << 20
+    d = mi.instanced_spheres_scene(width=res, height=res, spp=spp, flatten=True, materials=True, grid=2, n_u=8, n_v=4)
+    d["sky"] = {"type": "constant", "radiance": {"type": "rgb", "value": [0.2, 0.3, 0.5]}}
+    d.pop("ceiling", None)
+    scene = mi.load_dict(d)
+    imgs, stats = {}, {}
+    for on in (False, True):
+        integ = mi.load_dict({"type": "path", "max_depth": 4, "hide_emitters": True, setting: on})
+        imgs[on] = mi.render(scene, integrator=integ, spp=spp, seed=3).cpu().numpy()
+        stats[on] = integ.stats()
+    assert stats[False]["paths"] == 1 << 20
+    assert stats[True]["paths"] == stats[False]["paths"] and stats[True]["vertices"] == stats[False]["vertices"]
+    assert np.isfinite(imgs[False]).all() and np.abs(imgs[False]).max() > 0
+    assert rel_l2(imgs[True], imgs[False]) < 1e-6
+
+
 # ------------------------------------------------------------------ N1 (ii): PRB gradients on the instanced scene with a bitmap albedo
 
 def test_prb_gradients_instanced_textured(mi, O):
