@@ -60,7 +60,13 @@ typedef struct HarInstance {
  *   type 3 roughplastic    (src/bsdfs/roughplastic.cpp)    slot0 = diffuse_reflectance, slot1 = specular_reflectance, eta, alpha_u
  *   type 4 conductor       (src/bsdfs/conductor.cpp)       slot0 = specular_reflectance, eta_c / k_c (RGB)
  *   type 5 plastic         (src/bsdfs/plastic.cpp)         slot0 = diffuse_reflectance, slot1 = specular_reflectance, eta
+ *   type 6 blendbsdf       (src/bsdfs/blendbsdf.cpp)       slot0 = weight: a constant stored as (w, w, w) or a bitmap; `nested` = the two mixed BSDF records
  * slot0 may be a bitmap texture (`texture` >= 0), slot1 is constant.
+ * A blend record evaluates clip(weight, 0, 1) of Texture::eval_1 -- the constant, channel 0 of a one-channel bitmap (HAR_BSDF_MONO: stored three times), the luminance
+ * of a three-channel one -- and returns (1 - w) * nested[0] + w * nested[1] for eval / pdf, samples nested[1] with probability w.  The nested records are leaf models
+ * (types 0 - 5) without the twosided flag; HAR_BSDF_TWOSIDED on the blend record itself is supported (no nested dielectric then).  Gradients (`prb`): the weight's is
+ * d / d weight in the record's own row / bitmap (zero where the weight is clipped), the nested records' colour slot 0 receive theirs in their own rows / bitmaps; every
+ * backward pass of a scene with such a record takes the replay-cache route with the in-place commit (max_depth <= 12, no vertex-position / alpha / eta / k gradients).
  * flags: bit0 twosided (src/bsdfs/twosided.cpp; `back` = record used for the back side, -1 = the same one),
  *        bit1 GGX distribution (else Beckmann), bit2 sample_visible, bit3 plastic / roughplastic `nonlinear`. */
 #define HAR_BSDF_DIFFUSE        0
@@ -69,10 +75,12 @@ typedef struct HarInstance {
 #define HAR_BSDF_ROUGHPLASTIC   3
 #define HAR_BSDF_CONDUCTOR      4
 #define HAR_BSDF_PLASTIC        5
+#define HAR_BSDF_BLEND          6
 #define HAR_BSDF_TWOSIDED       1u
 #define HAR_BSDF_GGX            2u
 #define HAR_BSDF_SAMPLE_VISIBLE 4u
 #define HAR_BSDF_NONLINEAR      8u
+#define HAR_BSDF_MONO           16u     /* blend: the weight bitmap has one channel */
 typedef struct HarBSDF {
     uint32_t type;
     int32_t  texture;     /* -1: constant slot0 (srgb), else bitmap index */
@@ -83,6 +91,7 @@ typedef struct HarBSDF {
     float    eta;                     /* int_ior / ext_ior */
     float    eta_c[3], k_c[3];        /* conductor: real and imaginary part of the relative IOR */
     int32_t  back;
+    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs (read for type 6 only) */
 } HarBSDF;
 
 /* BitmapTexture, raw H x W x 3 f32 (src/textures/bitmap.cpp:175-206). HOST pointer.  mode = filter_type | wrap_mode (bitmap.cpp:182-206):
@@ -403,6 +412,11 @@ int har_raygen_lanes_host(const HarSensor *sensor, const HarSensor *children, ui
  * point calls it.  `film` (HOST, H x W x 4 of the crop window, {R, G, B, W}) is accumulated into; children / n_children as for har_raygen_lanes_host. */
 int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
                           int32_t max_depth, int32_t rr_depth, float *film);
+/* The same render with its counters: `stats` (HOST, may be null) is added to, as har_render_stats' totals are -- paths = the lanes, vertices = the iterations of
+ * PathIntegrator::sample's loop summed over the lanes (what the wavefront's bounce counters add up to), closest_rays = one per iteration, shadow_rays = the emitter
+ * samples with a non-zero contribution, which alone are traced. */
+int har_render_lanes_stats_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
+                                int32_t max_depth, int32_t rr_depth, float *film, HarStats *stats);
 /* ImageBlock::put (src/render/imageblock.cpp:187-540): film is H x W x 4 {R,G,B,W} */
 int har_film_put(const HarSensor *sensor, uint32_t n, const float *pos_x, const float *pos_y,
                  const float *values4 /*[n][4]*/, float *film, void *stream);
@@ -649,6 +663,13 @@ int har_aov_sample(HarScene scene, uint32_t n, const float *o, const float *d, c
  * every lane runs the per-lane AOV code the kernels run.  All pointers HOST. */
 int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const float *o, const float *d, const float *maxt, const uint8_t *active, uint32_t n_aovs,
                         const uint32_t *types, float *out);
+/* BSDF::eval_pdf / BSDF::sample of record `bsdf` of a scene on the HOST (no GPU): the scene is lowered as har_render_scalar does and every lane runs the per-lane code of
+ * har_bsdf_eval_pdf / har_bsdf_sample (twosided and blend records resolved, the caller's context honoured).  All pointers HOST; array shapes as for the device entries;
+ * `value` / `pdf` of the first, `eta` / `sampled_type` / `sampled_component` of the second may be NULL. */
+int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo,
+                           const uint8_t *active, float *value, float *pdf);
+int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
+                         const float *sample2, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component);
 /* The AOV pass of AOVIntegrator::render (aov.cpp:389-470: one more SamplingIntegrator pass with the same sampler seed): lanes [lane_begin, lane_end) (0, 0 = all) of the
  * wavefront of render() at `seed` / `spp` -- the same lanes, film positions and camera rays as there -- accumulate into `aov_film` (DEVICE, H x W x (C + 1): the C
  * channels, then the reconstruction filter's weight; accumulated, not cleared, not developed).  `integrator` gives the chunk size (chunk_lanes) and the film window

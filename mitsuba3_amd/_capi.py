@@ -34,7 +34,7 @@ class HarInstance(C.Structure):
 class HarBSDF(C.Structure):
     _fields_ = [("type", C.c_uint32), ("texture", C.c_int32), ("reflectance", C.c_float * 3), ("flags", C.c_uint32),
                 ("reflectance2", C.c_float * 3), ("alpha_u", C.c_float), ("alpha_v", C.c_float), ("eta", C.c_float),
-                ("eta_c", C.c_float * 3), ("k_c", C.c_float * 3), ("back", C.c_int32)]
+                ("eta_c", C.c_float * 3), ("k_c", C.c_float * 3), ("back", C.c_int32), ("nested", C.c_int32 * 2)]
 
 
 class HarTexture(C.Structure):
@@ -164,6 +164,7 @@ SIGNATURES = {
     "har_batch_sample_ray_aperture_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
     "har_raygen_lanes_host": (C.c_int, [C.POINTER(HarSensor), C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, vp, f32p, f32p, f32p, f32p, vp]),
     "har_render_lanes_host": (C.c_int, [C.POINTER(HarSceneDesc), C.POINTER(HarSensor), C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, f32p]),
+    "har_render_lanes_stats_host": (C.c_int, [C.POINTER(HarSceneDesc), C.POINTER(HarSensor), C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint32, C.c_int32, C.c_int32, f32p, C.POINTER(HarStats)]),
     "har_integrator_set_batch_sensors": (C.c_int, [vp, C.POINTER(HarSensor), C.c_uint32, vp]),
     "har_batch_sample_ray": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "har_batch_sample_ray_host": (C.c_int, [C.POINTER(HarSensor), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p]),
@@ -190,6 +191,8 @@ SIGNATURES = {
     "har_aov_channel_count": (C.c_int, [C.c_uint32, u32p, u32p]),
     "har_aov_sample": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u32p, vp, vp]),
     "har_aov_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, vp, C.c_uint32, u32p, f32p]),
+    "har_bsdf_eval_pdf_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, vp, f32p, f32p]),
+    "har_bsdf_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, u32p, u32p]),
     "har_render_aovs": (C.c_int, [vp, vp, C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, u32p, vp, vp]),
     "har_transform_translate": (C.c_int, [f32p, f32p]),
     "har_transform_scale": (C.c_int, [f32p, f32p]),

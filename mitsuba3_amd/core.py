@@ -286,6 +286,7 @@ class BSDFFlags:
     DeltaReflection = 0x20; DeltaTransmission = 0x40; Delta1DReflection = 0x80; Delta1DTransmission = 0x100
     Reflection = 0x2 | 0x20 | 0x80 | 0x8; Transmission = 0x4 | 0x40 | 0x100 | 0x10 | 0x1
     Diffuse = 0x2 | 0x4; Glossy = 0x8 | 0x10; Smooth = 0x2 | 0x4 | 0x8 | 0x10; Delta = 0x1 | 0x20 | 0x40; Delta1D = 0x80 | 0x100; All = 0x1ff
+    Anisotropic = 0x1000; NonSymmetric = 0x4000; FrontSide = 0x8000; BackSide = 0x10000          # lobe attributes (bsdf.h:71-83): reported by BSDF.flags(), not part of a type mask
 
 
 class BSDFContext:
@@ -441,7 +442,7 @@ def _cube(props):
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
-    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf',
+    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
@@ -996,7 +997,8 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 # BitmapTexture(props) (src/textures/bitmap.cpp:175-260); `raw` only silences a range warning for float data in RGB variants, `accel` picks Dr.Jit's texture
 # hardware path on CUDA (no effect on values), `format` = the storage type of the texels ("auto" / "variant" / "fp16": this path keeps float32)
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
-BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5}
+BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6}
+_LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
 # (parameter name of slot 0, default), (parameter name of slot 1, default)
 _BSDF_SLOTS = {'diffuse': (('reflectance', 0.5), None), 'dielectric': (('specular_reflectance', 1.0), ('specular_transmittance', 1.0)),
                'roughconductor': (('specular_reflectance', 1.0), None), 'roughplastic': (('diffuse_reflectance', 0.5), ('specular_reflectance', 1.0)),
@@ -1046,6 +1048,17 @@ def _bitmap_from_props(refl):
     return np.ascontiguousarray(t, np.float32), tex_mode, tex_to_uv
 
 
+class _RecordFlags(int):
+    """BlendBSDF.flags: an int (the record's flag word, as on every BSDF) that answers BSDF::flags() / BSDF::flags(i) when called"""
+
+    def __new__(cls, value, owner):
+        obj = int.__new__(cls, value); obj._owner = owner
+        return obj
+
+    def __call__(self, index=None):
+        return self._owner._lobe_flags(index)
+
+
 class BSDF:
     """diffuse / dielectric / conductor / plastic / roughconductor / roughplastic (src/bsdfs/*.cpp), optionally wrapped by `twosided`.
     Colour parameters live in two slots (include/hip_ad_rgb.h HarBSDF); slot 0 may be a raw `bitmap`."""
@@ -1054,6 +1067,8 @@ class BSDF:
         props = props or {}
         self.id = id
         self.kind = props.get('type', 'diffuse')
+        if self.kind == 'blendbsdf':
+            raise RuntimeError("blendbsdf: built by the plugin factory (mi.load_dict), which resolves its nested BSDFs")
         if self.kind not in BSDF_TYPES:
             raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb" % self.kind)
         _check_props(self.kind, props, _BSDF_PROPS[self.kind], free_children=False)
@@ -1159,13 +1174,103 @@ class BSDF:
         bs = type("BSDFSample3f", (), dict(wo=wo, pdf=pdf, eta=eta, sampled_type=st, sampled_component=sc, delta=(st & BSDFFlags.Delta) != 0))()
         return bs, w
 
+    def _own_lobes(self):
+        """BSDFFlags of the components of this plugin without a `twosided` wrapper (the constructors of src/bsdfs/*.cpp)"""
+        F = BSDFFlags; fs = F.FrontSide
+        return {'diffuse': [F.DiffuseReflection | fs], 'dielectric': [F.DeltaReflection | fs | F.BackSide, F.DeltaTransmission | fs | F.BackSide | F.NonSymmetric],
+                'roughconductor': [F.GlossyReflection | fs | (F.Anisotropic if self.alpha_u != self.alpha_v else 0)],
+                'roughplastic': [F.GlossyReflection | fs, F.DiffuseReflection | fs], 'conductor': [F.DeltaReflection | fs], 'plastic': [F.DeltaReflection | fs, F.DiffuseReflection | fs]}[self.kind]
+
+    def _lobe_flags(self, index=None):
+        """BSDF::flags() / BSDF::flags(i): the union of the lobes' BSDFFlags, or those of component i (twosided.cpp:86-99: the front BSDF's lobes on the front side, then the back's
+        on the back side)"""
+        lobes = self._own_lobes()
+        if int(self.flags) & 1:
+            back = self.back._own_lobes() if self.back is not None else lobes
+            side = BSDFFlags.FrontSide | BSDFFlags.BackSide
+            lobes = [(c & ~side) | BSDFFlags.FrontSide for c in lobes] + [(c & ~side) | BSDFFlags.BackSide for c in back]
+        if index is None:
+            out = 0
+            for c in lobes:
+                out |= c
+            return out
+        return lobes[index]
+
     def component_count(self):
-        """BSDF::component_count(): the lobes of this plugin (twosided: the front BSDF's, then the back's, twosided.cpp:86-99)"""
-        own = {'dielectric': 2, 'roughplastic': 2, 'plastic': 2}
-        n = own.get(self.kind, 1)
+        """BSDF::component_count(): the lobes of this plugin (twosided: the front BSDF's, then the back's, twosided.cpp:86-99; blendbsdf: the two nested BSDFs')"""
+        n = len(self._own_lobes())
         if self.flags & 1:
-            return n + (own.get(self.back.kind, 1) if self.back is not None else n)
+            return n + (len(self.back._own_lobes()) if self.back is not None else n)
         return n
+
+
+class BlendBSDF(BSDF):
+    """BlendBSDF (src/bsdfs/blendbsdf.cpp:80-100): a BSDF record whose colour slot 0 is the `weight` (a float, or a raw bitmap of 1 or 3 channels) and which names two nested
+    BSDFs; these become records of their own (Scene._add_bsdf)."""
+
+    def __init__(self, weight, nested, id=None):
+        self.id = id; self.kind = 'blendbsdf'; self.slot0_name = 'weight'; self.slot1_name = None
+        self.texture = None; self.tex_mode = 0; self.tex_to_uv = None; self.weight_channels = 0
+        if isinstance(weight, (int, float)) and not isinstance(weight, bool):
+            self.value = _f32([float(weight)] * 3)
+        elif isinstance(weight, dict) and weight.get('type') == 'bitmap':
+            self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(weight)
+            src = weight['data'] if 'data' in weight else (weight['bitmap'].data if isinstance(weight.get('bitmap'), Bitmap) else Bitmap(weight['filename']).data)
+            ch = 1 if len(tuple(src.shape)) == 2 else int(src.shape[2])
+            if ch not in (1, 3):
+                raise RuntimeError("blendbsdf: the `weight` bitmap has %d channels, expected 1 or 3" % ch)
+            self.weight_channels = ch
+            self.value = _f32([0.5, 0.5, 0.5])
+        else:
+            raise RuntimeError("blendbsdf: `weight` is a float or a `bitmap` texture")
+        self.value2 = _f32([0, 0, 0]); self.flags = 16 if self.weight_channels == 1 else 0          # (16: slot 0 is a one-channel bitmap, read channel 0)
+        self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
+        self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
+        self.scene = None; self.index = None
+        self.nested = list(nested)
+        for k, c in enumerate(self.nested):
+            if getattr(c, 'blend_parent', None) is None and c.scene is None:
+                c.blend_parent = (self, k)        # NAMES its parameters '<blend>.bsdf_<k>.*' (BlendBSDF::traverse, blendbsdf.cpp:102-106); what is refused for a nested record is decided from the scene's records, Scene._blend_nested
+
+    def _own_lobes(self):
+        """the nested BSDFs' components in order (blendbsdf.cpp:94-97)"""
+        return self.nested[0]._own_lobes() + self.nested[1]._own_lobes()
+
+    # the record's flag word (HarBSDF::flags: twosided, GGX, ...) wherever it is read or written, BSDF::flags() / BSDF::flags(i) when called
+    @property
+    def flags(self):
+        return _RecordFlags(self._flags, self)
+
+    @flags.setter
+    def flags(self, value):
+        self._flags = int(value)
+
+
+def _mk_blendbsdf(props, named, key):
+    """the `blendbsdf` plugin: `weight` and exactly two nested BSDFs under free names, in declaration order (blendbsdf.cpp:80-92)"""
+    _check_props('blendbsdf', props, ('weight',), children=('bsdf',))
+    nested = []
+    for k, v in props.items():
+        if k in ('type', 'id', 'weight'):
+            continue
+        obj = _resolve(v, named, k) if isinstance(v, dict) else v
+        if isinstance(obj, BSDF):
+            if len(nested) == 2:
+                raise RuntimeError("BlendBSDF: Cannot specify more than two child BSDFs")
+            nested.append(obj)
+    if 'weight' not in props:
+        raise RuntimeError("Property \"weight\" has not been specified!")
+    if len(nested) != 2:
+        raise RuntimeError("BlendBSDF: Two child BSDFs must be specified!")
+    for c in nested:
+        if c.kind == 'blendbsdf' or (c.flags & 1):
+            raise RuntimeError("blendbsdf: nested BSDFs must be plain BSDF models in this variant")
+    return BlendBSDF(props['weight'], nested, id=key)
+
+
+def _transmits(b):
+    """does the BSDF have a transmission lobe (what `twosided` refuses, twosided.cpp:79-83)"""
+    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested))
 
 
 def _mk_twosided(props, named, key):
@@ -1181,7 +1286,7 @@ def _mk_twosided(props, named, key):
     if not nested or len(nested) > 2:
         raise RuntimeError("twosided: a maximum of two nested BSDFs can be specified (and at least one)!")
     for b in nested:
-        if b.kind == 'dielectric':
+        if _transmits(b):
             raise RuntimeError("Only materials without a transmission component can be nested!")
     front = nested[0]
     if front.flags & 1:
@@ -1614,6 +1719,9 @@ class Integrator:
         else:
             check(lib().har_integrator_set_grad_positions(self._handle(), None, None))
             check(lib().har_integrator_set_grad_instances(self._handle(), None, None))
+        if self.bsdf_parameter_gradients and any(b.kind == 'blendbsdf' for b in scene.bsdfs):
+            raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `blendbsdf` in hip_ad_rgb (its `weight` and the nested BSDFs' colour slot 0 have gradients)"
+                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what != "ior"))
         g_extra = torch.zeros((max(1, len(scene.bsdfs)), 15), dtype=torch.float32, device=dev) if self.bsdf_parameter_gradients else None
         try:
             check(lib().har_integrator_set_grad_emitters(self._handle(), _ptr(g_emit) if self.emitter_gradients else None))
@@ -1680,6 +1788,15 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
     for k, v in tangents.items():
         kind, b = keys[k]
         v = torch.as_tensor(v, dtype=torch.float32, device=dev)
+        if kind != "emit" and id(b) in scene._blend_nested():
+            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` are not produced in hip_ad_rgb (the weight's are; use render_backward)" % k)
+        if kind != "emit" and b.kind == 'blendbsdf':
+            # the tangent of the weight, in every colour channel of the record's slot 0 (a three-channel bitmap: of its luminance)
+            if kind == "tex" and b.weight_channels == 3:
+                shape = t_tex[b.tex_index].shape
+                v = (v.reshape(shape) * v.new_tensor(_LUMINANCE).reshape(1, 1, 3)).sum(dim=2, keepdim=True).expand(shape).contiguous()
+            else:
+                v = scene._colour_store(kind, b, v, k)
         if kind == "tex":
             t_tex[b.tex_index].copy_(v.reshape(t_tex[b.tex_index].shape))
         elif kind == "emit":
@@ -2023,6 +2140,8 @@ class Scene:
         if b.texture is not None:
             b.tex_index = len(self.textures); self.textures.append(b.texture); self.texture_modes.append(b.tex_mode); self.texture_to_uv.append(b.tex_to_uv)
         self.bsdf_objs.append(b)
+        for c in getattr(b, 'nested', ()):           # blendbsdf: the nested BSDFs are records of their own (an object referenced from several places is lowered once)
+            self._add_bsdf(c)
         if getattr(b, 'back', None) is not None:
             self._add_bsdf(b.back)
         return b.index
@@ -2030,6 +2149,10 @@ class Scene:
     @property
     def bsdfs(self):
         return self.bsdf_objs
+
+    def _blend_nested(self):
+        """ids of the BSDF objects whose record is nested in a blend record of this scene -- also one that a shape or another blend references besides"""
+        return {id(c) for b in self.bsdf_objs for c in getattr(b, 'nested', ())}
 
     def _add_mesh(self, key, m):
         if m.bsdf is None:          # Shape(props), shape.cpp:50-57: a default diffuse BSDF -- black when the shape carries an emitter
@@ -2135,6 +2258,8 @@ class Scene:
             bsdfs[i].alpha_u = b.alpha_u; bsdfs[i].alpha_v = b.alpha_v; bsdfs[i].eta = b.eta
             bsdfs[i].eta_c = (C.c_float * 3)(*[float(x) for x in b.eta_c]); bsdfs[i].k_c = (C.c_float * 3)(*[float(x) for x in b.k_c])
             bsdfs[i].back = b.back.index if b.back is not None else -1
+            if b.kind == 'blendbsdf':
+                bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, b.nested[1].index)
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
             texs[i].data = _fp(t); texs[i].height = t.shape[0]; texs[i].width = t.shape[1]; texs[i].mode = self.texture_modes[i] if i < len(self.texture_modes) else 0
@@ -2247,6 +2372,9 @@ class Scene:
         """the prefix of a BSDF's parameters in mi.traverse(): its id -- the scene-level key, or '<shape>.bsdf' -- and, for the BSDFs nested in a `twosided`, the names
         TwoSidedBRDF::traverse registers them under (twosided.cpp:106-109): '<twosided>.brdf_0' and, when the back side is a BSDF of its own, '<twosided>.brdf_1'
         (util.py:320-334 walks an object once, so a twosided with ONE nested BSDF has no brdf_1 entries)"""
+        bp = getattr(b, 'blend_parent', None)
+        if bp is not None:          # nested in a blendbsdf (BlendBSDF::traverse, blendbsdf.cpp:102-106): '<blend>.bsdf_0' / '<blend>.bsdf_1'
+            return Scene._bsdf_key_base(bp[0]) + ".bsdf_%d" % bp[1]
         parent = getattr(b, 'twosided_parent', None)
         if parent is not None:
             return (parent.id if parent.id else "bsdf%d" % parent.index) + ".brdf_1"
@@ -2807,9 +2935,43 @@ class Scene:
             if kind == "emit":
                 if g_emit is not None:
                     out[k] = g_emit[b]
+            elif b.kind == 'blendbsdf':
+                # the weight of a blend: the buffers hold d L / d w per colour channel of the radiance; the parameter is a scalar (sum of the row, as `alpha` is summed), a
+                # one-channel bitmap (channel sum) or a three-channel one whose luminance is the weight (d w / d texel_k = lum_k)
+                if kind == "tex":
+                    s = g_tex[b.tex_index].sum(dim=2, keepdim=True)
+                    out[k] = s if b.weight_channels == 1 else s * s.new_tensor(_LUMINANCE).reshape(1, 1, 3)
+                else:
+                    out[k] = g_refl[b.index].sum().reshape(1)
             else:
                 out[k] = g_tex[b.tex_index] if kind == "tex" else g_refl[b.index]
         return out
+
+    @staticmethod
+    def _colour_view(kind, b, value):
+        """the value mi.traverse() shows for slot 0 of a BSDF: the stored one, except a blend's weight -- a scalar, or the H x W x 1 / x 3 bitmap it was given"""
+        if b.kind != 'blendbsdf':
+            return value
+        v = np.asarray(value, np.float32)
+        if kind == "tex":
+            return np.ascontiguousarray(v[:, :, :1]) if b.weight_channels == 1 else v
+        return v.reshape(-1)[:1].copy()
+
+    @staticmethod
+    def _colour_store(kind, b, t, key):
+        """the inverse for a blend's weight, on a torch tensor or a numpy array: a scalar is stored as (w, w, w), a one-channel bitmap three times"""
+        if b.kind != 'blendbsdf':
+            return t
+        if kind == "tex":
+            h, w = b.texture.shape[:2]; c = b.weight_channels
+            if int(np.prod(tuple(t.shape))) != h * w * c:
+                raise RuntimeError("%s: expected a tensor of shape %s" % (key, (h, w, c)))
+            t = t.reshape(h, w, c)
+            return t if c == 3 else (t.expand(h, w, 3).contiguous() if hasattr(t, 'expand') else np.ascontiguousarray(np.repeat(t, 3, axis=2)))
+        if int(np.prod(tuple(t.shape))) != 1:
+            raise RuntimeError("%s: expected 1 value" % key)
+        t = t.reshape(1)
+        return t.expand(3).contiguous() if hasattr(t, 'expand') else np.repeat(t, 3)
 
 
 class ParamFlags:
@@ -2865,7 +3027,7 @@ class SceneParameters(dict):
         scene.sync_host()
         dev = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else torch.device("cpu")
         for k, (kind, b) in scene._param_keys().items():
-            value = scene.emitters[b]["radiance"] if kind == "emit" else (b.texture if kind == "tex" else b.value)
+            value = scene.emitters[b]["radiance"] if kind == "emit" else scene._colour_view(kind, b, b.texture if kind == "tex" else b.value)
             self[k] = torch.tensor(np.asarray(value, np.float32), dtype=torch.float32, device=dev)
         for k, (what, b) in scene._bsdf_param_keys().items():
             self[k] = torch.tensor(np.asarray(scene._bsdf_param_value(what, b), np.float32), dtype=torch.float32, device=dev)
@@ -3084,6 +3246,8 @@ class SceneParameters(dict):
             if on_gpu:
                 # the scene's copy is the value AT update(): snapshot on the device (a later in-place edit of the tensor is not an update), host mirror refreshed lazily
                 v = t.detach().to(torch.float32).contiguous()
+                if kind != "emit":
+                    v = sc._colour_store(kind, b, v, k)
                 stream = stream or _stream()
                 if kind == "emit":
                     if v.numel() != 3:
@@ -3101,6 +3265,8 @@ class SceneParameters(dict):
                 pushed[k] = new_mark
                 continue
             v = t.detach().to("cpu").numpy().astype(np.float32) if hasattr(t, "detach") else np.asarray(t, np.float32)
+            if kind != "emit":
+                v = sc._colour_store(kind, b, v, k)
             if kind == "emit":
                 sc._device_values.pop(("emit", b), None)
                 sc.emitters[b]["radiance"] = np.ascontiguousarray(v.reshape(3))
@@ -3289,7 +3455,7 @@ class DeviceGroup:
 # ---------------------------------------------------------------------------
 
 _REGISTRY = {}
-_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided')
+_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf')
 
 
 def register_plugin(name, variant_name, instantiate):
@@ -3431,7 +3597,7 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
@@ -3492,6 +3658,9 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
     if fixed:       # ParamFlags::NonDifferentiable in the reference's traverse(): dr.enable_grad on them has no effect there; here it is said
         raise RuntimeError("%s are not differentiable parameters in hip_ad_rgb (placement of sensors and delta emitters: ParamFlags::NonDifferentiable in the reference; "
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
+    nested = [k for k in keys if k in scene._bsdf_param_keys() and id(scene._bsdf_param_keys()[k][1]) in scene._blend_nested()]
+    if nested:
+        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` have no gradient in hip_ad_rgb (its `weight` and the nested BSDFs' colour slot 0 do)" % nested)
     if not keys:
         return integrator.render(scene, sensor, seed, spp)
     params.update()

@@ -43,12 +43,25 @@ inline const char *aov_spec_lower(uint32_t n, const uint32_t *types, AovSpec &sp
  *  - `diffuse`: the reflectance texture at si.uv (diffuse.cpp:181); `plastic` / `roughplastic`: `diffuse_reflectance` (plastic.cpp:362, roughplastic.cpp:504);
  *    both are colour slot 0 of the record;
  *  - every other model: the base class, eval(BSDFContext(), si, wo = (0, 0, 1)) * pi (src/render/bsdf.cpp:38-43). */
+template <bool BLEND = false>        /* BLEND: the scene may hold `blendbsdf` records (the kernels of other scenes compile that branch out) */
 HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
     BsdfSide side;
     if (!bsdf_side(S, S.meshes[si.mesh].bsdf, si.wi, side)) return Vec3(0.f);
     const DBsdf &B = S.bsdfs[side.index];
     TexTaps taps;
     const BsdfInputs in = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps);
+    if (BLEND && B.type == BSDF_BLEND) {       /* BlendBSDF::eval_diffuse_reflectance (blendbsdf.cpp:228-233): rho_0 * (1 - w) + rho_1 * w of the nested BSDFs' own answers */
+        bool inside; const float w = blend_weight(B, in, inside);
+        const uint32_t child[2] = { (uint32_t) B.table, B.pad };
+        Vec3 rho[2];
+        for (int k = 0; k < 2; ++k) {
+            const DBsdf &N = S.bsdfs[child[k]];
+            TexTaps nt; const BsdfInputs nin = bsdf_inputs(S, N, si.uv_x, si.uv_y, nt);
+            if (N.type == BSDF_DIFFUSE || N.type == BSDF_ROUGHPLASTIC || N.type == BSDF_PLASTIC) rho[k] = nin.slot0;
+            else { BsdfEval ne; bsdf_eval_pdf_one<HAR_BSDF_ALL_TYPES, false>(N, nin, side.wi, Vec3(0.f, 0.f, 1.f), ne); rho[k] = ne.value * HAR_PI; }
+        }
+        return rho[0] * (1.f - w) + rho[1] * w;
+    }
     if (B.type == BSDF_DIFFUSE || B.type == BSDF_ROUGHPLASTIC || B.type == BSDF_PLASTIC) return in.slot0;
     BsdfEval e;
     bsdf_eval_pdf_one<HAR_BSDF_ALL_TYPES, false>(B, in, side.wi, Vec3(0.f, 0.f, 1.f), e);
@@ -59,6 +72,7 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
  * si.p comes from the triangle), `top_meshes` = number of top-level meshes of the scene.
  * shape_index (aov.cpp:288-297, the scalar branch): the 1-based position of the hit instance -- or, without one, of the hit shape -- in the
  * scene's shape list, which here is { top-level meshes, instances }; 0 on a miss. */
+template <bool BLEND = false>
 HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, Vec3 ray_d, const Hit &hit, bool active, float *out, size_t stride) {
     const bool valid = active && hit.t != HAR_INF;
     SurfInt si; SurfPartials P;
@@ -68,7 +82,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
     if (valid) {
         si = compute_si(S, ray_d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
         if (need_partials) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
-        if (need_albedo) albedo = aov_albedo(S, si);
+        if (need_albedo) albedo = aov_albedo<BLEND>(S, si);
     }
     size_t c = 0;
     for (uint32_t k = 0; k < spec.n; ++k) {

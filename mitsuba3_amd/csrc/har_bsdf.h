@@ -6,6 +6,7 @@
  *   type 2  roughconductor   src/bsdfs/roughconductor.cpp:226-520       (Beckmann / GGX microfacet, conductor Fresnel)
  *   type 3  roughplastic     src/bsdfs/roughplastic.cpp:244-420         (rough dielectric coating over a diffuse base)
  *   flag    twosided         src/bsdfs/twosided.cpp:112-270             (one nested BSDF, or a different one on the back)
+ *   type 6  blendbsdf        src/bsdfs/blendbsdf.cpp:108-233            (two nested records mixed by a weight; resolved in har_scene.h, where the scene's records are at hand)
  *
  * plus include/mitsuba/render/fresnel.h:35-91 (fresnel), :93-116 (fresnel_conductor), :276-313 (reflect / refract)
  * and  include/mitsuba/render/microfacet.h:185-421 (MicrofacetDistribution eval / pdf / sample / smith_g1).
@@ -20,8 +21,11 @@
 
 namespace har {
 
-enum { BSDF_DIFFUSE = 0, BSDF_DIELECTRIC = 1, BSDF_ROUGHCONDUCTOR = 2, BSDF_ROUGHPLASTIC = 3, BSDF_CONDUCTOR = 4, BSDF_PLASTIC = 5, BSDF_TYPE_COUNT = 6 };
-enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u };
+enum { BSDF_DIFFUSE = 0, BSDF_DIELECTRIC = 1, BSDF_ROUGHCONDUCTOR = 2, BSDF_ROUGHPLASTIC = 3, BSDF_CONDUCTOR = 4, BSDF_PLASTIC = 5, BSDF_TYPE_COUNT = 6 /* the leaf models */,
+       BSDF_BLEND = 6 /* a record that names two leaf records (DBsdf::table, ::pad) and mixes them by the weight in slot 0 */ };
+/* BF_MONO: the bitmap in slot 0 of a blend record has ONE channel (stored three times): Texture::eval_1 reads it instead of taking the luminance (bitmap.cpp:537-540).
+ * BF_BLEND_SMOOTH: derived when a blend record is lowered -- one of its nested BSDFs has a smooth lobe (BSDFFlags::Smooth of the union, blendbsdf.cpp:99) */
+enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u, BF_MONO = 16u, BF_BLEND_SMOOTH = 32u };
 #define HAR_ROUGH_TRANSMITTANCE_RES 64          /* MI_ROUGH_TRANSMITTANCE_RES, include/mitsuba/render/microfacet.h */
 
 /* colour parameter slots: slot 0 = diffuse.reflectance | roughconductor.specular_reflectance |
@@ -34,9 +38,9 @@ struct DBsdf {
     float alpha_u, alpha_v, eta;
     float eta_c[3], k_c[3];
     int32_t back;                 /* twosided: BSDF record of the back side (-1: the same record) */
-    int32_t table;                /* roughplastic: offset of its 64-entry external transmittance table, else -1 */
+    int32_t table;                /* roughplastic: offset of its 64-entry external transmittance table, else -1; blend: record index of nested BSDF 0 */
     float inv_eta_2, internal_reflectance, spec_sampling_weight;
-    uint32_t pad;
+    uint32_t pad;                 /* blend: record index of nested BSDF 1 */
 };
 static_assert(sizeof(DBsdf) == 96, "DBsdf layout");
 
@@ -291,6 +295,10 @@ HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC &&
 /* ... and an area light that radiates a BITMAP (emitter type 7): its texel-distribution code costs the generic kernels registers they do not have (128, spills), so
  * only scenes with such a light run kernels that carry it: TYPES = HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT */
 #define HAR_SCENE_TEXLIGHT 0x400u
+/* ... and a `blendbsdf` record (type 6): two models run at one vertex, which no kernel of another scene pays for.  A scene with such a record runs ONE widest
+ * instantiation per launch, TYPES = HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_BLEND; every line of blend code sits behind a test of this bit */
+#define HAR_SCENE_BLEND 0x800u
+#define HAR_SCENE_BLEND_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_BLEND)
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */

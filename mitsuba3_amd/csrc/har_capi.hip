@@ -652,7 +652,9 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     chunk = std::min(chunk, I->bw_chunk_max);
     /* texels of a light's bitmap radiance: committed in place by the re-shading replay as well (the record tape holds neither the sampled uv nor the unit weight) */
     const bool light_texels = I->set.grad_light_texels && (S->ds.bsdf_types & HAR_SCENE_TEXLIGHT) != 0u;
-    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && chunk <= (1u << 29)) ? 2 : 1;
+    /* a `blendbsdf` record: the nested records' gradients are deposited by the in-place commit of the re-shading replay (the record tape holds one record per vertex) */
+    const bool blend = (S->ds.bsdf_types & HAR_SCENE_BLEND) != 0u;
+    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
     tape = std::min(tape, I->bw_tape_max);
     /* The tapes are the large workspaces (record tape 69 B, state tape 115 B per lane and bounce against 25 B for the lane-indexed cache: 28 - 90 GB for a 2^26-lane chunk
      * at max_depth 6 - 12).  When the device -- or the host's allocator pool, shared with the caller's tensors -- cannot hold one, step down instead of failing: record
@@ -690,6 +692,12 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
         if (!I->set.use_cache || I->shape_on) return fail("gradients of a light's texels need the replay cache and cannot be combined with vertex-position gradients");
         if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail("gradients of a light's texels: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
         if (!W.adjoint_inline) return fail("gradients of a light's texels need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
+    }
+    if (blend) {
+        if (I->set.grad_bsdf_params) return fail("blendbsdf: gradients of alpha / eta / k / specular colours are not produced for scenes with a blend record (the weight and the nested BSDFs' colour slot 0 are)");
+        if (!I->set.use_cache || I->shape_on) return fail("blendbsdf: gradients need the replay cache and cannot be combined with vertex-position gradients");
+        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail("blendbsdf: gradients of a scene with a blend record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
+        if (!W.adjoint_inline) return fail("blendbsdf: gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (I->set.grad_bsdf_params) {
         /* the alpha / eta / k / slot-1 terms are committed in place by the cached-bounce shading kernel only */
@@ -802,6 +810,8 @@ int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const 
          * of the models come from har_bsdf_dir.h); the rest of the scene may carry any model -- a vertex next to moving geometry contributes through its
          * attached si.wi (prb.py:128-140) */
         const size_t nm = S->hs.meshes.size();
+        /* their adjoint goes through items, which carry one (record, direct, relative) triple per vertex: a blend vertex has three */
+        if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("vertex-position gradients are not produced for a scene with a `blendbsdf` record");
         offset.assign(nm, -1); user.assign(nm, nullptr); count.assign(nm, 0);
         for (size_t m = 0; m < nm; ++m) {          /* top-level meshes, then the meshes of the shape groups (vertex positions shared by all their instances) */
             if (!grad_positions[m]) continue;
@@ -842,6 +852,7 @@ int har_integrator_set_grad_instances(HarIntegrator I, HarScene S, float *grad_t
     uint32_t n = 0;
     if (grad_to_world) {
         if (!S) return fail("null scene");
+        if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("instance to_world gradients are not produced for a scene with a `blendbsdf` record");
         /* as for the vertex positions: any BSDF with a non-delta lobe on the moving geometry, i.e. on the meshes of the shape groups */
         for (size_t m = S->hs.top_mesh_count; m < S->hs.meshes.size(); ++m)
             if (!record_has_smooth_lobe(S->hs, S->hs.meshes[m].bsdf)) return fail("instance to_world gradients: an instanced mesh cannot carry a BSDF made of delta lobes only (`dielectric`, `conductor`); top-level meshes may");

@@ -1005,6 +1005,27 @@ __device__ __forceinline__ void light_texel_commit(const DScene &S, float *const
         wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
     }
 }
+/* g = d L / d (slot 0 of BSDF record `rec`, evaluated at (u, v)) deposited where that record's gradient lives: its row of `grad_slots`, or -- a bitmap -- its entry of
+ * `grad_tex` through the transpose of the lookup.  What the in-place commit of a BLEND vertex does for the two nested records (the weight's own gradient rides in the
+ * vertex's ordinary commit, adjoint_commit_regs): it only deposits -- no update of L, no emitter part.  Called by whole waves; lanes aimed at the same address are pre-reduced. */
+__device__ __forceinline__ void blend_child_commit(const DScene &S, float *grad_slots, float *const *grad_tex, bool pred, uint32_t rec, float u, float v, Vec3 g) {
+    pred = pred && (g.x != 0.f || g.y != 0.f || g.z != 0.f);
+    if (!__ballot(pred)) return;
+    TexTaps taps; float *dst = nullptr; bool tex = false;
+    taps.idx[0] = taps.idx[1] = taps.idx[2] = taps.idx[3] = 0u; taps.w0x = taps.w1x = taps.w0y = taps.w1y = 0.f;
+    if (pred) {
+        const int32_t t = S.bsdfs[rec].texture;
+        if (t >= 0) { tex = true; tex_taps(S.textures[t], u, v, taps); dst = grad_tex[t]; }
+        else dst = grad_slots + 3 * (size_t) rec;
+    }
+    wave_aggregated_add3(dst, g, pred && !tex);
+    if (!__ballot(pred && tex)) return;
+    const float w[4] = { taps.w0x * taps.w0y, taps.w1x * taps.w0y, taps.w0x * taps.w1y, taps.w1x * taps.w1y };
+    for (int k = 0; k < 4; ++k) {
+        const bool on = pred && tex && w[k] != 0.f;
+        wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
+    }
+}
 template <bool FWD = false>
 __device__ __forceinline__ void adjoint_commit_values(const DScene &S, bool pred, bool visible, uint32_t lane, float4 s2, float4 s3, float4 s4, float4 *result, const float4 *dL,
                                                       float *grad_refl, float *const *grad_tex, float *gacc, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr) {
@@ -1354,6 +1375,16 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                     if (v.x == 0.f && v.y == 0.f && v.z == 0.f) continue;
                     if (R.bsdf < HAR_LDS_EXTRA_BSDFS) { float *a = xacc + 15 * R.bsdf + 3 * g; atomicAdd(a, v.x); atomicAdd(a + 1, v.y); atomicAdd(a + 2, v.z); }
                     else { float *a = grad_extra + 15 * (size_t) R.bsdf + 3 * g; atomicAdd(a, v.x); atomicAdd(a + 1, v.y); atomicAdd(a + 2, v.z); }
+                }
+            }
+            if ((TYPES & HAR_SCENE_BLEND) != 0u) {
+                /* a blend vertex: the same two terms for slot 0 of its two nested records, g = dL * ([visible] d Lr_dir / d slot0 + L * (d f / d slot0) / f) with f the
+                 * blended value and L already reduced by this vertex's Lr_dir (ShadeResult::bl_*) */
+                for (int k = 0; k < 2; ++k) {
+                    const bool on = item_pred && R.bl_rec[k] != 0xffffffffu;
+                    Vec3 g = (on && visible) ? R.bl_dir[k] : Vec3(0.f);
+                    if (on) g = g + Vec3(Lr.x * R.bl_rel[k].x, Lr.y * R.bl_rel[k].y, Lr.z * R.bl_rel[k].z);
+                    blend_child_commit(S, grad_slots, grad_tex, on, on ? R.bl_rec[k] : 0u, R.uv_x, R.uv_y, g * dlr);
                 }
             }
             /* write-back: replay -> the survivor's slot of the next bounce (the primal pass's compaction, TapeArrays::next); otherwise the lane's result */
@@ -2154,6 +2185,7 @@ __global__ void k_api_sampler_next(uint32_t n, uint64_t *state, const uint64_t *
 }
 /* BSDF::eval_pdf / eval / pdf (bsdf.h:375-465) of scene BSDF `bsdf` under the caller's BSDFContext; `value` / `pdf` may be NULL (eval / pdf alone: for the
  * models of har_bsdf.h the pair is computed in one pass and BSDF::eval, ::pdf return its halves).  A masked lane evaluates to zero. */
+template <bool BLEND>          /* BLEND: the scene holds `blendbsdf` records (the kernel of other scenes is the code it was before that record existed) */
 __global__ void k_api_bsdf_eval_pdf(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active, float *value, float *pdf) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2161,12 +2193,13 @@ __global__ void k_api_bsdf_eval_pdf(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32
     if (!(active && !active[i])) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx(S, bsdf, side, ctx));
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | (BLEND ? HAR_SCENE_BLEND : 0u), true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<BLEND>(S, bsdf, side, ctx), uv[i], uv[n + i]);
     }
     if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
     if (pdf) pdf[i] = e.pdf;
 }
 /* BSDF::sample (bsdf.h:322-373): BSDFSample3f {wo, pdf, eta, sampled_type, sampled_component} + the weight.  A masked lane returns dr::zeros. */
+template <bool BLEND>
 __global__ void k_api_bsdf_sample(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const uint8_t *active,
                                   float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2175,7 +2208,7 @@ __global__ void k_api_bsdf_sample(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t
     if (!(active && !active[i])) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-        bsdf_sample<HAR_BSDF_ALL_TYPES, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx(S, bsdf, side, ctx));
+        bsdf_sample<HAR_BSDF_ALL_TYPES | (BLEND ? HAR_SCENE_BLEND : 0u), true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<BLEND>(S, bsdf, side, ctx), uv[i], uv[n + i]);
     }
     wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
     weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
@@ -2287,6 +2320,21 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_BLEND) {
+        /* a scene with a `blendbsdf` record: ONE widest instantiation per flavour -- forward, prb primal, the in-place adjoint commit of a cached / taped bounce (the route
+         * every backward pass of such a scene takes: it deposits the nested records' gradients) and the item-writing adjoint that forward mode reads.  plan_chunk keeps the
+         * first-vertex regeneration and the material queues away from these scenes, backward_range the record tape; position and alpha / eta / k gradients are refused. */
+        constexpr uint32_t T = HAR_SCENE_BLEND_TYPES;
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PATH)
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PRB_PRIMAL)
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        return;
+    }
     if (rc.mode == 5) {       /* record tape, primal pass: the adjoint flavour of the shading code, primal bookkeeping, one record per vertex (k_shade<.., RECORD>) */
         const bool env = (S.bsdf_types & HAR_SCENE_ENVMAP) != 0u, diffuse = S.bsdf_types == HAR_BSDF_ONLY_DIFFUSE, cls = (S.bsdf_types & 0x7fffffffu & ~HAR_BSDF_CLASSIC_TYPES) == 0u;
 #define HAR_LAUNCH_SHADE_RECORD(T) do { if (first && tab) hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, false, false, false, true, true, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape); \
@@ -2499,11 +2547,13 @@ void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const u
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {
-    hipLaunchKernelGGL(k_api_bsdf_eval_pdf, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    else hipLaunchKernelGGL(k_api_bsdf_eval_pdf<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
 }
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
-    hipLaunchKernelGGL(k_api_bsdf_sample, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    else hipLaunchKernelGGL(k_api_bsdf_sample<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
 }
 void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
     hipLaunchKernelGGL(k_api_sensor_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, ax, ay, o, d, maxt);

@@ -76,6 +76,10 @@ struct ShadeResult {
      * (-1: none), and the uv its bitmap is looked up at -- si.uv of the hit (area.cpp:83-90), ds.uv of the sample (:139-146).  d em_b / d radiance(uv) = em_unit, d contrib / d
      * radiance(uv) = contrib_unit, as for the colour of a uniform light */
     int32_t lt_hit_emitter, lt_nee_emitter; float lt_hit_uv[2], lt_nee_uv[2];
+    /* ... kernels of scenes with a `blendbsdf` record (HAR_SCENE_BLEND), at a blend vertex: the two nested records (0xffffffff at any other vertex), d Lr_dir / d slot 0 of
+     * each and (d f / d slot 0) / f at the sampled direction -- the factors (1 - w) / w are in them and f is the BLENDED value; bl_ind: the second term exists.  The weight's
+     * own pair rides in dLr_drho / rel_grad (BsdfEval::d_slot0 of a blend vertex is d value / d weight); the in-place commit of k_shade deposits the nested ones */
+    uint32_t bl_rec[2]; Vec3 bl_dir[2], bl_rel[2]; bool bl_ind;
 };
 #define HAR_EXTRA_GROUPS 5
 
@@ -138,6 +142,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     R.alive = false; R.add_emission = false; R.item = false; R.item_ray = false;
     if (MODE == MODE_PRB_ADJOINT && EXTRA) { for (int g = 0; g < 5; ++g) { R.x_dir[g] = Vec3(0.f); R.x_rel[g] = Vec3(0.f); } R.x_ind = false; }
     if (MODE == MODE_PRB_ADJOINT) { R.lt_hit_emitter = -1; R.lt_nee_emitter = -1; R.lt_hit_uv[0] = R.lt_hit_uv[1] = R.lt_nee_uv[0] = R.lt_nee_uv[1] = 0.f; }
+    if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_BLEND) != 0u) { R.bl_rec[0] = R.bl_rec[1] = 0xffffffffu; R.bl_dir[0] = R.bl_dir[1] = R.bl_rel[0] = R.bl_rel[1] = Vec3(0.f); R.bl_ind = false; }
     if (MODE == MODE_PRB_ADJOINT) { R.em_index = -1; R.nee_emitter = -1; R.em_unit = Vec3(0.f); R.contrib_unit = Vec3(0.f); R.nee_flags = 0u; R.cos_em = 0.f; R.nee_p = Vec3(0.f); R.nee_n = Vec3(0.f); R.nee_w = Vec3(0.f); }
     uint64_t rng = st.rng;
     const uint64_t inc = sampler_inc(P.seed, st.lane);
@@ -206,7 +211,10 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
      * every active lane; only BSDFs with a Smooth lobe use them (path.cpp:237, prb.py:169) */
     float ex = 0.f, ey = 0.f;
     /* BSDFFlags::Smooth of the record: a compile-time constant in the kernels of a single-model material queue */
-    const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR) : bsdf_is_smooth(B);
+    /* a blend record (kernels of blend scenes only): Smooth if one of the nested BSDFs is (the union of their flags, blendbsdf.cpp:99; derived when the record is lowered) */
+    const bool blend = (TYPES & HAR_SCENE_BLEND) != 0u && B.type == BSDF_BLEND;
+    const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR)
+                                               : (blend ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
     DirSample ds; ds.pdf = 0.f; ds.d = Vec3(0.f); ds.p = Vec3(0.f); ds.n = Vec3(0.f); ds.dist = 0.f;
     Vec3 em_weight(0.f); float em_unit = 0.f; uint32_t em_sampled = 0;
@@ -266,9 +274,10 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     /* ---- BSDF (bsdf.cpp:21-31 eval_pdf_sample) */
     float s1 = pcg32_next_float(rng, inc);
     float s2x = pcg32_next_float(rng, inc), s2y = pcg32_next_float(rng, inc);
-    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev);
+    BlendChildGrad cg;          /* blend vertex, prb: d value / d slot 0 of the two nested records (both passes of a backward step: the shadow-ray condition below reads it) */
+    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr);
     BsdfSample bs; bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
-    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs);
+    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y);
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
     R.contrib = Vec3(0.f); R.dLr_drho = Vec3(0.f); R.dLr_drho_unit = Vec3(0.f); R.rho = bin.slot0;
@@ -283,6 +292,8 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 /* em_weight = radiance * em_unit for `area` / `constant` emitters (prb.py:198-206, attached eval_emitter_direction) */
                 R.nee_emitter = ((P.flags & HAR_SHADE_EMITTER_GRADS) && S.emitters[em_sampled].type != 2u && S.emitters[em_sampled].type != 7u) ? (int32_t) em_sampled : -1;
                 R.contrib_unit = ((st.throughput * mis_em) * ev.value) * em_unit;
+                if ((TYPES & HAR_SCENE_BLEND) != 0u && blend)
+                    for (int k = 0; k < 2; ++k) R.bl_dir[k] = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
                 if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
                     BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok, wo_em, x);
                     const Vec3 w = (st.throughput * mis_em) * em_weight;
@@ -298,6 +309,11 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
         if (MODE != MODE_PATH) {
             const Vec3 d0 = ((st.throughput * mis_em) * ev.d_slot0) * em_weight;
             grad_item = d0.x != 0.f || d0.y != 0.f || d0.z != 0.f;
+            if ((TYPES & HAR_SCENE_BLEND) != 0u && blend)          /* ... or the nested records' colours have one (two equal nested values: d / d weight = 0) */
+                for (int k = 0; k < 2; ++k) {
+                    const Vec3 dk = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
+                    grad_item = grad_item || dk.x != 0.f || dk.y != 0.f || dk.z != 0.f;
+                }
             if ((P.flags & HAR_SHADE_EMITTER_GRADS) || ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && lt_sampled)) {
                 const Vec3 cu = ((st.throughput * mis_em) * ev.value) * em_unit;
                 grad_item = grad_item || cu.x != 0.f || cu.y != 0.f || cu.z != 0.f;
@@ -352,7 +368,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT) {
         /* Lr_ind = L * relative_grad(bsdf.eval(si, wo, active_next)) (prb.py:288-297): d/d slot0 = L * (df/dslot0) / f */
         Vec3 wo = si.to_local(wo_world);
-        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2);
+        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2, BsdfCtx(), si.uv_x, si.uv_y, (TYPES & HAR_SCENE_BLEND) != 0u ? &cg : nullptr);
         R.rel_grad = Vec3(e2.value.x != 0.f ? e2.d_slot0.x / e2.value.x : 0.f, e2.value.y != 0.f ? e2.d_slot0.y / e2.value.y : 0.f,
                           e2.value.z != 0.f ? e2.d_slot0.z / e2.value.z : 0.f);
         R.ind_active = alive && (R.rel_grad.x != 0.f || R.rel_grad.y != 0.f || R.rel_grad.z != 0.f);
@@ -367,6 +383,14 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
             }
         }
         R.item = R.item_ray || R.ind_active || (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE && R.x_ind);   /* otherwise the vertex has a zero gradient */
+        if ((TYPES & HAR_SCENE_BLEND) != 0u && blend) {
+            R.bl_rec[0] = (uint32_t) B.table; R.bl_rec[1] = B.pad;
+            for (int k = 0; k < 2; ++k) {
+                R.bl_rel[k] = Vec3(e2.value.x != 0.f ? cg.d[k].x / e2.value.x : 0.f, e2.value.y != 0.f ? cg.d[k].y / e2.value.y : 0.f, e2.value.z != 0.f ? cg.d[k].z / e2.value.z : 0.f);
+                R.bl_ind = R.bl_ind || (alive && (R.bl_rel[k].x != 0.f || R.bl_rel[k].y != 0.f || R.bl_rel[k].z != 0.f));
+            }
+            R.item = R.item || R.bl_ind;
+        }
     }
 }
 

@@ -63,7 +63,7 @@ struct BoundScene {
         S.n_emitters = (uint32_t) hs.emitters.size(); S.n_meshes = (uint32_t) hs.meshes.size();
         S.n_bsdfs = (uint32_t) hs.bsdfs.size(); S.n_insts = (uint32_t) hs.insts.size(); S.n_textures = (uint32_t) hs.textures.size();
         S.env_emitter = hs.env_emitter;
-        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
         hs.bind_tables(S, hs.emitter_distr.data());
         if (hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) S.bsdf_types |= HAR_SCENE_ENVMAP;
@@ -104,7 +104,7 @@ std::vector<Block> spiral(uint32_t w, uint32_t h, uint32_t off_x, uint32_t off_y
 }
 
 /* PathIntegrator::sample, scalar variant, on the host-compiled path code: radiance + valid_ray */
-Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o, Vec3 d, float maxt, bool &valid_ray, int &status, uint32_t lane = 0u) {
+Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o, Vec3 d, float maxt, bool &valid_ray, int &status, uint32_t lane = 0u, HarStats *stats = nullptr) {
     Vec3 result(0.f);
     valid_ray = S.env_emitter >= 0;                               /* path.cpp:114-115 (hide_emitters is refused by the caller) */
     if (P.max_depth == 0) return result;                          /* path.cpp:102-103 */
@@ -113,13 +113,15 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
     for (;;) {
         Hit hit; ScalarStack stack;
         accel_trace<false>(S.accel, st.o, st.d, st.maxt, hit, stack, status);
+        if (stats) { stats->vertices++; stats->closest_rays++; }   /* one loop iteration of PathIntegrator::sample: what the wavefront's bounce counters add up to */
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
-        shade_lane<MODE_PATH, HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT>(S, P, st, hit, R);
+        shade_lane<MODE_PATH, HAR_SCENE_BLEND_TYPES>(S, P, st, hit, R);
         valid_ray = valid_ray || hit.t != HAR_INF;                /* path.cpp:307-308 */
         if (R.add_emission) result = Vec3(fma_(R.em_a.x, R.em_b.x, result.x), fma_(R.em_a.y, R.em_b.y, result.y), fma_(R.em_a.z, R.em_b.z, result.z));
         if (R.item && R.item_ray) {                                /* the emitter sample's shadow ray (path.cpp:271-281; ray_test inside sample_emitter_direction) */
             Hit h2; ScalarStack s2;
+            if (stats) stats->shadow_rays++;
             if (!accel_trace<true>(S.accel, R.sh_o, R.sh_d, R.sh_maxt, h2, s2, status)) result = result + R.contrib;
         }
         if (!R.alive) { rng = R.next.rng; break; }
@@ -287,12 +289,78 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
             const bool act = !(active && !active[i]);
             Hit hit; hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
             if (act) { ScalarStack stack; accel_trace<false>(S.accel, O, D, maxt[i], hit, stack, status); }
-            aov_lane(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            aov_lane<true>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
         }
         if (status) return har_set_error("har_aov_sample_host: traversal stack overflow");
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_aov_sample_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_aov_sample_host: ") + ex.what()); }
+}
+
+/* BSDF::eval_pdf / BSDF::sample of record `bsdf` of a scene on the host: the functions k_api_bsdf_eval_pdf / k_api_bsdf_sample run per lane (bsdf_side, bsdf_inputs,
+ * bsdf_eval_pdf / bsdf_sample with the caller's context, the blend-carrying instantiation).  The twins of har_bsdf_eval_pdf / har_bsdf_sample: `value` / `pdf` may be
+ * NULL, a masked lane returns zeros.  wi, wo, value, weight: 3 x n; uv, sample2: 2 x n. */
+static bool lower_ctx_host(const HarBSDFContext *ctx, BsdfCtx &out) {
+    out = BsdfCtx();
+    if (!ctx) return true;
+    if (ctx->mode > 1u) return false;
+    out.mode = ctx->mode; out.type_mask = ctx->type_mask; out.component = ctx->component;
+    return true;
+}
+extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo,
+                                      const uint8_t *active, float *value, float *pdf) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
+        if (n == 0) return 0;
+        if (!wi || !uv || !wo) return har_set_error("null input arrays");
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            BsdfEval ev; ev.value = Vec3(0.f); ev.pdf = 0.f;
+            if (!(active && !active[i])) {
+                BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+                TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_BLEND, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+            }
+            if (value) { value[i] = ev.value.x; value[n + i] = ev.value.y; value[2 * (size_t) n + i] = ev.value.z; }
+            if (pdf) pdf[i] = ev.pdf;
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_eval_pdf_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_eval_pdf_host: ") + ex.what()); }
+}
+extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
+                                    const float *sample2, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
+        if (n == 0) return 0;
+        if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return har_set_error("null input / output arrays");
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
+            if (!(active && !active[i])) {
+                BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+                TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_BLEND, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+            }
+            wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
+            weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
+            if (eta) eta[i] = b.eta;
+            if (sampled_type) sampled_type[i] = b.type;
+            if (sampled_component) sampled_component[i] = b.comp;
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_sample_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_host: ") + ex.what()); }
 }
 
 /* BatchSensor::sample_ray (src/sensors/batch.cpp:132-159) on the host: batch_sample_ray (har_scene.h) -- the function k_raygen_batch runs per lane -- over the children
@@ -342,8 +410,8 @@ extern "C" int har_sensor_sample_ray_aperture_host(const HarSensor *sensor, uint
 /* The forward `path` render of hip_ad_rgb on the host, lane by lane and serially: raygen_lane, the closest-hit traversal and shade_lane<MODE_PATH> with the JIT variants'
  * draws (every lane of the wavefront draws its emitter samples), the splat of ImageBlock::put's coalesced branch (film_footprint).  A test instrument for small films: it
  * runs the functions the kernels run, in the order the wavefront runs them per lane, without a GPU.  `film`: H x W x 4 of the crop window, accumulated into. */
-extern "C" int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
-                                     int32_t max_depth, int32_t rr_depth, float *film) {
+extern "C" int har_render_lanes_stats_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
+                                           int32_t max_depth, int32_t rr_depth, float *film, HarStats *stats) {
     try {
         if (!desc || !sensor || !film) return har_set_error("null argument");
         if (spp == 0) return har_set_error("spp must be > 0");
@@ -365,11 +433,12 @@ extern "C" int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *
         uint32_t log_spp = 0xffffffffu; for (uint32_t k = 0; k < 32; ++k) if ((1u << k) == spp) log_spp = k;
         ShadeParams P{ seed, (uint32_t) max_depth, (uint32_t) rr_depth, 0u };
         int status = 0;
+        HarStats count{}; count.paths = total;
         for (uint32_t lane = 0; lane < (uint32_t) total; ++lane) {
             LaneSample ls;
             const PathState st = raygen_lane<true>(C, seed, spp, log_spp, lane, ls, nullptr, nullptr, n_children ? &T : nullptr);
             uint64_t rng = st.rng; bool valid = false;
-            const Vec3 rgb = sample_scalar(B.ds, P, rng, st.o, st.d, st.maxt, valid, status, lane);
+            const Vec3 rgb = sample_scalar(B.ds, P, rng, st.o, st.d, st.maxt, valid, status, lane, &count);
             const float v[4] = { rgb.x, rgb.y, rgb.z, 1.f };
             Footprint F; film_footprint(C, ls, F);
             for (uint32_t ys = 0; ys < F.count; ++ys)
@@ -382,9 +451,14 @@ extern "C" int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *
                 }
         }
         if (status) return har_set_error("host render: traversal stack overflow");
+        if (stats) { stats->paths += count.paths; stats->vertices += count.vertices; stats->closest_rays += count.closest_rays; stats->shadow_rays += count.shadow_rays; }
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_render_lanes_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_render_lanes_host: ") + ex.what()); }
+}
+extern "C" int har_render_lanes_host(const HarSceneDesc *desc, const HarSensor *sensor, const HarSensor *children, uint32_t n_children, uint32_t seed, uint32_t spp,
+                                     int32_t max_depth, int32_t rr_depth, float *film) {
+    return har_render_lanes_stats_host(desc, sensor, children, n_children, seed, spp, max_depth, rr_depth, film, nullptr);
 }
 
 /* raygen_lane on the host over a lane range: the rays, film positions and sampler states the ray generation kernels produce (k_raygen for pinhole cameras,

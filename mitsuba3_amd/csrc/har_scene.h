@@ -356,7 +356,7 @@ HAR_HD BsdfInputs bsdf_inputs(const DScene &S, const DBsdf &B, float u, float v,
     BsdfInputs in;
     in.slot0 = bsdf_reflectance(S, B, u, v, taps);
     in.slot1 = Vec3(B.r2, B.g2, B.b2);
-    in.table = B.table >= 0 ? S.bsdf_tables + B.table : nullptr;
+    in.table = B.table >= 0 ? S.bsdf_tables + B.table : nullptr;      /* (a blend record keeps a record index there: its `table` is never read) */
     return in;
 }
 
@@ -375,17 +375,113 @@ HAR_HD bool bsdf_side(const DScene &S, uint32_t index, Vec3 wi, BsdfSide &side) 
     if (wi.z < 0.f) { side.index = (uint32_t) B.back; side.wi.z = -wi.z; side.wo_sign = -1.f; return true; }
     return false;
 }
+/* BSDF::component_count() of a record: the model's, or for a blend the two nested records' (blendbsdf.cpp:94-97) */
+HAR_HD uint32_t bsdf_record_component_count(const DScene &S, const DBsdf &B) {
+    if (B.type == BSDF_BLEND) return bsdf_component_count(S.bsdfs[B.table].type) + bsdf_component_count(S.bsdfs[B.pad].type);
+    return bsdf_component_count(B.type);
+}
 /* The context a nested BSDF of a `twosided` record sees (twosided.cpp:129-146, 164-180): the front side and a one-BSDF `twosided` get the caller's context as it
  * is; the back side of a two-BSDF pair gets `component - component_count(front)` (uint32 arithmetic, as in the reference) unless the component is "all" */
+template <bool BLEND = false>         /* BLEND: the front record may be a blend (scenes with such a record) */
 HAR_HD BsdfCtx bsdf_side_ctx(const DScene &S, uint32_t index, const BsdfSide &side, BsdfCtx ctx) {
     const DBsdf &B = S.bsdfs[index];
-    if ((B.flags & BF_TWOSIDED) && B.back >= 0 && side.wo_sign < 0.f && ctx.component != 0xffffffffu) ctx.component -= bsdf_component_count(B.type);
+    if ((B.flags & BF_TWOSIDED) && B.back >= 0 && side.wo_sign < 0.f && ctx.component != 0xffffffffu) ctx.component -= BLEND ? bsdf_record_component_count(S, B) : bsdf_component_count(B.type);
     return ctx;
 }
+
+/* ---- BlendBSDF (src/bsdfs/blendbsdf.cpp), record type 6: slot 0 is the weight, DBsdf::table / ::pad name the two nested (leaf, not twosided) records.  Everything it
+ * returns is an affine combination of eval / pdf / sample of the two nested BSDFs, evaluated at the vertex's uv with their own colour inputs.  Only the kernels of scenes
+ * that hold such a record carry this code (TYPES & HAR_SCENE_BLEND); the nested models run with that bit cleared.
+ * eval_weight (:224-226) = clip(weight->eval_1(si), 0, 1); eval_1 of a bitmap (bitmap.cpp:523-541): the channel of a one-channel bitmap (BF_MONO; stored three times, channel
+ * 0 is read), luminance (spectrum.h:439-442) of the interpolated texel of a three-channel one; a constant is stored (w, w, w).  `inside`: the unclipped weight lies strictly
+ * inside (0, 1), where d clip / d weight = 1 (0 outside; the derivative AT 0 and 1 is unpinned, docs/parity.md) */
+HAR_HD float blend_weight(const DBsdf &B, const BsdfInputs &in, bool &inside) {
+    const float raw = (B.texture < 0 || (B.flags & BF_MONO)) ? in.slot0.x : in.slot0.x * 0.212671f + in.slot0.y * 0.715160f + in.slot0.z * 0.072169f;
+    inside = raw > 0.f && raw < 1.f;
+    return fminf(fmaxf(raw, 0.f), 1.f);
+}
+/* d value / d (slot 0 of nested BSDF k), factor included: (1 - w) * d_slot0 of BSDF 0, w * d_slot0 of BSDF 1 (the adjoint files them under the nested records) */
+struct BlendChildGrad { Vec3 d[2]; };
+/* eval / pdf / eval_pdf (:162-222).  e.d_slot0 = d value / d weight = v1 - v0 where the weight is not clipped (with a component selected: +/- the nested value) */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_BLEND;
+    bool inside; const float w = blend_weight(B, in, inside);
+    const uint32_t child[2] = { (uint32_t) B.table, B.pad };
+    if (cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
+    if (CTX && ctx.component != 0xffffffffu) {                   /* :167-175, :185-191, :205-215: one nested BSDF, its value scaled, its pdf as it is */
+        const uint32_t n0 = bsdf_component_count(S.bsdfs[child[0]].type);
+        const bool first = ctx.component < n0;
+        BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
+        const float k = first ? 1.f - w : w;
+        const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, e, ctx2);
+        const Vec3 nv = e.value;
+        if (cg) cg->d[first ? 0 : 1] = e.d_slot0 * k;
+        e.value = nv * k; e.d_slot1 = Vec3(0.f);
+        e.d_slot0 = inside ? (first ? -nv : nv) : Vec3(0.f);
+        return;
+    }
+    Vec3 val[2]; float pdf[2];
+#if defined(__HIP_DEVICE_COMPILE__)
+#pragma unroll 1          /* one copy of the model switch, run twice: two copies side by side cost the shading kernels their registers */
+#endif
+    for (int k = 0; k < 2; ++k) {
+        const DBsdf &N = S.bsdfs[child[k]];
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        BsdfEval ne; bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, ne, ctx);
+        val[k] = ne.value; pdf[k] = ne.pdf;
+        if (cg) cg->d[k] = ne.d_slot0 * (k == 0 ? 1.f - w : w);
+    }
+    e.value = val[0] * (1.f - w) + val[1] * w;                   /* :220-221 */
+    e.pdf = pdf[0] * (1.f - w) + pdf[1] * w;
+    e.d_slot0 = inside ? val[1] - val[0] : Vec3(0.f); e.d_slot1 = Vec3(0.f);
+}
+/* sample (:108-160): sample1 > w takes nested BSDF 0 with (sample1 - w) / (1 - w), otherwise BSDF 1 with sample1 / w; the other one is evaluated at the sampled direction.
+ * eta, sampled_type and sampled_component are the sampled BSDF's own (not offset, as in the reference); delta lobes go through the same arithmetic. */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_BLEND;
+    bool inside; const float w = blend_weight(B, in, inside);
+    const uint32_t child[2] = { (uint32_t) B.table, B.pad };
+    if (CTX && ctx.component != 0xffffffffu) {                   /* :116-126 */
+        const uint32_t n0 = bsdf_component_count(S.bsdfs[child[0]].type);
+        const bool first = ctx.component < n0;
+        BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
+        const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        bsdf_sample_one<LEAF, CTX>(N, nin, wi, s1, s2x, s2y, bs, ctx2);
+        bs.weight = bs.weight * (first ? 1.f - w : w);
+        return;
+    }
+    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
+    const bool m0 = s1 > w, m1 = s1 <= w;
+    if (!m0 && !m1) return;
+    const DBsdf &Ns = S.bsdfs[child[m0 ? 0 : 1]], &No = S.bsdfs[child[m0 ? 1 : 0]];
+    TexTaps taps;
+    const BsdfInputs sin = bsdf_inputs(S, Ns, u, v, taps);
+    bsdf_sample_one<LEAF, CTX>(Ns, sin, wi, m0 ? (s1 - w) / (1.f - w) : s1 / w, s2x, s2y, bs, ctx);
+    const BsdfInputs oin = bsdf_inputs(S, No, u, v, taps);
+    BsdfEval eo; bsdf_eval_pdf_one<LEAF, CTX>(No, oin, wi, bs.wo, eo, ctx);
+    /* :138-141 / :150-153: weight is nested BSDF 1's share in both branches */
+    const float pdf_weighted = m0 ? w * eo.pdf + (1.f - w) * bs.pdf : w * bs.pdf + (1.f - w) * eo.pdf;
+    const Vec3 sum = m0 ? eo.value * w + (bs.weight * (1.f - w)) * bs.pdf : (bs.weight * w) * bs.pdf + eo.value * (1.f - w);
+    bs.weight = sum * (pdf_weighted > 0.f ? rcp_(pdf_weighted) : 0.f);
+    bs.pdf = pdf_weighted;
+}
+
+/* (u, v): the vertex's texture coordinates -- read only by the kernels of blend scenes, whose nested records look up their own colour inputs there */
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
-HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx()) {
-    if (!side_ok) { e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f); return; }
-    bsdf_eval_pdf_one<TYPES, CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
+HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx(), float u = 0.f, float v = 0.f,
+                          BlendChildGrad *cg = nullptr) {
+    if (!side_ok) { e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f); if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); } return; }
+    if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) {
+        blend_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        return;
+    }
+    if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
+    bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_BLEND), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
 }
 /* d value / d {alpha, eta, k} of the record serving this side (see bsdf_eval_extra_one) */
 HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEvalExtra &x) {
@@ -393,9 +489,11 @@ HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInp
     bsdf_eval_extra_one(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), x);
 }
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
-HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx = BsdfCtx()) {
+HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx = BsdfCtx(),
+                        float u = 0.f, float v = 0.f) {
     if (!side_ok) { bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u; return; }
-    bsdf_sample_one<TYPES, CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
+    if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
+    else bsdf_sample_one<(TYPES & ~HAR_SCENE_BLEND), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
     bs.wo.z *= side.wo_sign;
 }
 

@@ -204,6 +204,7 @@ void quad_gauss_legendre(int n, std::vector<float> &nodes, std::vector<float> &w
 bool scene_set_bsdf_params_host(HostScene &hs, uint32_t index, const HarBSDF &in, std::string &err) {
     if (index >= hs.bsdfs.size()) { err = "invalid bsdf index"; return false; }
     DBsdf &b = hs.bsdfs[index];
+    if (b.type == BSDF_BLEND) { err = "blendbsdf: the record has no parameter besides its weight (slot 0)"; return false; }
     for (float v : { in.alpha_u, in.alpha_v, in.eta, in.eta_c[0], in.eta_c[1], in.eta_c[2], in.k_c[0], in.k_c[1], in.k_c[2], in.reflectance2[0], in.reflectance2[1], in.reflectance2[2] })
         if (!std::isfinite(v)) { err = "BSDF parameter is not finite"; return false; }
     const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
@@ -338,7 +339,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.bsdf_count; ++i) {
         const HarBSDF &b = d.bsdfs[i];
-        if (b.type >= BSDF_TYPE_COUNT) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic and twosided are implemented in hip_ad_rgb)"; return false; }
+        if (b.type > BSDF_BLEND) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf and twosided are implemented in hip_ad_rgb)"; return false; }
         if (b.texture >= (int32_t) d.texture_count) { err = "BSDF references a texture that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
@@ -350,6 +351,18 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
         db.alpha_u = b.alpha_u; db.alpha_v = b.alpha_v; db.eta = b.eta;
         for (int k = 0; k < 3; ++k) { db.eta_c[k] = b.eta_c[k]; db.k_c[k] = b.k_c[k]; }
         db.back = (b.flags & BF_TWOSIDED) ? b.back : -1; db.table = -1;
+        if (b.type == BSDF_BLEND) {                         /* BlendBSDF (blendbsdf.cpp:80-100): two nested records, named by index; `table` / `pad` are free in such a record */
+            db.flags &= BF_TWOSIDED | BF_MONO;
+            for (int k = 0; k < 2; ++k)
+                if (b.nested[k] < 0 || b.nested[k] >= (int32_t) d.bsdf_count) { err = "blendbsdf: a nested BSDF index is out of range"; return false; }
+            for (int k = 0; k < 2; ++k) {
+                const HarBSDF &c = d.bsdfs[b.nested[k]];
+                if (c.type >= BSDF_TYPE_COUNT || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
+                if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
+                if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_BLEND_SMOOTH;
+            }
+            db.table = b.nested[0]; db.pad = (uint32_t) b.nested[1];
+        } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH);
         hs.bsdfs.push_back(db);
         if (b.type == BSDF_ROUGHPLASTIC) { build_roughplastic_tables(hs, i); update_roughplastic_sampling_weight(hs, i); }
         if (b.type == BSDF_PLASTIC) {                       /* SmoothPlastic::parameters_changed (plastic.cpp:188-205) */
@@ -358,6 +371,13 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             p.internal_reflectance = fresnel_diffuse_reflectance(1.f / p.eta);
             update_roughplastic_sampling_weight(hs, i);
         }
+    }
+    /* a `twosided` whose back side is a blend: that record's nested BSDFs must not transmit either */
+    for (uint32_t i = 0; i < d.bsdf_count; ++i) {
+        const HarBSDF &b = d.bsdfs[i];
+        if (!(b.flags & BF_TWOSIDED) || b.back < 0 || d.bsdfs[b.back].type != BSDF_BLEND) continue;
+        for (int k = 0; k < 2; ++k)
+            if (d.bsdfs[d.bsdfs[b.back].nested[k]].type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }
     }
     for (uint32_t i = 0; i < d.emitter_count; ++i) {
         const HarEmitter &e = d.emitters[i];
