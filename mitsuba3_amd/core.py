@@ -2617,6 +2617,7 @@ class Scene:
             # sampling record are re-baked from it -- what '<rect>.to_world' reads back
             self._set_rect_to_world(mesh, self._rect_frame(mesh, p))
             return
+        held = np.array(V, np.float32)        # a refused update (below) leaves the mirror as it was: the next scene handle is built from it
         V[:, :3] = p
         if self.meshes[mesh]["flags"] & 1:
             # Mesh::parameters_changed (mesh.cpp:876-878): pack(regenerate_normals = positions written and normals not) -> compute_normals (:1216-1267)
@@ -2630,7 +2631,13 @@ class Scene:
             # fresh build traces faster -- the next render creates it)
             Vc = np.ascontiguousarray(self.meshes[mesh]["V"], np.float32)
             getattr(self, "_stale_meshes", set()).discard(mesh)
-            self._after_vertex_update(mesh, lib().har_scene_update_vertices(self._h, int(mesh), _fp(Vc), _stream()))
+            try:
+                self._after_vertex_update(mesh, lib().har_scene_update_vertices(self._h, int(mesh), _fp(Vc), _stream()))
+            except RuntimeError:
+                # e.g. an instance level that no longer fits the traversal stacks: the handle is gone, and the scene goes on with the positions it held -- as after a
+                # refused device-resident update, whose mirror was never written
+                self.meshes[mesh]["V"] = held
+                raise
 
     def _after_vertex_update(self, mesh, rc):
         """return codes of har_scene_update_vertices(_device): 2 / 3 = valid scene, but the next render needs / is better off with a new handle; anything else but 0 is an

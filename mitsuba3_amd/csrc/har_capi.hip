@@ -152,6 +152,13 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
         I->result2 = nullptr; overlap = false; (void) hipGetLastError();      /* no room for the second item set: one stream (an optimisation, not a requirement) */
     }
     if (overlap) HIP_TRY(hipMemsetAsync(I->result2, 0, (size_t) n * sizeof(float4), s));
+    /* `path` on one stream adds an emitter sample as path.cpp:279 does, with one rounding (HAR_SHADE_FUSED_NEE): k_resolve reads the throughput from the bounce's input
+     * wavefront, which stands until the NEXT bounce is shaded (the ping-pong pair) -- later than every resolve launch below but the overlapped one, whose shadow rays
+     * run next to that shading launch and whose sums reach `result` in another order anyway (result2).  Not bounce 0 of FIRST VERTEX (no stored state; the throughput is 1).
+     * Only for caller-supplied rays (Integrator::sample), whose per-lane radiance the caller sees and can hold against the reference bit by bit; a film is a sum of
+     * atomics in no fixed order, and there the extra 16-byte read per unoccluded shadow ray cost 1.5 % of the headline frame (1125 against 1142 Mpaths/s on an MI355X) */
+    const bool fused_nee = mode == MODE_PATH && rays && !overlap;
+    if (fused_nee) P.flags |= HAR_SHADE_FUSED_NEE;
     hipEvent_t ev_res[2] = { I->ev_resolved, I->ev_resolved2 };
     bool resolve_pending[2] = { false, false };
     int cur = 0; uint32_t b = 0;
@@ -211,6 +218,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
                      items_b, cnt_items(I, b), I->result, rc, ps.rng, I->dL, grad_refl, shape ? &I->geo : nullptr, inline_commit && cached ? I->d_grad_tex : nullptr,
                      queued ? &I->tq : nullptr, (inline_commit && cached) ? I->set.grad_bsdf_params : nullptr, nullptr, 0, (tape || rec_w) ? &tp : nullptr);
         prof_mark(I, s, CLS_SHADE);
+        const float4 *const beta = (fused_nee && !(b == 0 && first_regen)) ? st_in.a2 : nullptr;
         if (queued) { texel_queues_accumulate(I, n, s); prof_mark(I, s, CLS_OTHER); }
         if (overlap) {
             HIP_TRY(hipEventRecord(I->ev_shaded, s));
@@ -221,7 +229,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
         } else if (late_on && b >= late_from && b + 1 < nb) {
             HIP_TRY(hipEventRecord(I->ev_shaded, s));
             HIP_TRY(hipStreamWaitEvent(I->aux_stream, I->ev_shaded, 0));
-            launch_resolve(mode, I->aux_stream, tgrid, spill, S->ds, cnt_items(I, b), cur_resolve(I, b), I->shard_cap, I->items, I->result, I->dL, grad_refl, I->d_grad_tex, I->status, rc, nullptr, 0);
+            launch_resolve(mode, I->aux_stream, tgrid, spill, S->ds, cnt_items(I, b), cur_resolve(I, b), I->shard_cap, I->items, I->result, I->dL, grad_refl, I->d_grad_tex, I->status, rc, nullptr, 0, nullptr, beta);
             HIP_TRY(hipEventRecord(I->ev_resolved, I->aux_stream));
             late_pending = true;
         } else if (!(inline_commit && cached)) {
@@ -229,7 +237,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
             const bool item_queued = mode == MODE_PRB_ADJOINT && rc.mode == CACHE_READ && !fwd && I->tq.nq != 0;
             if (item_queued && texel_queues_begin(I, s)) return 1;
             launch_resolve(mode, s, rc.mode == CACHE_READ ? grid : tgrid, spill, S->ds, cnt_items(I, b), cur_resolve(I, b), I->shard_cap, I->items, I->result, I->dL, grad_refl, I->d_grad_tex, I->status, rc,
-                           shape ? I->geo.vis : nullptr, fwd ? 1 : 0, item_queued ? &I->tq : nullptr);
+                           shape ? I->geo.vis : nullptr, fwd ? 1 : 0, item_queued ? &I->tq : nullptr, beta);
             if (item_queued) texel_queues_accumulate(I, n, s);
         }
         prof_mark(I, s, CLS_RESOLVE);

@@ -1439,7 +1439,9 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                 const Vec3 c = fact ? R.contrib_unit : R.contrib;
                 const uint32_t tag = (R.bsdf & 0xfffffu) | ((fact ? (uint32_t) R.nee_emitter : HAR_ITEM_NO_EMITTER) << 20) | (R.ind_active ? 0x80000000u : 0u);
                 items.s2[islot] = make_float4(c.x, c.y, c.z, __uint_as_float(tag));
-            } else items.s2[islot] = make_float4(R.contrib.x, R.contrib.y, R.contrib.z, __uint_as_float(((HAR_RESOLVE_ATOMIC || HAR_RESOLVE_LANE_S2) && (rc.mode == 0 || rc.mode == 1)) ? lane : i));
+            } else if (MODE == MODE_PATH && (P.flags & HAR_SHADE_FUSED_NEE))      /* the factor next to the throughput, which k_resolve reads from slot i of this bounce's input wavefront */
+                items.s2[islot] = make_float4(R.contrib_b.x, R.contrib_b.y, R.contrib_b.z, __uint_as_float(i));
+            else items.s2[islot] = make_float4(R.contrib.x, R.contrib.y, R.contrib.z, __uint_as_float(((HAR_RESOLVE_ATOMIC || HAR_RESOLVE_LANE_S2) && (rc.mode == 0 || rc.mode == 1)) ? lane : i));
             /* .w: the vertex slot in tape modes (where k_resolve files the visibility); otherwise the LANE again (HAR_RESOLVE_ATOMIC), so that k_resolve's commit reads
              * the contribution and its destination with ONE 16-byte load */
             if (MODE == MODE_PRB_ADJOINT && !RECORD) {
@@ -1669,7 +1671,7 @@ __global__ __launch_bounds__(kBlock) void k_resolve_adjoint_cached(DScene S, con
 template <int MODE, bool SPILL, bool FWD = false, bool FLAT = false>
 __global__ __launch_bounds__(kBlock, (MODE == MODE_PRB_ADJOINT ? 1 : HAR_TRACE_MIN_WAVES)) void k_resolve(    /* the adjoint flavour keeps gradient accumulators in LDS: 5 blocks per CU */
                                                     DScene S, const uint32_t *item_count, uint32_t *cursor, uint32_t shard_cap, ItemArrays items, float4 *result,
-                                                    const float4 *dL, float *grad_refl, float *const *grad_tex, int *status, ReplayCache rc, uint2 *spill, uint8_t *item_vis) {
+                                                    const float4 *dL, float *grad_refl, float *const *grad_tex, int *status, ReplayCache rc, uint2 *spill, uint8_t *item_vis, const float4 *beta) {
     __shared__ uint2 lds[HAR_LDS_STACK_SMALL * kBlock];
     /* adjoint: per-block accumulators of the constant-albedo gradients.  Every path of the chip adds to the same
      * few floats of grad_refl (one 64 B line): direct global atomics serialise at ~88 atomics/us per line, which
@@ -1696,7 +1698,14 @@ __global__ __launch_bounds__(kBlock, (MODE == MODE_PRB_ADJOINT ? 1 : HAR_TRACE_M
             const uint32_t i = base + idx;
             if (rc.mode == 1) rc.vis[__float_as_uint(items.s1[i].w)] = T.found ? 0 : 1;      /* replay cache: per lane */
             else if (rc.mode == 3 || rc.mode == 5) rc.vis[__float_as_uint(items.s2[i].w)] = T.found ? 0 : 1; /* replay / record tape: per vertex slot */
-            if (!T.found) {
+            if (!T.found && beta) {
+                /* HAR_SHADE_FUSED_NEE: the item holds the factor next to the throughput, and the throughput is still where the shading kernel read it (slot s2.w of the
+                 * bounce's input wavefront, which nobody writes before the next bounce is shaded) -- the term is added with the one rounding of path.cpp:279 */
+                const float4 s2 = items.s2[i], t = beta[__float_as_uint(s2.w)];
+                const uint32_t lane = __float_as_uint(items.s1[i].w);
+                const float4 r = result[lane];
+                result[lane] = make_float4(fma_(t.x, s2.x, r.x), fma_(t.y, s2.y, r.y), fma_(t.z, s2.z, r.z), 0.f);
+            } else if (!T.found) {
 #if HAR_RESOLVE_ATOMIC
                 /* one item per lane and bounce: the add has a single writer, so a no-return atomic gives the bits of load + add + store -- without the load's round
                  * trip in the middle of the wave's refill (the commit used to be a chain of THREE dependent loads: s1.w -> result[lane], s2) and without reading
@@ -2444,7 +2453,7 @@ void launch_texel_accumulate(hipStream_t s, const TexelQueues &tq, float *const 
     hipLaunchKernelGGL(k_texel_accumulate<false>, dim3(HAR_SHARDS * tq.nq * bpq), dim3(kBlock), lds_bytes, s, tq, grad_tex, bpq, spread, fixed ? 0u : 1u);
 }
 void launch_resolve(int mode, hipStream_t s, uint32_t grid, uint2 *spill, const DScene &S, const uint32_t *item_count, uint32_t *cursor, uint32_t shard_cap, const ItemArrays &items,
-                    float4 *result, const float4 *dL, float *grad_refl, float *const *grad_tex, int *status, const ReplayCache &rc, uint8_t *item_vis, int fwd, const TexelQueues *tq) {
+                    float4 *result, const float4 *dL, float *grad_refl, float *const *grad_tex, int *status, const ReplayCache &rc, uint8_t *item_vis, int fwd, const TexelQueues *tq, const float4 *beta) {
     dim3 g(grid), b(kBlock);
     if (mode == MODE_PRB_ADJOINT && rc.mode == 2) {
         const TexelQueues no_tq{ nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr };
@@ -2452,9 +2461,10 @@ void launch_resolve(int mode, hipStream_t s, uint32_t grid, uint2 *spill, const 
         else hipLaunchKernelGGL(k_resolve_adjoint_cached<false>, g, b, 0, s, S, item_count, shard_cap, items, result, dL, grad_refl, grad_tex, rc, item_vis, tq ? *tq : no_tq);
         return;
     }
-#define HAR_LAUNCH_RESOLVE(M, SP, FL) hipLaunchKernelGGL((k_resolve<M, SP, false, FL>), g, b, 0, s, S, item_count, cursor, shard_cap, items, result, dL, grad_refl, grad_tex, status, rc, spill, item_vis)
-#define HAR_LAUNCH_RESOLVE_FWD(SP) hipLaunchKernelGGL((k_resolve<MODE_PRB_ADJOINT, SP, true>), g, b, 0, s, S, item_count, cursor, shard_cap, items, result, dL, grad_refl, grad_tex, status, rc, spill, item_vis)
+#define HAR_LAUNCH_RESOLVE(M, SP, FL) hipLaunchKernelGGL((k_resolve<M, SP, false, FL>), g, b, 0, s, S, item_count, cursor, shard_cap, items, result, dL, grad_refl, grad_tex, status, rc, spill, item_vis, beta)
+#define HAR_LAUNCH_RESOLVE_FWD(SP) hipLaunchKernelGGL((k_resolve<MODE_PRB_ADJOINT, SP, true>), g, b, 0, s, S, item_count, cursor, shard_cap, items, result, dL, grad_refl, grad_tex, status, rc, spill, item_vis, nullptr)
     const bool flat = !spill && !S.accel.has_tlas && flat_kernels();
+    if (mode != MODE_PATH) beta = nullptr;            /* the primal pass of prb runs the MODE_PATH instantiation: its items hold Lr_dir, added as it is (prb.py:216) */
     if (mode == MODE_PRB_ADJOINT && fwd) { if (spill) HAR_LAUNCH_RESOLVE_FWD(true); else HAR_LAUNCH_RESOLVE_FWD(false); }
     else if (mode == MODE_PRB_ADJOINT) { if (spill) HAR_LAUNCH_RESOLVE(MODE_PRB_ADJOINT, true, false); else if (flat) HAR_LAUNCH_RESOLVE(MODE_PRB_ADJOINT, false, true); else HAR_LAUNCH_RESOLVE(MODE_PRB_ADJOINT, false, false); }
     else { if (spill) HAR_LAUNCH_RESOLVE(MODE_PATH, true, false); else if (flat) HAR_LAUNCH_RESOLVE(MODE_PATH, false, true); else HAR_LAUNCH_RESOLVE(MODE_PATH, false, false); }

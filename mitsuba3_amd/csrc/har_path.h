@@ -46,6 +46,8 @@ struct ShadeParams {
 #define HAR_SHADE_SCALAR_DRAWS 8u    /* scalar variants: the two emitter samples are only drawn where the BSDF has a smooth lobe (path.cpp:244-249); JIT variants draw them on every lane */
 #define HAR_SHADE_LIGHT_TEXELS 64u    /* adjoint: also differentiate w.r.t. the texels of bitmap `radiance` textures of area lights (ShadeResult::lt_*; committed in place by the re-shading replay) */
 #define HAR_SHADE_HIDE_EMITTERS 2u   /* Integrator property `hide_emitters`: the environment is not seen by camera rays (path.cpp:114-115, prb.py:146-148) */
+#define HAR_SHADE_FUSED_NEE 128u     /* `path` on caller-supplied rays (Integrator::sample): the shadow-ray item carries ShadeResult::contrib_b and k_resolve adds it as path.cpp:279 does, result = fmadd(throughput, contrib_b, result),
+                                      * with the throughput it reads back from the bounce's input wavefront (run_chunk) */
 #define HAR_ITEM_NO_EMITTER 0x7ffu   /* emitter field of an adjoint item's tag: contribution stored as is (no emitter gradient) */
 
 struct ShadeResult {
@@ -56,6 +58,7 @@ struct ShadeResult {
     bool item_ray;                        /* item carries a shadow ray to test */
     Vec3 sh_o, sh_d; float sh_maxt;
     Vec3 contrib;                         /* PATH: throughput*bsdf*em*mis; PRB: Lr_dir */
+    Vec3 contrib_b;                       /* PATH: bsdf*em*mis -- path.cpp:279 adds the term with ONE rounding, result = fmadd(throughput, contrib_b, result) */
     /* MODE_PRB_ADJOINT only: d Lr_dir / d slot0, and (d f / d slot0) / f at the sampled direction */
     Vec3 dLr_drho, rel_grad; bool ind_active; uint32_t bsdf; float uv_x, uv_y;
     /* ... for the COMPACT record of diffuse-only scenes (HAR_TAPE_COMPACT, k_shade<.., RECORD> / k_commit<.., COMPACT>): d Lr_dir / d slot0 for a UNIT radiance of
@@ -280,10 +283,10 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y);
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
-    R.contrib = Vec3(0.f); R.dLr_drho = Vec3(0.f); R.dLr_drho_unit = Vec3(0.f); R.rho = bin.slot0;
+    R.contrib = Vec3(0.f); R.contrib_b = Vec3(0.f); R.dLr_drho = Vec3(0.f); R.dLr_drho_unit = Vec3(0.f); R.rho = bin.slot0;
     if (active_em) {
         float mis_em = ((TYPES & HAR_SCENE_ENVMAP) != 0u && em_delta) ? 1.f : mis_weight(ds.pdf, ev.pdf);
-        if (MODE == MODE_PATH) R.contrib = st.throughput * ((ev.value * em_weight) * mis_em);
+        if (MODE == MODE_PATH) { R.contrib_b = (ev.value * em_weight) * mis_em; R.contrib = st.throughput * R.contrib_b; }
         else {
             R.contrib = ((st.throughput * mis_em) * ev.value) * em_weight;
             if (MODE == MODE_PRB_ADJOINT) {

@@ -122,7 +122,7 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         if (R.item && R.item_ray) {                                /* the emitter sample's shadow ray (path.cpp:271-281; ray_test inside sample_emitter_direction) */
             Hit h2; ScalarStack s2;
             if (stats) stats->shadow_rays++;
-            if (!accel_trace<true>(S.accel, R.sh_o, R.sh_d, R.sh_maxt, h2, s2, status)) result = result + R.contrib;
+            if (!accel_trace<true>(S.accel, R.sh_o, R.sh_d, R.sh_maxt, h2, s2, status)) result = fma3(st.throughput, R.contrib_b, result);      /* path.cpp:279 */
         }
         if (!R.alive) { rng = R.next.rng; break; }
         st = R.next;

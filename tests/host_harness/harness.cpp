@@ -359,7 +359,7 @@ int hh_render(void *h, const HarSensor *sensor, int mode, uint32_t seed, uint32_
             if (R.add_emission) result = mode == MODE_PATH ? fma3(R.em_a, R.em_b, result) : result + R.em_b;
             if (R.item && R.item_ray) {
                 Hit sh; HostStack s2;
-                if (!accel_trace<true>(S.accel, R.sh_o, R.sh_d, R.sh_maxt, sh, s2, status)) result = result + R.contrib;
+                if (!accel_trace<true>(S.accel, R.sh_o, R.sh_d, R.sh_maxt, sh, s2, status)) result = mode == MODE_PATH ? fma3(st.throughput, R.contrib_b, result) : result + R.contrib;
             }
             alive = R.alive; st = R.next;
         }
@@ -628,6 +628,7 @@ int hh_trace_stats(void *h, const HarSensor *sensor, uint32_t seed, uint32_t spp
     std::vector<PathState> cur, next; LaneSample ls;
     for (uint64_t lane = lane_begin; lane < lane_end; ++lane) cur.push_back(raygen_lane(C, seed, spp, log_spp, (uint32_t) lane, ls));
     int status = 0;
+    std::vector<Hit> last; uint32_t last_bounce = 0xffffffffu;      /* the occluder-cache what-if below: per call (a film of another size must not index the previous call's array) */
     for (uint32_t b = 0; b < max_bounces && !cur.empty(); ++b) {
         double *o = out + 32 * b;
         struct Sh { Vec3 o, d; float maxt; uint32_t pixel; };
@@ -799,7 +800,6 @@ int hh_trace_stats(void *h, const HarSensor *sensor, uint32_t seed, uint32_t spp
             /* occluder-cache what-if: is the occluder of this ray the one that occluded the pixel's previous occluded shadow ray of this bounce?
              * slot 29: same instance (upper bound of a cache's hit rate), slot 30: same triangle (lower bound) */
             if (f1) {
-                static std::vector<Hit> last; static uint32_t last_bounce = 0xffffffffu;
                 if (last_bounce != b) { last.assign((size_t) C.samp_w * C.samp_h, Hit{ HAR_INF, 0.f, 0.f, 0u, 0u, 0u }); last_bounce = b; }
                 Hit occ; { HostStack s3; int st3 = 0; accel_trace<false>(S.accel, shadow[i].o, shadow[i].d, shadow[i].maxt, occ, s3, st3); }      /* any-hit reports no identity: take the nearest occluder */
                 hh = occ;
