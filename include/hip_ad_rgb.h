@@ -61,12 +61,18 @@ typedef struct HarInstance {
  *   type 4 conductor       (src/bsdfs/conductor.cpp)       slot0 = specular_reflectance, eta_c / k_c (RGB)
  *   type 5 plastic         (src/bsdfs/plastic.cpp)         slot0 = diffuse_reflectance, slot1 = specular_reflectance, eta
  *   type 6 blendbsdf       (src/bsdfs/blendbsdf.cpp)       slot0 = weight: a constant stored as (w, w, w) or a bitmap; `nested` = the two mixed BSDF records
+ *   type 7 mask            (src/bsdfs/mask.cpp)            slot0 = opacity: a constant stored as (o, o, o) or a bitmap; `nested[0]` = the nested BSDF record
  * slot0 may be a bitmap texture (`texture` >= 0), slot1 is constant.
  * A blend record evaluates clip(weight, 0, 1) of Texture::eval_1 -- the constant, channel 0 of a one-channel bitmap (HAR_BSDF_MONO: stored three times), the luminance
  * of a three-channel one -- and returns (1 - w) * nested[0] + w * nested[1] for eval / pdf, samples nested[1] with probability w.  The nested records are leaf models
  * (types 0 - 5) without the twosided flag; HAR_BSDF_TWOSIDED on the blend record itself is supported (no nested dielectric then).  Gradients (`prb`): the weight's is
  * d / d weight in the record's own row / bitmap (zero where the weight is clipped), the nested records' colour slot 0 receive theirs in their own rows / bitmaps; every
  * backward pass of a scene with such a record takes the replay-cache route with the in-place commit (max_depth <= 12, no vertex-position / alpha / eta / k gradients).
+ * A mask record evaluates o = clip(opacity, 0, 1) the same way and returns nested[0] * o for eval / pdf; its sample takes the nested BSDF with probability o and otherwise the
+ * NULL lobe (wo = -wi, weight 1, pdf 1 - o, eta 1, sampled_type 0x1, sampled_component = the nested BSDF's component count).  nested[0] is a leaf record (types 0 - 5) that
+ * MAY carry the twosided flag, with one or two BSDFs; a nested blend / mask, a mask inside a blend and HAR_BSDF_TWOSIDED on the mask record itself are refused.  `path`
+ * counts a camera sample as valid when a non-null lobe was sampled at one of its vertices (path.cpp:307-308).  Gradients (`prb`): the opacity's in the record's own row /
+ * bitmap, the nested leaf record's colour slot 0 in its own; the refusals of a blend scene hold for a scene with a mask record as well.
  * flags: bit0 twosided (src/bsdfs/twosided.cpp; `back` = record used for the back side, -1 = the same one),
  *        bit1 GGX distribution (else Beckmann), bit2 sample_visible, bit3 plastic / roughplastic `nonlinear`. */
 #define HAR_BSDF_DIFFUSE        0
@@ -76,11 +82,12 @@ typedef struct HarInstance {
 #define HAR_BSDF_CONDUCTOR      4
 #define HAR_BSDF_PLASTIC        5
 #define HAR_BSDF_BLEND          6
+#define HAR_BSDF_MASK           7
 #define HAR_BSDF_TWOSIDED       1u
 #define HAR_BSDF_GGX            2u
 #define HAR_BSDF_SAMPLE_VISIBLE 4u
 #define HAR_BSDF_NONLINEAR      8u
-#define HAR_BSDF_MONO           16u     /* blend: the weight bitmap has one channel */
+#define HAR_BSDF_MONO           16u     /* blend / mask: the weight / opacity bitmap has one channel */
 typedef struct HarBSDF {
     uint32_t type;
     int32_t  texture;     /* -1: constant slot0 (srgb), else bitmap index */
@@ -91,7 +98,7 @@ typedef struct HarBSDF {
     float    eta;                     /* int_ior / ext_ior */
     float    eta_c[3], k_c[3];        /* conductor: real and imaginary part of the relative IOR */
     int32_t  back;
-    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs (read for type 6 only) */
+    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask: nested[0] (read for types 6 and 7 only) */
 } HarBSDF;
 
 /* BitmapTexture, raw H x W x 3 f32 (src/textures/bitmap.cpp:175-206). HOST pointer.  mode = filter_type | wrap_mode (bitmap.cpp:182-206):

@@ -442,7 +442,7 @@ def _cube(props):
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
-    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf',
+    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
@@ -997,7 +997,8 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 # BitmapTexture(props) (src/textures/bitmap.cpp:175-260); `raw` only silences a range warning for float data in RGB variants, `accel` picks Dr.Jit's texture
 # hardware path on CUDA (no effect on values), `format` = the storage type of the texels ("auto" / "variant" / "fp16": this path keeps float32)
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
-BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6}
+BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7}
+_WEIGHTED_BSDFS = ('blendbsdf', 'mask')          # records whose slot 0 is a scalar texture (Texture::eval_1): the blend weight, the mask opacity
 _LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
 # (parameter name of slot 0, default), (parameter name of slot 1, default)
 _BSDF_SLOTS = {'diffuse': (('reflectance', 0.5), None), 'dielectric': (('specular_reflectance', 1.0), ('specular_transmittance', 1.0)),
@@ -1067,8 +1068,8 @@ class BSDF:
         props = props or {}
         self.id = id
         self.kind = props.get('type', 'diffuse')
-        if self.kind == 'blendbsdf':
-            raise RuntimeError("blendbsdf: built by the plugin factory (mi.load_dict), which resolves its nested BSDFs")
+        if self.kind in _WEIGHTED_BSDFS:
+            raise RuntimeError("%s: built by the plugin factory (mi.load_dict), which resolves its nested BSDFs" % self.kind)
         if self.kind not in BSDF_TYPES:
             raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb" % self.kind)
         _check_props(self.kind, props, _BSDF_PROPS[self.kind], free_children=False)
@@ -1208,8 +1209,10 @@ class BlendBSDF(BSDF):
     """BlendBSDF (src/bsdfs/blendbsdf.cpp:80-100): a BSDF record whose colour slot 0 is the `weight` (a float, or a raw bitmap of 1 or 3 channels) and which names two nested
     BSDFs; these become records of their own (Scene._add_bsdf)."""
 
+    _plugin = 'blendbsdf'; _weight_name = 'weight'
+
     def __init__(self, weight, nested, id=None):
-        self.id = id; self.kind = 'blendbsdf'; self.slot0_name = 'weight'; self.slot1_name = None
+        self.id = id; self.kind = self._plugin; self.slot0_name = self._weight_name; self.slot1_name = None
         self.texture = None; self.tex_mode = 0; self.tex_to_uv = None; self.weight_channels = 0
         if isinstance(weight, (int, float)) and not isinstance(weight, bool):
             self.value = _f32([float(weight)] * 3)
@@ -1218,17 +1221,17 @@ class BlendBSDF(BSDF):
             src = weight['data'] if 'data' in weight else (weight['bitmap'].data if isinstance(weight.get('bitmap'), Bitmap) else Bitmap(weight['filename']).data)
             ch = 1 if len(tuple(src.shape)) == 2 else int(src.shape[2])
             if ch not in (1, 3):
-                raise RuntimeError("blendbsdf: the `weight` bitmap has %d channels, expected 1 or 3" % ch)
+                raise RuntimeError("%s: the `%s` bitmap has %d channels, expected 1 or 3" % (self._plugin, self._weight_name, ch))
             self.weight_channels = ch
             self.value = _f32([0.5, 0.5, 0.5])
         else:
-            raise RuntimeError("blendbsdf: `weight` is a float or a `bitmap` texture")
+            raise RuntimeError("%s: `%s` is a float or a `bitmap` texture" % (self._plugin, self._weight_name))
         self.value2 = _f32([0, 0, 0]); self.flags = 16 if self.weight_channels == 1 else 0          # (16: slot 0 is a one-channel bitmap, read channel 0)
         self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
         self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
         self.scene = None; self.index = None
         self.nested = list(nested)
-        for k, c in enumerate(self.nested):
+        for k, c in enumerate(self.nested if self._plugin == 'blendbsdf' else ()):
             if getattr(c, 'blend_parent', None) is None and c.scene is None:
                 c.blend_parent = (self, k)        # NAMES its parameters '<blend>.bsdf_<k>.*' (BlendBSDF::traverse, blendbsdf.cpp:102-106); what is refused for a nested record is decided from the scene's records, Scene._blend_nested
 
@@ -1244,6 +1247,43 @@ class BlendBSDF(BSDF):
     @flags.setter
     def flags(self, value):
         self._flags = int(value)
+
+
+class MaskBSDF(BlendBSDF):
+    """MaskBSDF (src/bsdfs/mask.cpp:93-119): a BSDF record whose colour slot 0 is the `opacity` (a float, or a raw bitmap of 1 or 3 channels) and which names ONE nested
+    BSDF -- a plain model, or a `twosided` over one or two of them; it becomes a record of its own (Scene._add_bsdf)."""
+    _plugin = 'mask'; _weight_name = 'opacity'
+
+    def __init__(self, opacity, nested, id=None):
+        BlendBSDF.__init__(self, opacity, [nested], id=id)
+        if getattr(nested, 'mask_parent', None) is None and nested.scene is None:
+            nested.mask_parent = self          # NAMES its parameters '<mask>.nested_bsdf.*' (MaskBSDF::traverse, mask.cpp:116-119): Scene._bsdf_key_base
+
+    def _own_lobes(self):
+        """the nested BSDF's components -- those of its `twosided`, if it is one --, then the null lobe at the last index (mask.cpp:107-113)"""
+        n = self.nested[0]
+        lobes = [n._lobe_flags(i) for i in range(n.component_count())]
+        return lobes + [BSDFFlags.Null | BSDFFlags.FrontSide | BSDFFlags.BackSide]
+
+
+def _mk_mask(props, named, key):
+    """the `mask` plugin: `opacity` (default 0.5) and exactly one nested BSDF under a free name (mask.cpp:93-105)"""
+    _check_props('mask', props, ('opacity',), children=('bsdf',))
+    nested = None
+    for k, v in props.items():
+        if k in ('type', 'id', 'opacity'):
+            continue
+        obj = _resolve(v, named, k) if isinstance(v, dict) else v
+        if isinstance(obj, BSDF):
+            if nested is not None:
+                raise RuntimeError("Cannot specify more than one child BSDF")
+            nested = obj
+    if nested is None:
+        raise RuntimeError("Child BSDF not specified")
+    if nested.kind in _WEIGHTED_BSDFS or (nested.back is not None and nested.back.kind in _WEIGHTED_BSDFS):
+        raise RuntimeError("mask: a nested `%s` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models, or `twosided` over them)"
+                           % (nested.kind if nested.kind in _WEIGHTED_BSDFS else nested.back.kind))
+    return MaskBSDF(props.get('opacity', 0.5), nested, id=key)
 
 
 def _mk_blendbsdf(props, named, key):
@@ -1263,6 +1303,8 @@ def _mk_blendbsdf(props, named, key):
     if len(nested) != 2:
         raise RuntimeError("BlendBSDF: Two child BSDFs must be specified!")
     for c in nested:
+        if c.kind == 'mask':
+            raise RuntimeError("blendbsdf: a nested `mask` is not supported in hip_ad_rgb (put the `mask` outside, over plain BSDF models)")
         if c.kind == 'blendbsdf' or (c.flags & 1):
             raise RuntimeError("blendbsdf: nested BSDFs must be plain BSDF models in this variant")
     return BlendBSDF(props['weight'], nested, id=key)
@@ -1270,7 +1312,7 @@ def _mk_blendbsdf(props, named, key):
 
 def _transmits(b):
     """does the BSDF have a transmission lobe (what `twosided` refuses, twosided.cpp:79-83)"""
-    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested))
+    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask'      # (BSDFFlags::Null is part of BSDFFlags::Transmission)
 
 
 def _mk_twosided(props, named, key):
@@ -1719,6 +1761,9 @@ class Integrator:
         else:
             check(lib().har_integrator_set_grad_positions(self._handle(), None, None))
             check(lib().har_integrator_set_grad_instances(self._handle(), None, None))
+        if self.bsdf_parameter_gradients and any(b.kind == 'mask' for b in scene.bsdfs):
+            raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `mask` in hip_ad_rgb (its `opacity` and the nested BSDF's colour slot 0 have gradients)"
+                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what != "ior"))
         if self.bsdf_parameter_gradients and any(b.kind == 'blendbsdf' for b in scene.bsdfs):
             raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `blendbsdf` in hip_ad_rgb (its `weight` and the nested BSDFs' colour slot 0 have gradients)"
                                % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what != "ior"))
@@ -1789,8 +1834,8 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
         kind, b = keys[k]
         v = torch.as_tensor(v, dtype=torch.float32, device=dev)
         if kind != "emit" and id(b) in scene._blend_nested():
-            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` are not produced in hip_ad_rgb (the weight's are; use render_backward)" % k)
-        if kind != "emit" and b.kind == 'blendbsdf':
+            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` are not produced in hip_ad_rgb (the weight's / opacity's are; use render_backward)" % k)
+        if kind != "emit" and b.kind in _WEIGHTED_BSDFS:
             # the tangent of the weight, in every colour channel of the record's slot 0 (a three-channel bitmap: of its luminance)
             if kind == "tex" and b.weight_channels == 3:
                 shape = t_tex[b.tex_index].shape
@@ -2152,7 +2197,8 @@ class Scene:
 
     def _blend_nested(self):
         """ids of the BSDF objects whose record is nested in a blend record of this scene -- also one that a shape or another blend references besides"""
-        return {id(c) for b in self.bsdf_objs for c in getattr(b, 'nested', ())}
+        out = {id(c) for b in self.bsdf_objs for c in getattr(b, 'nested', ())}
+        return out | {id(c.back) for b in self.bsdf_objs if b.kind == 'mask' for c in b.nested if c.back is not None}          # (mask: both sides of a nested `twosided` pair)
 
     def _add_mesh(self, key, m):
         if m.bsdf is None:          # Shape(props), shape.cpp:50-57: a default diffuse BSDF -- black when the shape carries an emitter
@@ -2260,6 +2306,8 @@ class Scene:
             bsdfs[i].back = b.back.index if b.back is not None else -1
             if b.kind == 'blendbsdf':
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, b.nested[1].index)
+            elif b.kind == 'mask':
+                bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, -1)
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
             texs[i].data = _fp(t); texs[i].height = t.shape[0]; texs[i].width = t.shape[1]; texs[i].mode = self.texture_modes[i] if i < len(self.texture_modes) else 0
@@ -2375,7 +2423,13 @@ class Scene:
         bp = getattr(b, 'blend_parent', None)
         if bp is not None:          # nested in a blendbsdf (BlendBSDF::traverse, blendbsdf.cpp:102-106): '<blend>.bsdf_0' / '<blend>.bsdf_1'
             return Scene._bsdf_key_base(bp[0]) + ".bsdf_%d" % bp[1]
+        mp = getattr(b, 'mask_parent', None)
+        if mp is not None:          # nested in a mask (MaskBSDF::traverse, mask.cpp:116-119): '<mask>.nested_bsdf', under a nested `twosided` '<mask>.nested_bsdf.brdf_0'
+            base = Scene._bsdf_key_base(mp) + ".nested_bsdf"
+            return base + ".brdf_0" if (b.flags & 1) else base
         parent = getattr(b, 'twosided_parent', None)
+        if parent is not None and getattr(parent, 'mask_parent', None) is not None:
+            return Scene._bsdf_key_base(parent.mask_parent) + ".nested_bsdf.brdf_1"
         if parent is not None:
             return (parent.id if parent.id else "bsdf%d" % parent.index) + ".brdf_1"
         base = b.id if b.id else "bsdf%d" % b.index
@@ -2942,8 +2996,8 @@ class Scene:
             if kind == "emit":
                 if g_emit is not None:
                     out[k] = g_emit[b]
-            elif b.kind == 'blendbsdf':
-                # the weight of a blend: the buffers hold d L / d w per colour channel of the radiance; the parameter is a scalar (sum of the row, as `alpha` is summed), a
+            elif b.kind in _WEIGHTED_BSDFS:
+                # the weight of a blend (the opacity of a mask): the buffers hold d L / d w per colour channel of the radiance; the parameter is a scalar (sum of the row, as `alpha` is summed), a
                 # one-channel bitmap (channel sum) or a three-channel one whose luminance is the weight (d w / d texel_k = lum_k)
                 if kind == "tex":
                     s = g_tex[b.tex_index].sum(dim=2, keepdim=True)
@@ -2957,7 +3011,7 @@ class Scene:
     @staticmethod
     def _colour_view(kind, b, value):
         """the value mi.traverse() shows for slot 0 of a BSDF: the stored one, except a blend's weight -- a scalar, or the H x W x 1 / x 3 bitmap it was given"""
-        if b.kind != 'blendbsdf':
+        if b.kind not in _WEIGHTED_BSDFS:
             return value
         v = np.asarray(value, np.float32)
         if kind == "tex":
@@ -2967,7 +3021,7 @@ class Scene:
     @staticmethod
     def _colour_store(kind, b, t, key):
         """the inverse for a blend's weight, on a torch tensor or a numpy array: a scalar is stored as (w, w, w), a one-channel bitmap three times"""
-        if b.kind != 'blendbsdf':
+        if b.kind not in _WEIGHTED_BSDFS:
             return t
         if kind == "tex":
             h, w = b.texture.shape[:2]; c = b.weight_channels
@@ -3462,7 +3516,7 @@ class DeviceGroup:
 # ---------------------------------------------------------------------------
 
 _REGISTRY = {}
-_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf')
+_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask')
 
 
 def register_plugin(name, variant_name, instantiate):
@@ -3604,7 +3658,7 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
@@ -3667,7 +3721,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
     nested = [k for k in keys if k in scene._bsdf_param_keys() and id(scene._bsdf_param_keys()[k][1]) in scene._blend_nested()]
     if nested:
-        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` have no gradient in hip_ad_rgb (its `weight` and the nested BSDFs' colour slot 0 do)" % nested)
+        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` have no gradient in hip_ad_rgb (the `weight` / `opacity` and the nested BSDFs' colour slot 0 do)" % nested)
     if not keys:
         return integrator.render(scene, sensor, seed, spp)
     params.update()

@@ -43,10 +43,16 @@ inline const char *aov_spec_lower(uint32_t n, const uint32_t *types, AovSpec &sp
  *  - `diffuse`: the reflectance texture at si.uv (diffuse.cpp:181); `plastic` / `roughplastic`: `diffuse_reflectance` (plastic.cpp:362, roughplastic.cpp:504);
  *    both are colour slot 0 of the record;
  *  - every other model: the base class, eval(BSDFContext(), si, wo = (0, 0, 1)) * pi (src/render/bsdf.cpp:38-43). */
-template <bool BLEND = false>        /* BLEND: the scene may hold `blendbsdf` records (the kernels of other scenes compile that branch out) */
+template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
 HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
+    constexpr bool BLEND = (COMP & HAR_SCENE_BLEND) != 0u;
     BsdfSide side;
     if (!bsdf_side(S, S.meshes[si.mesh].bsdf, si.wi, side)) return Vec3(0.f);
+    if ((COMP & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) {
+        /* MaskBSDF::eval_diffuse_reflectance (mask.cpp:229-232): the nested BSDF's own answer -- through its `twosided`, if it has one (twosided.cpp:243-259) */
+        const uint32_t nested = S.bsdfs[side.index].pad;
+        if (!bsdf_side(S, nested, si.wi, side)) return Vec3(0.f);
+    }
     const DBsdf &B = S.bsdfs[side.index];
     TexTaps taps;
     const BsdfInputs in = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps);
@@ -72,7 +78,7 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
  * si.p comes from the triangle), `top_meshes` = number of top-level meshes of the scene.
  * shape_index (aov.cpp:288-297, the scalar branch): the 1-based position of the hit instance -- or, without one, of the hit shape -- in the
  * scene's shape list, which here is { top-level meshes, instances }; 0 on a miss. */
-template <bool BLEND = false>
+template <uint32_t COMP = 0u>
 HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, Vec3 ray_d, const Hit &hit, bool active, float *out, size_t stride) {
     const bool valid = active && hit.t != HAR_INF;
     SurfInt si; SurfPartials P;
@@ -82,7 +88,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
     if (valid) {
         si = compute_si(S, ray_d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
         if (need_partials) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
-        if (need_albedo) albedo = aov_albedo<BLEND>(S, si);
+        if (need_albedo) albedo = aov_albedo<COMP>(S, si);
     }
     size_t c = 0;
     for (uint32_t k = 0; k < spec.n; ++k) {

@@ -72,7 +72,20 @@ __global__ __launch_bounds__(kBlock) void k_aov_fill(DScene S, AovSpec spec, uin
     else { D = Vec3(d[i], d[n + i], d[2 * (size_t) n + i]); act = !(active && !active[i]); }
     const float4 a = h0[i]; const uint2 b = h1[i];
     Hit hit; hit.t = a.x; hit.u = a.y; hit.v = a.z; hit.prim = __float_as_uint(a.w); hit.shape = b.x; hit.inst = b.y;
-    aov_lane<BLEND>(S, spec, top_meshes, D, hit, act, aov + i, stride);
+    aov_lane<(BLEND ? HAR_SCENE_BLEND : 0u)>(S, spec, top_meshes, D, hit, act, aov + i, stride);
+}
+/* ... of a scene that holds a `mask` record (blend and mask records resolved); a kernel of its own, so that the ones above keep their code and names */
+template <bool LANES>
+__global__ __launch_bounds__(kBlock) void k_aov_fill_mask(DScene S, AovSpec spec, uint32_t top_meshes, DSensor C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                          uint32_t n, const float *d, const uint8_t *active, const float4 *h0, const uint2 *h1, float *aov, size_t stride) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    Vec3 D; bool act = true;
+    if (LANES) { LaneSample ls; D = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls).d; }
+    else { D = Vec3(d[i], d[n + i], d[2 * (size_t) n + i]); act = !(active && !active[i]); }
+    const float4 a = h0[i]; const uint2 b = h1[i];
+    Hit hit; hit.t = a.x; hit.u = a.y; hit.v = a.z; hit.prim = __float_as_uint(a.w); hit.shape = b.x; hit.inst = b.y;
+    aov_lane<HAR_SCENE_COMPOSITE>(S, spec, top_meshes, D, hit, act, aov + i, stride);
 }
 
 /* ImageBlock::put (coalesced JIT branch, imageblock.cpp:444-520) of `channels` values + the weight per lane: the LDS gather of k_splat (har_kernels.hip) for an
@@ -193,12 +206,14 @@ void launch_aov_trace_rays(hipStream_t s, const DScene &S, bool deep, uint32_t n
 }
 void launch_aov_fill_lanes(hipStream_t s, const DScene &S, const AovSpec &spec, uint32_t top_meshes, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp,
                            uint32_t lane_base, uint32_t n, const float4 *h0, const uint2 *h1, float *aov, size_t stride) {
+    if (S.bsdf_types & HAR_SCENE_MASK) { hipLaunchKernelGGL((k_aov_fill_mask<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
     if (S.bsdf_types & HAR_SCENE_BLEND) { hipLaunchKernelGGL((k_aov_fill<true, true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
     hipLaunchKernelGGL((k_aov_fill<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride);
 }
 void launch_aov_fill_rays(hipStream_t s, const DScene &S, const AovSpec &spec, uint32_t top_meshes, uint32_t n, const float *d, const uint8_t *active,
                           const float4 *h0, const uint2 *h1, float *aov) {
     const DSensor C{};
+    if (S.bsdf_types & HAR_SCENE_MASK) { hipLaunchKernelGGL((k_aov_fill_mask<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }
     if (S.bsdf_types & HAR_SCENE_BLEND) { hipLaunchKernelGGL((k_aov_fill<false, true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }
     hipLaunchKernelGGL((k_aov_fill<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n);
 }

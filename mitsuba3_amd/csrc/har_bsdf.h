@@ -8,6 +8,8 @@
  *   flag    twosided         src/bsdfs/twosided.cpp:112-270             (one nested BSDF, or a different one on the back)
  *   type 6  blendbsdf        src/bsdfs/blendbsdf.cpp:108-233            (two nested records mixed by a weight; resolved in har_scene.h, where the scene's records are at hand)
  *
+ *   type 7  mask             src/bsdfs/mask.cpp:93-232                  (one nested record scaled by an opacity, and a null lobe; resolved in har_scene.h)
+ *
  * plus include/mitsuba/render/fresnel.h:35-91 (fresnel), :93-116 (fresnel_conductor), :276-313 (reflect / refract)
  * and  include/mitsuba/render/microfacet.h:185-421 (MicrofacetDistribution eval / pdf / sample / smith_g1).
  *
@@ -22,10 +24,13 @@
 namespace har {
 
 enum { BSDF_DIFFUSE = 0, BSDF_DIELECTRIC = 1, BSDF_ROUGHCONDUCTOR = 2, BSDF_ROUGHPLASTIC = 3, BSDF_CONDUCTOR = 4, BSDF_PLASTIC = 5, BSDF_TYPE_COUNT = 6 /* the leaf models */,
-       BSDF_BLEND = 6 /* a record that names two leaf records (DBsdf::table, ::pad) and mixes them by the weight in slot 0 */ };
+       BSDF_BLEND = 6 /* a record that names two leaf records (DBsdf::table, ::pad) and mixes them by the weight in slot 0 */,
+       BSDF_MASK = 7 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and scales it by the opacity in slot 0, with a null lobe for the rest */ };
 /* BF_MONO: the bitmap in slot 0 of a blend record has ONE channel (stored three times): Texture::eval_1 reads it instead of taking the luminance (bitmap.cpp:537-540).
- * BF_BLEND_SMOOTH: derived when a blend record is lowered -- one of its nested BSDFs has a smooth lobe (BSDFFlags::Smooth of the union, blendbsdf.cpp:99) */
-enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u, BF_MONO = 16u, BF_BLEND_SMOOTH = 32u };
+ * BF_BLEND_SMOOTH: derived when a blend record is lowered -- one of its nested BSDFs has a smooth lobe (BSDFFlags::Smooth of the union, blendbsdf.cpp:99)
+ * BF_MASK_SMOOTH (the same bit, in a mask record): the nested BSDF -- either side of a nested `twosided` pair -- has a smooth lobe (mask.cpp:113) */
+enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u, BF_MONO = 16u, BF_BLEND_SMOOTH = 32u, BF_MASK_SMOOTH = 32u };
+enum { LOBE_NULL = 0x1u };                    /* BSDFFlags::Null (bsdf.h:37): the only lobe of that kind is the mask record's */
 #define HAR_ROUGH_TRANSMITTANCE_RES 64          /* MI_ROUGH_TRANSMITTANCE_RES, include/mitsuba/render/microfacet.h */
 
 /* colour parameter slots: slot 0 = diffuse.reflectance | roughconductor.specular_reflectance |
@@ -40,7 +45,7 @@ struct DBsdf {
     int32_t back;                 /* twosided: BSDF record of the back side (-1: the same record) */
     int32_t table;                /* roughplastic: offset of its 64-entry external transmittance table, else -1; blend: record index of nested BSDF 0 */
     float inv_eta_2, internal_reflectance, spec_sampling_weight;
-    uint32_t pad;                 /* blend: record index of nested BSDF 1 */
+    uint32_t pad;                 /* blend: record index of nested BSDF 1; mask: record index of its nested BSDF (`table` stays -1) */
 };
 static_assert(sizeof(DBsdf) == 96, "DBsdf layout");
 
@@ -299,6 +304,14 @@ HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC &&
  * instantiation per launch, TYPES = HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_BLEND; every line of blend code sits behind a test of this bit */
 #define HAR_SCENE_BLEND 0x800u
 #define HAR_SCENE_BLEND_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_BLEND)
+/* ... and a `mask` record (type 7): a null lobe, and the validity of a camera sample decided along the path.  A scene with such a record runs the widest set,
+ * TYPES = HAR_SCENE_MASK_TYPES = the blend set | HAR_SCENE_MASK (it may hold blend records on other meshes: ONE more set of instantiations instead of two); every line of
+ * mask code sits behind a test of this bit.  The bits in use: 0xff models, 0x100 ENVMAP, 0x200 QUEUED, 0x400 TEXLIGHT, 0x800 BLEND, 0x1000 MASK, 0x80000000 twosided
+ * (DScene::bsdf_types) -- a blend / mask record sets its scene bit there, not 1u << type, which would fall into the model bits */
+#define HAR_SCENE_MASK 0x1000u
+#define HAR_SCENE_MASK_TYPES (HAR_SCENE_BLEND_TYPES | HAR_SCENE_MASK)
+#define HAR_SCENE_COMPOSITE (HAR_SCENE_BLEND | HAR_SCENE_MASK)          /* scenes that run one widest shading kernel per flavour */
+static_assert((HAR_SCENE_MASK & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x80000000u)) == 0u, "HAR_SCENE_MASK collides with another scene bit");
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */

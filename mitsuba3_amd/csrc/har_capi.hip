@@ -134,6 +134,13 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
     ShadeParams P{ seed, I->set.max_depth, I->set.rr_depth, plan.shade_flags };
     /* generic shading kernels: material-sort window in tiles of 256 paths (k_shade; HAR_SORT_WINDOW=1 is the round-3 kernel, A/B) */
     P.sort_window = switches().sort_window;
+    /* `path` in a scene with a mask record: the validity flags start at 0 (the miss value: no visible environment here) and come out of shading */
+    float *valid_dst = nullptr;
+    if (plan.valid_shade) {
+        if (!valid_lane && !I->alpha_lane && ws_alloc(I, &I->alpha_lane, I->ws_lanes)) return 1;
+        valid_dst = valid_lane ? valid_lane : I->alpha_lane;
+        HIP_TRY(hipMemsetAsync(valid_dst, 0, (size_t) n * sizeof(float), s));
+    }
     ShadeParams P0 = P;           /* bounce 0 with first_regen */
     if (first_regen) { P0.flags |= HAR_SHADE_FIRST_VERTEX; P0.spp = spp; P0.log_spp = log_spp; P0.sensor = C; P0.resume = (ps.rng && ps.pass) ? 1u : 0u; }
     uint2 *spill = plan.spill ? I->stack_spill : nullptr;
@@ -216,7 +223,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
         } else
         launch_shade(mode, s, grid, S->ds, (b == 0 && first_regen) ? P0 : P, lane_base, I->shard_cap, cnt_alive(I, b), st_in, h0, h1, st_out, cnt_alive(I, b + 1),
                      items_b, cnt_items(I, b), I->result, rc, ps.rng, I->dL, grad_refl, shape ? &I->geo : nullptr, inline_commit && cached ? I->d_grad_tex : nullptr,
-                     queued ? &I->tq : nullptr, (inline_commit && cached) ? I->set.grad_bsdf_params : nullptr, nullptr, 0, (tape || rec_w) ? &tp : nullptr);
+                     queued ? &I->tq : nullptr, valid_dst ? valid_dst /* `path`, mask scene: launch_shade hands the flags to the kernel in this slot */ : (inline_commit && cached) ? I->set.grad_bsdf_params : nullptr, nullptr, 0, (tape || rec_w) ? &tp : nullptr);
         prof_mark(I, s, CLS_SHADE);
         const float4 *const beta = (fused_nee && !(b == 0 && first_regen)) ? st_in.a2 : nullptr;
         if (queued) { texel_queues_accumulate(I, n, s); prof_mark(I, s, CLS_OTHER); }
@@ -253,6 +260,7 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
     for (int k = 0; k < 2; ++k) if (resolve_pending[k]) HIP_TRY(hipStreamWaitEvent(s, ev_res[k], 0));
     if (late_pending) { HIP_TRY(hipStreamWaitEvent(s, I->ev_resolved, 0)); late_pending = false; prof_mark(I, s, CLS_RESOLVE); }
     if (overlap) launch_add(s, reinterpret_cast<const float *>(I->result2), reinterpret_cast<float *>(I->result), 4u * n);      /* the shadow rays' share of the radiance */
+    if (valid_dst) launch_drop_invalid(s, n, valid_dst, I->result);
     if (shape && b > 0) {            /* the last bounce: no path continues */
         launch_shape_adjoint(s, grid, S->ds, cnt_items(I, b - 1), I->shard_cap, I->items, I->geo, I->result, I->dL, 0, I->st[cur], I->h0, I->h1, ReplayCache{ nullptr, nullptr, nullptr, CACHE_NONE }, targets);
         prof_mark(I, s, CLS_OTHER);
@@ -661,7 +669,8 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     /* texels of a light's bitmap radiance: committed in place by the re-shading replay as well (the record tape holds neither the sampled uv nor the unit weight) */
     const bool light_texels = I->set.grad_light_texels && (S->ds.bsdf_types & HAR_SCENE_TEXLIGHT) != 0u;
     /* a `blendbsdf` record: the nested records' gradients are deposited by the in-place commit of the re-shading replay (the record tape holds one record per vertex) */
-    const bool blend = (S->ds.bsdf_types & HAR_SCENE_BLEND) != 0u;
+    const bool blend = (S->ds.bsdf_types & HAR_SCENE_COMPOSITE) != 0u;
+    const char *const comp = (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
     int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
     tape = std::min(tape, I->bw_tape_max);
     /* The tapes are the large workspaces (record tape 69 B, state tape 115 B per lane and bounce against 25 B for the lane-indexed cache: 28 - 90 GB for a 2^26-lane chunk
@@ -702,10 +711,10 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
         if (!W.adjoint_inline) return fail("gradients of a light's texels need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (blend) {
-        if (I->set.grad_bsdf_params) return fail("blendbsdf: gradients of alpha / eta / k / specular colours are not produced for scenes with a blend record (the weight and the nested BSDFs' colour slot 0 are)");
-        if (!I->set.use_cache || I->shape_on) return fail("blendbsdf: gradients need the replay cache and cannot be combined with vertex-position gradients");
-        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail("blendbsdf: gradients of a scene with a blend record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
-        if (!W.adjoint_inline) return fail("blendbsdf: gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
+        if (I->set.grad_bsdf_params) return fail(std::string(comp) + ": gradients of alpha / eta / k / specular colours are not produced for scenes with a " + ((S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask record (the opacity and the nested BSDF's colour slot 0 are)" : "blend record (the weight and the nested BSDFs' colour slot 0 are)"));
+        if (!I->set.use_cache || I->shape_on) return fail(std::string(comp) + ": gradients need the replay cache and cannot be combined with vertex-position gradients");
+        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail(std::string(comp) + ": gradients of a scene with a " + ((S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blend") + " record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
+        if (!W.adjoint_inline) return fail(std::string(comp) + ": gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (I->set.grad_bsdf_params) {
         /* the alpha / eta / k / slot-1 terms are committed in place by the cached-bounce shading kernel only */
@@ -819,6 +828,7 @@ int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const 
          * attached si.wi (prb.py:128-140) */
         const size_t nm = S->hs.meshes.size();
         /* their adjoint goes through items, which carry one (record, direct, relative) triple per vertex: a blend vertex has three */
+        if (S->ds.bsdf_types & HAR_SCENE_MASK) return fail("vertex-position gradients are not produced for a scene with a `mask` record");
         if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("vertex-position gradients are not produced for a scene with a `blendbsdf` record");
         offset.assign(nm, -1); user.assign(nm, nullptr); count.assign(nm, 0);
         for (size_t m = 0; m < nm; ++m) {          /* top-level meshes, then the meshes of the shape groups (vertex positions shared by all their instances) */
@@ -860,6 +870,7 @@ int har_integrator_set_grad_instances(HarIntegrator I, HarScene S, float *grad_t
     uint32_t n = 0;
     if (grad_to_world) {
         if (!S) return fail("null scene");
+        if (S->ds.bsdf_types & HAR_SCENE_MASK) return fail("instance to_world gradients are not produced for a scene with a `mask` record");
         if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("instance to_world gradients are not produced for a scene with a `blendbsdf` record");
         /* as for the vertex positions: any BSDF with a non-delta lobe on the moving geometry, i.e. on the meshes of the shape groups */
         for (size_t m = S->hs.top_mesh_count; m < S->hs.meshes.size(); ++m)

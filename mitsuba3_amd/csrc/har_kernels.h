@@ -183,6 +183,8 @@ void launch_shape_adjoint(hipStream_t s, uint32_t grid, const DScene &S, const u
 void launch_normals_adjoint(hipStream_t s, const DScene &S, uint32_t mesh, uint32_t face_count, uint32_t vertex_count, float *acc, const float *nbar, float *grad);
 void launch_splat(hipStream_t s, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base, uint32_t n,
                   const float4 *result, int weights_only, float *film, const float2 *jitter = nullptr, const float *scalar = nullptr);   /* weights_only + scalar: w * scalar[i] */
+/* `path` in a mask scene: result[i] = 0 where valid[i] == 0 (the chunk's n lanes), see k_drop_invalid */
+void launch_drop_invalid(hipStream_t s, uint32_t n, const float *valid, float4 *result);
 /* alpha flags of the camera samples of a wavefront (1 = valid), see k_alpha_flags */
 void launch_alpha_flags(hipStream_t s, uint32_t grid, uint32_t shard_cap, const uint32_t *count_in, const WaveState &in, const float4 *h0, uint32_t lane_base, float miss_value, float *alpha);
 void launch_pass_jitter(hipStream_t s, uint32_t seed, uint32_t lane_base, uint32_t n, uint32_t pass, float2 *jitter);

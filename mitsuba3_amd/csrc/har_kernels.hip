@@ -1306,6 +1306,9 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
             Hit hit; hit.t = hh.x; hit.u = hh.y; hit.v = hh.z; hit.prim = __float_as_uint(hh.w); hit.shape = hs.x; hit.inst = hs.y;
             shade_lane<MODE, TYPES, EXTRA>(S, P, st, hit, R, has_hx ? &hx : nullptr);
             lane = st.lane - lane_base;
+            /* `path` in a scene with a mask record (ChunkPlan::valid_shade): valid_ray |= a non-null lobe was sampled here (path.cpp:307-308).  The chunk's per-lane validity
+             * flags, cleared by run_chunk, arrive in the `grad_extra` argument, which no MODE_PATH kernel reads otherwise (the kernels' argument list stays what it was) */
+            if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH && grad_extra && R.non_null) grad_extra[lane] = 1.f;
             if (MODE == MODE_PRB_ADJOINT && INLINE) {
                 if (tape_read) { const float4 a = tape.la_in[i]; const float2 c2 = tape.lb_in[i]; Lr = Vec3(a.x, a.y, a.z); dlr = Vec3(a.w, c2.x, c2.y); }
                 else { const float4 r = result[lane], d4 = dL[lane]; Lr = Vec3(r.x, r.y, r.z); dlr = Vec3(d4.x, d4.y, d4.z); }
@@ -2225,6 +2228,42 @@ __global__ void k_api_bsdf_sample(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t
     if (stype) stype[i] = b.type;
     if (scomp) scomp[i] = b.comp;
 }
+/* ... of a scene that holds a `mask` record: the same two entries over the widest BSDF code (blend and mask records resolved).  Kernels of their own, so that the ones
+ * above stay the code -- and keep the names -- they had */
+__global__ void k_api_bsdf_eval_pdf_mask(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active, float *value, float *pdf) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    BsdfEval e; e.value = Vec3(0.f); e.pdf = 0.f;
+    if (!(active && !active[i])) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_COMPOSITE, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+    }
+    if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
+    if (pdf) pdf[i] = e.pdf;
+}
+__global__ void k_api_bsdf_sample_mask(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const uint8_t *active,
+                                       float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
+    if (!(active && !active[i])) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_COMPOSITE, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+    }
+    wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
+    weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
+    if (eta) eta[i] = b.eta;
+    if (stype) stype[i] = b.type;
+    if (scomp) scomp[i] = b.comp;
+}
+/* `path` in a scene with a mask record: the radiance of a camera sample that stayed invalid is dropped, dr::select(valid_ray, result, 0) (path.cpp:341-345) */
+__global__ void k_drop_invalid(uint32_t n, const float *valid, float4 *result) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (valid[i] == 0.f) result[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+}
 __global__ void k_api_sensor_ray(DSensor C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
@@ -2329,6 +2368,20 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_MASK) {
+        /* a scene with a `mask` record: the same four flavours as for a blend scene (below), in the set that carries the mask code as well -- such a scene may hold blend
+         * records on other meshes, so this set is the blend set plus the null lobe: four more shading kernels, not eight */
+        constexpr uint32_t T = HAR_SCENE_MASK_TYPES;
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PATH)
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags, or null (run_chunk) */, no_mq, 0u, tape);
+        else if (mode == MODE_PRB_PRIMAL)
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_BLEND) {
         /* a scene with a `blendbsdf` record: ONE widest instantiation per flavour -- forward, prb primal, the in-place adjoint commit of a cached / taped bounce (the route
          * every backward pass of such a scene takes: it deposits the nested records' gradients) and the item-writing adjoint that forward mode reads.  plan_chunk keeps the
@@ -2471,6 +2524,9 @@ void launch_resolve(int mode, hipStream_t s, uint32_t grid, uint2 *spill, const 
 #undef HAR_LAUNCH_RESOLVE
 #undef HAR_LAUNCH_RESOLVE_FWD
 }
+void launch_drop_invalid(hipStream_t s, uint32_t n, const float *valid, float4 *result) {
+    hipLaunchKernelGGL(k_drop_invalid, dim3(blocks_for(n)), dim3(kBlock), 0, s, n, valid, result);
+}
 void launch_alpha_flags(hipStream_t s, uint32_t grid, uint32_t shard_cap, const uint32_t *count_in, const WaveState &in, const float4 *h0, uint32_t lane_base, float miss_value, float *alpha) {
     hipLaunchKernelGGL(k_alpha_flags, dim3(grid), dim3(kBlock), 0, s, shard_cap, count_in, in.a3, h0, lane_base, miss_value, alpha);
 }
@@ -2557,12 +2613,14 @@ void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const u
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {
-    if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else hipLaunchKernelGGL(k_api_bsdf_eval_pdf<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
 }
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
-    if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_sample_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else hipLaunchKernelGGL(k_api_bsdf_sample<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
 }
 void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {

@@ -83,6 +83,10 @@ struct ShadeResult {
      * each and (d f / d slot 0) / f at the sampled direction -- the factors (1 - w) / w are in them and f is the BLENDED value; bl_ind: the second term exists.  The weight's
      * own pair rides in dLr_drho / rel_grad (BsdfEval::d_slot0 of a blend vertex is d value / d weight); the in-place commit of k_shade deposits the nested ones */
     uint32_t bl_rec[2]; Vec3 bl_dir[2], bl_rel[2]; bool bl_ind;
+    /* ... kernels of scenes with a `mask` record (HAR_SCENE_MASK), MODE_PATH: this vertex makes the camera sample valid -- the lane entered the loop body at a surface and
+     * the BSDF sample drawn there is not the null lobe (path.cpp:307-308; JIT order: drawn at the last vertex, depth + 1 == max_depth, too).  A mask vertex files the
+     * opacity's gradient pair in dLr_drho / rel_grad and the nested LEAF record's in bl_*[0] (bl_rec[1] stays 0xffffffff), as a blend vertex does */
+    bool non_null;
 };
 #define HAR_EXTRA_GROUPS 5
 
@@ -146,6 +150,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT && EXTRA) { for (int g = 0; g < 5; ++g) { R.x_dir[g] = Vec3(0.f); R.x_rel[g] = Vec3(0.f); } R.x_ind = false; }
     if (MODE == MODE_PRB_ADJOINT) { R.lt_hit_emitter = -1; R.lt_nee_emitter = -1; R.lt_hit_uv[0] = R.lt_hit_uv[1] = R.lt_nee_uv[0] = R.lt_nee_uv[1] = 0.f; }
     if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_BLEND) != 0u) { R.bl_rec[0] = R.bl_rec[1] = 0xffffffffu; R.bl_dir[0] = R.bl_dir[1] = R.bl_rel[0] = R.bl_rel[1] = Vec3(0.f); R.bl_ind = false; }
+    if ((TYPES & HAR_SCENE_MASK) != 0u) R.non_null = false;
     if (MODE == MODE_PRB_ADJOINT) { R.em_index = -1; R.nee_emitter = -1; R.em_unit = Vec3(0.f); R.contrib_unit = Vec3(0.f); R.nee_flags = 0u; R.cos_em = 0.f; R.nee_p = Vec3(0.f); R.nee_n = Vec3(0.f); R.nee_w = Vec3(0.f); }
     uint64_t rng = st.rng;
     const uint64_t inc = sampler_inc(P.seed, st.lane);
@@ -199,6 +204,21 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     }
 
     bool active_next = (depth + 1u < P.max_depth) && valid;
+    if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH && !active_next && valid) {
+        /* the path ends at this surface.  JIT order: the lane still draws this iteration's numbers, and valid_ray takes the sampled lobe's type (path.cpp:263-267,307-308):
+         * at a mask record the third draw decides, sample1 < opacity.  Scalar order: the early exit (:227-231), valid_ray |= the surface is an emitter */
+        if (P.flags & HAR_SHADE_SCALAR_DRAWS) R.non_null = emitter >= 0;
+        else {
+            BsdfSide vs; R.non_null = true;
+            if (bsdf_side(S, M.bsdf, si.wi, vs) && S.bsdfs[vs.index].type == BSDF_MASK) {
+                const DBsdf VB = S.bsdfs[vs.index];
+                TexTaps vt; const BsdfInputs vin = bsdf_inputs(S, VB, si.uv_x, si.uv_y, vt);
+                bool inside; const float o = mask_opacity(VB, vin, inside);
+                uint64_t r = rng; pcg32_next_float(r, inc); pcg32_next_float(r, inc);
+                R.non_null = pcg32_next_float(r, inc) < o;
+            }
+        }
+    }
     if (MODE == MODE_PATH && !active_next) return;
     if (MODE != MODE_PATH && !valid) return;      /* prb: nothing below contributes for a miss */
 
@@ -216,8 +236,11 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     /* BSDFFlags::Smooth of the record: a compile-time constant in the kernels of a single-model material queue */
     /* a blend record (kernels of blend scenes only): Smooth if one of the nested BSDFs is (the union of their flags, blendbsdf.cpp:99; derived when the record is lowered) */
     const bool blend = (TYPES & HAR_SCENE_BLEND) != 0u && B.type == BSDF_BLEND;
+    /* a mask record (kernels of mask scenes only): Smooth if its nested BSDF is (mask.cpp:113); `composite`: the vertex files gradients for nested records (bl_*) */
+    const bool mask = (TYPES & HAR_SCENE_MASK) != 0u && B.type == BSDF_MASK;
+    const bool composite = blend || mask;
     const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR)
-                                               : (blend ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
+                                               : (composite ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
     DirSample ds; ds.pdf = 0.f; ds.d = Vec3(0.f); ds.p = Vec3(0.f); ds.n = Vec3(0.f); ds.dist = 0.f;
     Vec3 em_weight(0.f); float em_unit = 0.f; uint32_t em_sampled = 0;
@@ -281,6 +304,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr);
     BsdfSample bs; bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
     if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y);
+    if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH) R.non_null = !(mask && bs.type == LOBE_NULL);        /* path.cpp:307-308 (si is valid here) */
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
     R.contrib = Vec3(0.f); R.contrib_b = Vec3(0.f); R.dLr_drho = Vec3(0.f); R.dLr_drho_unit = Vec3(0.f); R.rho = bin.slot0;
@@ -295,7 +319,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 /* em_weight = radiance * em_unit for `area` / `constant` emitters (prb.py:198-206, attached eval_emitter_direction) */
                 R.nee_emitter = ((P.flags & HAR_SHADE_EMITTER_GRADS) && S.emitters[em_sampled].type != 2u && S.emitters[em_sampled].type != 7u) ? (int32_t) em_sampled : -1;
                 R.contrib_unit = ((st.throughput * mis_em) * ev.value) * em_unit;
-                if ((TYPES & HAR_SCENE_BLEND) != 0u && blend)
+                if ((TYPES & HAR_SCENE_BLEND) != 0u && composite)
                     for (int k = 0; k < 2; ++k) R.bl_dir[k] = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
                 if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
                     BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok, wo_em, x);
@@ -312,7 +336,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
         if (MODE != MODE_PATH) {
             const Vec3 d0 = ((st.throughput * mis_em) * ev.d_slot0) * em_weight;
             grad_item = d0.x != 0.f || d0.y != 0.f || d0.z != 0.f;
-            if ((TYPES & HAR_SCENE_BLEND) != 0u && blend)          /* ... or the nested records' colours have one (two equal nested values: d / d weight = 0) */
+            if ((TYPES & HAR_SCENE_BLEND) != 0u && composite)          /* ... or the nested records' colours have one (two equal nested values: d / d weight = 0) */
                 for (int k = 0; k < 2; ++k) {
                     const Vec3 dk = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
                     grad_item = grad_item || dk.x != 0.f || dk.y != 0.f || dk.z != 0.f;
@@ -386,8 +410,11 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
             }
         }
         R.item = R.item_ray || R.ind_active || (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE && R.x_ind);   /* otherwise the vertex has a zero gradient */
-        if ((TYPES & HAR_SCENE_BLEND) != 0u && blend) {
+        if ((TYPES & HAR_SCENE_BLEND) != 0u && composite) {
             R.bl_rec[0] = (uint32_t) B.table; R.bl_rec[1] = B.pad;
+            if (mask) {          /* one nested record: the leaf that serves this side of a nested `twosided` (none where a two-BSDF pair is zero, wi.z == 0) */
+                BsdfSide ns; R.bl_rec[0] = bsdf_side(S, B.pad, si.wi, ns) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
+            }
             for (int k = 0; k < 2; ++k) {
                 R.bl_rel[k] = Vec3(e2.value.x != 0.f ? cg.d[k].x / e2.value.x : 0.f, e2.value.y != 0.f ? cg.d[k].y / e2.value.y : 0.f, e2.value.z != 0.f ? cg.d[k].z / e2.value.z : 0.f);
                 R.bl_ind = R.bl_ind || (alive && (R.bl_rel[k].x != 0.f || R.bl_rel[k].y != 0.f || R.bl_rel[k].z != 0.f));

@@ -405,7 +405,7 @@ struct BlendChildGrad { Vec3 d[2]; };
 /* eval / pdf / eval_pdf (:162-222).  e.d_slot0 = d value / d weight = v1 - v0 where the weight is not clipped (with a component selected: +/- the nested value) */
 template <uint32_t TYPES, bool CTX>
 HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
-    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_BLEND;
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bool inside; const float w = blend_weight(B, in, inside);
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
     if (cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
@@ -442,7 +442,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
  * eta, sampled_type and sampled_component are the sampled BSDF's own (not offset, as in the reference); delta lobes go through the same arithmetic. */
 template <uint32_t TYPES, bool CTX>
 HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
-    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_BLEND;
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bool inside; const float w = blend_weight(B, in, inside);
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
     if (CTX && ctx.component != 0xffffffffu) {                   /* :116-126 */
@@ -471,7 +471,67 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
     bs.pdf = pdf_weighted;
 }
 
-/* (u, v): the vertex's texture coordinates -- read only by the kernels of blend scenes, whose nested records look up their own colour inputs there */
+/* ---- MaskBSDF (src/bsdfs/mask.cpp), record type 7: slot 0 is the opacity, DBsdf::pad names the nested record -- a leaf model that may carry the twosided flag (one
+ * BSDF or a pair): bsdf_side is applied to IT, with the vertex's unmirrored wi, and the leaf it returns is evaluated with its own colour inputs at the vertex's uv.  Only
+ * the kernels of scenes that hold such a record carry this code (TYPES & HAR_SCENE_MASK).  eval_opacity (:225-227) = clip(opacity->eval_1(si), 0, 1): the blend weight's
+ * arithmetic, `inside` included.  Components: the nested BSDF's, then the null lobe at the last index (:107-113). */
+HAR_HD float mask_opacity(const DBsdf &B, const BsdfInputs &in, bool &inside) { return blend_weight(B, in, inside); }
+HAR_HD uint32_t mask_null_index(const DScene &S, const DBsdf &B) {
+    const DBsdf &N = S.bsdfs[B.pad];
+    uint32_t c = bsdf_component_count(N.type);
+    if (N.flags & BF_TWOSIDED) c += N.back >= 0 ? bsdf_component_count(S.bsdfs[N.back].type) : c;        /* twosided.cpp:86-100: the front BSDF's components, then the back's -- also when both are ONE BSDF */
+    return c;
+}
+/* eval / pdf / eval_pdf (:169-217): the nested value times the opacity; the pdf is 0 when the context leaves the nested components out and is scaled by the opacity only
+ * when the null lobe is enabled.  e.d_slot0 = d value / d opacity = the nested value where the opacity is not clipped; cg->d[0] = d value / d (slot 0 of the nested LEAF) */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
+    bool inside; const float o = mask_opacity(B, in, inside);
+    bool transmission = true, nested = true;
+    if (CTX) {
+        const uint32_t null_index = mask_null_index(S, B);
+        transmission = ctx.is_enabled(LOBE_NULL, null_index);
+        nested = ctx.component == 0xffffffffu || ctx.component < null_index;
+    }
+    BsdfEval ne; ne.value = Vec3(0.f); ne.pdf = 0.f; ne.d_slot0 = Vec3(0.f); ne.d_slot1 = Vec3(0.f);
+    BsdfSide ns;
+    if (bsdf_side(S, B.pad, wi, ns)) {
+        const DBsdf &N = S.bsdfs[ns.index];
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        bsdf_eval_pdf_one<LEAF, CTX>(N, nin, ns.wi, Vec3(wo.x, wo.y, wo.z * ns.wo_sign), ne, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
+    }
+    e.value = ne.value * o;
+    e.pdf = !nested ? 0.f : (transmission ? ne.pdf * o : ne.pdf);
+    e.d_slot0 = inside ? ne.value : Vec3(0.f); e.d_slot1 = Vec3(0.f);
+    if (cg) { cg->d[0] = ne.d_slot0 * o; cg->d[1] = Vec3(0.f); }
+}
+/* sample (:121-167): sample1 < o takes the nested BSDF with sample1 / o -- its weight, type, component and eta as they are, its pdf times o --, otherwise the null lobe:
+ * wo = -wi (the vertex's own wi, not the mirrored one), pdf = 1 - o, weight = 1, eta = 1.  A context that enables only one of the two makes o 1 or 0. */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
+    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
+    bool inside; float o = mask_opacity(B, in, inside);
+    const uint32_t null_index = mask_null_index(S, B);
+    if (CTX) {
+        const bool transmission = ctx.is_enabled(LOBE_NULL, null_index), nested = ctx.component == 0xffffffffu || ctx.component < null_index;
+        if (!transmission && !nested) return;
+        if (transmission != nested) o = transmission ? 1.f : 0.f;
+    }
+    if (s1 < o) {
+        BsdfSide ns;
+        if (!bsdf_side(S, B.pad, wi, ns)) return;
+        const DBsdf &N = S.bsdfs[ns.index];
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        bsdf_sample_one<LEAF, CTX>(N, nin, ns.wi, s1 / o, s2x, s2y, bs, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
+        bs.wo.z *= ns.wo_sign; bs.pdf *= o;
+        return;
+    }
+    bs.wo = Vec3(-wi.x, -wi.y, -wi.z); bs.pdf = 1.f - o; bs.weight = Vec3(1.f); bs.eta = 1.f; bs.delta = true; bs.type = LOBE_NULL; bs.comp = null_index;
+}
+
+/* (u, v): the vertex's texture coordinates -- read only by the kernels of blend / mask scenes, whose nested records look up their own colour inputs there */
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx(), float u = 0.f, float v = 0.f,
                           BlendChildGrad *cg = nullptr) {
@@ -480,8 +540,12 @@ HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInput
         blend_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
         return;
     }
+    if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) {
+        mask_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        return;
+    }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
-    bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_BLEND), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
+    bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_COMPOSITE), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
 }
 /* d value / d {alpha, eta, k} of the record serving this side (see bsdf_eval_extra_one) */
 HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEvalExtra &x) {
@@ -493,7 +557,8 @@ HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs 
                         float u = 0.f, float v = 0.f) {
     if (!side_ok) { bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u; return; }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
-    else bsdf_sample_one<(TYPES & ~HAR_SCENE_BLEND), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
+    else if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) mask_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
+    else bsdf_sample_one<(TYPES & ~HAR_SCENE_COMPOSITE), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
     bs.wo.z *= side.wo_sign;
 }
 

@@ -205,6 +205,7 @@ bool scene_set_bsdf_params_host(HostScene &hs, uint32_t index, const HarBSDF &in
     if (index >= hs.bsdfs.size()) { err = "invalid bsdf index"; return false; }
     DBsdf &b = hs.bsdfs[index];
     if (b.type == BSDF_BLEND) { err = "blendbsdf: the record has no parameter besides its weight (slot 0)"; return false; }
+    if (b.type == BSDF_MASK) { err = "mask: the record has no parameter besides its opacity (slot 0)"; return false; }
     for (float v : { in.alpha_u, in.alpha_v, in.eta, in.eta_c[0], in.eta_c[1], in.eta_c[2], in.k_c[0], in.k_c[1], in.k_c[2], in.reflectance2[0], in.reflectance2[1], in.reflectance2[2] })
         if (!std::isfinite(v)) { err = "BSDF parameter is not finite"; return false; }
     const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
@@ -339,9 +340,11 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.bsdf_count; ++i) {
         const HarBSDF &b = d.bsdfs[i];
-        if (b.type > BSDF_BLEND) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf and twosided are implemented in hip_ad_rgb)"; return false; }
+        if (b.type > BSDF_MASK) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask and twosided are implemented in hip_ad_rgb)"; return false; }
         if (b.texture >= (int32_t) d.texture_count) { err = "BSDF references a texture that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
+        /* ... and BSDFFlags::Null is part of BSDFFlags::Transmission: `twosided` over a `mask`, on either side */
+        if ((b.flags & BF_TWOSIDED) && (b.type == BSDF_MASK || (b.back >= 0 && d.bsdfs[b.back].type == BSDF_MASK))) { err = "twosided over `mask`: Only materials without a transmission component can be nested!"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
         if ((b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC) && !(b.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
         if (b.type == BSDF_ROUGHPLASTIC && b.eta == 1.f) { err = "The interior and exterior indices of refraction must be positive and differ!"; return false; }
@@ -357,11 +360,27 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 if (b.nested[k] < 0 || b.nested[k] >= (int32_t) d.bsdf_count) { err = "blendbsdf: a nested BSDF index is out of range"; return false; }
             for (int k = 0; k < 2; ++k) {
                 const HarBSDF &c = d.bsdfs[b.nested[k]];
+                if (c.type == BSDF_MASK) { err = "blendbsdf: a nested `mask` BSDF is not supported (put the `mask` outside, over plain BSDF models)"; return false; }
                 if (c.type >= BSDF_TYPE_COUNT || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
                 if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
                 if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_BLEND_SMOOTH;
             }
             db.table = b.nested[0]; db.pad = (uint32_t) b.nested[1];
+        } else if (b.type == BSDF_MASK) {                   /* MaskBSDF (mask.cpp:93-114): one nested record, named by index; it may be a `twosided` (one BSDF or a pair) */
+            db.flags &= BF_MONO;
+            if (b.nested[0] < 0 || b.nested[0] >= (int32_t) d.bsdf_count) { err = "mask: the nested BSDF index is out of range"; return false; }
+            const HarBSDF &c = d.bsdfs[b.nested[0]];
+            if (c.type == BSDF_BLEND) { err = "mask: unsupported BSDF type of the nested record: a nested `blendbsdf` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
+            if (c.type == BSDF_MASK) { err = "mask: unsupported BSDF type of the nested record: a nested `mask` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
+            if (c.type >= BSDF_TYPE_COUNT) { err = "mask: unsupported BSDF type of the nested record"; return false; }
+            if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
+            if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
+                if (c.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
+                const HarBSDF &k = d.bsdfs[c.back];
+                if (k.type >= BSDF_TYPE_COUNT) { err = "mask: the back side of a nested `twosided` must be a plain BSDF model (a `blendbsdf` or `mask` there is not supported)"; return false; }
+                if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
+            }
+            db.pad = (uint32_t) b.nested[0];
         } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH);
         hs.bsdfs.push_back(db);
         if (b.type == BSDF_ROUGHPLASTIC) { build_roughplastic_tables(hs, i); update_roughplastic_sampling_weight(hs, i); }
