@@ -111,6 +111,17 @@ typedef struct HarBSDF {
 /* to_uv: the `to_uv` property of BitmapTexture (bitmap.cpp:175), a 2-D affine map applied to the surface's uv before every lookup (`uv = m_transform * si.uv`,
  * bitmap.cpp:565,792,831,847): row-major 2 x 3, { m00, m01, m02, m10, m11, m12 } -> u' = fma(m01, v, fma(m00, u, m02)), v' likewise (AffineTransform * Point,
  * include/mitsuba/core/transform.h:322-335).  Six zeros (a zero-initialised record) mean the identity. */
+/* HAR_TEX_MESH_ATTRIBUTE: the record is not a bitmap but the `mesh_attribute` texture (src/textures/mesh_attribute.cpp) of ONE mesh -- Mesh::eval_attribute
+ * (src/render/mesh.cpp:2464-2631) of a per-vertex or, with HAR_TEX_ATTRIBUTE_PER_FACE, per-face attribute.  `data` = height rows of three floats (width = 1; an attribute of
+ * one channel is stored three times, as a one-channel bitmap is), height = the vertex / face count of mesh `reserved` (an index into HarSceneDesc::meshes, a top-level
+ * mesh: har_scene_create checks both), to_uv[0] = `scale`; no filter / wrap bits.  A vertex attribute is fmadd(a0, b0, fmadd(a1, b1, a2 * b2)) * scale with (b0, b1, b2) =
+ * Mesh::barycentric_coordinates(si) (mesh.cpp:2227-2251, the least-squares solve on si.p); a face attribute is the row of si.prim_index.  The record may be slot 0 of any
+ * BSDF record that ONLY mesh `reserved` carries (directly, as a back side, nested in a blend / mask): one record per (BSDF, shape) pair.  Updates: har_scene_set_texture /
+ * _device (rows x 3 floats), har_scene_set_texture_to_uv (to_uv[0] = the new scale).  Gradients (`prb`): into the record's entry of `grad_textures` (rows x 3), d / d row =
+ * b_k * scale; every backward pass of such a scene takes the replay-cache route with the in-place commit (max_depth <= 12; no vertex-position / instance / alpha / eta / k
+ * gradients; har_render_forward under the same two conditions).  Emitters cannot read such a record; har_bsdf_* (which see a uv, not a hit) are refused for a scene that holds one. */
+#define HAR_TEX_MESH_ATTRIBUTE     8u
+#define HAR_TEX_ATTRIBUTE_PER_FACE 16u
 typedef struct HarTexture { const float *data; uint32_t width, height; uint32_t mode, reserved; float to_uv[6]; } HarTexture;
 
 /* type 0: AreaLight on a Rectangle (src/emitters/area.cpp, src/shapes/rectangle.cpp:108-179);
@@ -677,6 +688,10 @@ int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSD
                            const uint8_t *active, float *value, float *pdf);
 int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
                          const float *sample2, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component);
+/* The lookup of HAR_TEX_MESH_ATTRIBUTE record `texture` and its transpose on the HOST (no GPU), by the per-lane code of the kernels: n hits on the record's mesh, face prim[i]
+ * at the point p (3 x n).  value (3 x n, may be NULL) = the colour looked up; g (3 x n) with grad (rows x 3, ACCUMULATED into; both or neither) = the deposit of the adjoint:
+ * grad[row_k] += g * b_k * scale over the lookup's three rows (a face attribute: its one row).  All pointers HOST. */
+int har_attribute_lookup_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const uint32_t *prim, const float *p, float *value, const float *g, float *grad);
 /* The AOV pass of AOVIntegrator::render (aov.cpp:389-470: one more SamplingIntegrator pass with the same sampler seed): lanes [lane_begin, lane_end) (0, 0 = all) of the
  * wavefront of render() at `seed` / `spp` -- the same lanes, film positions and camera rays as there -- accumulate into `aov_film` (DEVICE, H x W x (C + 1): the C
  * channels, then the reconstruction filter's weight; accumulated, not cleared, not developed).  `integrator` gives the chunk size (chunk_lanes) and the film window
@@ -738,6 +753,18 @@ int har_mesh_transform(const float to_world[32], uint32_t vertex_count, float *v
  * ---------------------------------------------------------------------- */
 typedef struct HarMeshData { float *vertices; uint32_t *faces; uint32_t vertex_count, face_count, flags, reserved; } HarMeshData;
 int  har_mesh_load_ply(const char *filename, int face_normals, int flip_tex_coords, const float *to_world /*[32] or NULL*/, int flip_normals, HarMeshData *out);
+/* ... and the file's OTHER per-vertex / per-face properties, from which PLYMesh forms the mesh attributes (find_other_fields, src/shapes/ply.h:272-422; `vertex_color`,
+ * `face_<prefix>`, ...): every scalar (non-list) property of the vertex and of the face element in file order, one float per value (integers converted without rescaling),
+ * row-major vertex_count x vertex_cols / face_count x face_cols, in the order of the records of `out` (the loader neither welds nor re-orders; a flipped winding only
+ * permutes a face's indices).  *_names: one line "<f|i>:<property name>" per column (f: a float / double property, i: an integer one).  The grouping into attributes is the
+ * caller's (mitsuba3_amd.core.Mesh.from_ply).  All four buffers are malloc'ed: har_mesh_fields_free. */
+typedef struct HarMeshFields { char *vertex_names, *face_names; float *vertex_data, *face_data; uint32_t vertex_cols, face_cols; } HarMeshFields;
+int  har_mesh_load_ply_fields(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out, HarMeshFields *fields);
+void har_mesh_fields_free(HarMeshFields *fields);
+/* har_mesh_load_serialized + the custom attributes of a version-5 sub-mesh (Mesh::write_serialized, src/render/mesh.cpp:1091-1148) in the same structure, laid out per
+ * ATTRIBUTE: *_names hold one line "<attribute name>:<dim>" per attribute, *_data their (rows x dim) arrays back to back in that order, *_cols the number of attributes;
+ * per-vertex attributes in the vertex_* members, 'face_*' ones in the face_* members.  Versions 3 and 4 have none. */
+int  har_mesh_load_serialized_fields(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out, HarMeshFields *fields);
 /* OBJMesh ctor (src/shapes/obj.cpp:98-296) + Mesh::from_corners (src/render/mesh_utils.cpp:210-560): polygons are fan-triangulated,
  * corners of a point weld when normal / texcoord / UV-orientation agree; missing normals are regenerated per surface point */
 int  har_mesh_load_obj(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out);

@@ -50,6 +50,10 @@ class HarMeshData(C.Structure):
     _fields_ = [("vertices", f32p), ("faces", u32p), ("vertex_count", C.c_uint32), ("face_count", C.c_uint32), ("flags", C.c_uint32), ("reserved", C.c_uint32)]
 
 
+class HarMeshFields(C.Structure):
+    _fields_ = [("vertex_names", C.c_void_p), ("face_names", C.c_void_p), ("vertex_data", f32p), ("face_data", f32p), ("vertex_cols", C.c_uint32), ("face_cols", C.c_uint32)]
+
+
 class HarImage(C.Structure):
     _fields_ = [("data", f32p), ("width", C.c_uint32), ("height", C.c_uint32), ("channels", C.c_uint32), ("reserved", C.c_uint32)]
 
@@ -153,6 +157,10 @@ SIGNATURES = {
     "har_integrator_set_packet_tracing": (C.c_int, [vp, C.c_int]),
     "har_integrator_set_top_seed": (C.c_int, [vp, C.c_int]),
     "har_mesh_load_ply": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp]),
+    "har_mesh_load_ply_fields": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp, vp]),
+    "har_mesh_fields_free": (None, [vp]),
+    "har_attribute_lookup_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, vp, f32p, f32p, f32p, f32p]),
+    "har_mesh_load_serialized_fields": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp, vp]),
     "har_mesh_load_obj": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp]),
     "har_mesh_load_serialized": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp]),
     "har_mesh_compute_normals": (C.c_int, [C.c_uint32, vp, C.c_uint32, vp]),

@@ -344,6 +344,40 @@ class Mesh:
         self.name = name
         self.V = np.zeros((0, 8), np.float32); self.F = np.zeros((0, 4), np.uint32); self.flags = 0
         self.bsdf = None; self.emitter = None
+        self.attributes = {}          # Mesh::m_mesh_attributes: name -> float32 (rows, dim), one row per vertex ('vertex_*') or per face ('face_*')
+
+    # -- mesh attributes (Mesh::add_attribute / remove_attribute / has_attribute / attribute, src/render/mesh.cpp:2538-2601).  `to_world` and `flip_normals` leave them alone.
+    def add_attribute(self, name, values):
+        name = str(name)
+        if name in self.attributes:
+            raise RuntimeError("add_attribute(): attribute \"%s\" already exists." % name)
+        vertex = name.startswith("vertex_")
+        if not vertex and not name.startswith("face_"):
+            raise RuntimeError("add_attribute(): attribute name must start with either \"vertex_\" or \"face_\".")
+        if hasattr(values, 'detach'):
+            values = values.detach().cpu().numpy()
+        values = np.asarray(values, np.float32)
+        rows = self.vertex_count() if vertex else self.face_count()
+        if values.ndim != 2 or values.shape[0] != rows:
+            raise RuntimeError("add_attribute(): attribute \"%s\": expected a (%d, dim) tensor with one row per %s." % (name, rows, "vertex" if vertex else "face"))
+        dim = values.shape[1]
+        if dim == 0 or dim > 4:
+            raise RuntimeError("add_attribute(): attribute \"%s\": 1 to 4 channels are supported, got %d." % (name, dim))
+        self.attributes[name] = np.ascontiguousarray(values, np.float32).copy()
+        return self
+
+    def remove_attribute(self, name):
+        if name not in self.attributes:
+            raise RuntimeError("remove_attribute(): attribute \"%s\" doesn't exist." % name)       # (Shape::remove_attribute: this variant has no texture attributes on shapes)
+        del self.attributes[name]
+
+    def has_attribute(self, name):
+        return name in self.attributes
+
+    def attribute(self, name):
+        if name not in self.attributes:
+            raise RuntimeError("attribute(): attribute \"%s\" doesn't exist." % name)
+        return self.attributes[name]
 
     def from_fields(self, faces, positions, normals=None, texcoords=None):
         positions = _f32(positions).reshape(-1, 3)
@@ -375,9 +409,25 @@ class Mesh:
     def from_ply(self, filename, face_normals=False, flip_tex_coords=False, to_world=None, flip_normals=False):
         """PLYMesh (src/shapes/ply.cpp): parsed by the C++ host library into the packed layout; `to_world` / `flip_normals` are
         baked before missing normals are regenerated, as PackedMesh::set_transform does (mesh_utils.cpp:33-44)."""
-        md = _capi.HarMeshData()
-        check(lib().har_mesh_load_ply(str(filename).encode(), int(bool(face_normals)), int(bool(flip_tex_coords)), self._tw(to_world), int(bool(flip_normals)), C.byref(md)))
-        return self._adopt(md)
+        md = _capi.HarMeshData(); fields = _capi.HarMeshFields()
+        check(lib().har_mesh_load_ply_fields(str(filename).encode(), int(bool(face_normals)), int(bool(flip_tex_coords)), self._tw(to_world), int(bool(flip_normals)), C.byref(md),
+                                             C.byref(fields)))
+        try:
+            nv, nf = int(md.vertex_count), int(md.face_count)
+            groups = []
+            for prefix, names, data, cols, rows in (("vertex_", fields.vertex_names, fields.vertex_data, int(fields.vertex_cols), nv), ("face_", fields.face_names, fields.face_data, int(fields.face_cols), nf)):
+                cols_named = [ln.split(":", 1) for ln in C.string_at(names).decode().split("\n") if ln] if names else []
+                table = np.ctypeslib.as_array(data, shape=(max(rows * cols, 1), ))[:rows * cols].reshape(rows, cols).copy() if rows * cols else np.zeros((rows, cols), np.float32)
+                reserved = ("x", "y", "z", "nx", "ny", "nz", "u", "v") if prefix == "vertex_" else ()
+                for name, idx in _ply_other_fields(prefix, [(n, t == "f") for t, n in cols_named], reserved, str(filename)):
+                    groups.append((name, np.ascontiguousarray(table[:, idx], np.float32)))
+        finally:
+            lib().har_mesh_fields_free(C.byref(fields))
+        self._adopt(md)
+        self.attributes = {}
+        for name, values in groups:          # PLYMesh: pm.add_attribute(descr.name, descr.dim) (ply.cpp:259-262, 308-311); rows in the order of the vertex / face records
+            self.add_attribute(name, values)
+        return self
 
     def from_obj(self, filename, face_normals=False, flip_tex_coords=True, to_world=None, flip_normals=False):
         """OBJMesh (src/shapes/obj.cpp) + Mesh::from_corners (mesh_utils.cpp:210-560)"""
@@ -387,10 +437,27 @@ class Mesh:
 
     def from_serialized(self, filename, shape_index=0, face_normals=None, to_world=None, flip_normals=False):
         """SerializedMesh (src/shapes/serialized.cpp), container versions 3, 4 and 5; face_normals=None: the property is unset (a v5 file's own flag applies)"""
-        md = _capi.HarMeshData()
+        md = _capi.HarMeshData(); fields = _capi.HarMeshFields()
         fn = -1 if face_normals is None else int(bool(face_normals))
-        check(lib().har_mesh_load_serialized(str(filename).encode(), int(shape_index), fn, self._tw(to_world), int(bool(flip_normals)), C.byref(md)))
-        return self._adopt(md)
+        check(lib().har_mesh_load_serialized_fields(str(filename).encode(), int(shape_index), fn, self._tw(to_world), int(bool(flip_normals)), C.byref(md), C.byref(fields)))
+        try:
+            groups = []
+            for names, data, rows in ((fields.vertex_names, fields.vertex_data, int(md.vertex_count)), (fields.face_names, fields.face_data, int(md.face_count))):
+                at = 0
+                for ln in (C.string_at(names).decode().split("\n") if names else []):
+                    if not ln:
+                        continue
+                    name, dim = ln.rsplit(":", 1); dim = int(dim)
+                    n = rows * dim
+                    vals = np.ctypeslib.as_array(data, shape=(max(at + n, 1), ))[at:at + n].reshape(rows, dim).copy() if n else np.zeros((rows, dim), np.float32)
+                    groups.append((name, vals)); at += n
+        finally:
+            lib().har_mesh_fields_free(C.byref(fields))
+        self._adopt(md)
+        self.attributes = {}
+        for name, values in groups:          # the custom attributes of a version-5 file (SerializedMesh::load_v5 -> add_attribute)
+            self.add_attribute(name, values)
+        return self
 
     def recompute_vertex_normals(self):
         """Mesh::compute_normals (src/render/mesh.cpp:1218-1267)"""
@@ -415,6 +482,93 @@ class Mesh:
 # `silhouette_sampling_weight` only feeds the projective integrators' boundary sampling: queried, no effect on `path` / `prb`.
 _SHAPE_PROPS = ('to_world', 'flip_normals', 'face_normals', 'silhouette_sampling_weight')
 _SHAPE_CHILDREN = ('bsdf', 'emitter')       # Shape(props) (shape.cpp:22-49) also takes sensors, media and texture attributes: not part of this variant, refused
+
+
+def _ply_other_fields(prefix, fields, reserved, filename):
+    """find_other_fields (src/shapes/ply.h:272-422): the attributes PLYMesh forms from the properties of an element that are not positions, normals, texcoords or indices.
+    `fields` = [(property name, is float)] in file order -> [(attribute name, [column indices])].  `r g b [a]` / `red green blue [alpha]` become `<prefix>color` (3 or 4
+    fields); contiguous runs `<p>_{x,y,z,w | r,g,b,a | 0,1,2,3 | 1,2,3,4}` become `<prefix><p>` (`<prefix><p>_color` for the r g b a scheme) when they have 1 or 3 fields,
+    and are dropped with a warning otherwise.  Integer fields are converted to float without rescaling (a warning, as there)."""
+    names = [n for n, _ in fields]
+    if prefix == "vertex_":            # ply.cpp:238-246: texture_u / texture_v, or s / t, are the texcoords
+        if "texture_u" in names and "texture_v" in names:
+            names = ["u" if n == "texture_u" else "v" if n == "texture_v" else n for n in names]
+        elif "s" in names and "t" in names:
+            names = ["u" if n == "s" else "v" if n == "t" else n for n in names]
+    if not ("r" in names and "g" in names and "b" in names) and "red" in names and "green" in names and "blue" in names:
+        ren = {"red": "r", "green": "g", "blue": "b"}
+        if "alpha" in names:
+            ren["alpha"] = "a"
+        names = [ren.get(n, n) for n in names]
+    out = []
+    if "r" in names and "g" in names and "b" in names:
+        idx = [names.index(c) for c in ("r", "g", "b")] + ([names.index("a")] if "a" in names else [])
+        out.append((prefix + "color", idx))
+        if not fields[idx[0]][1]:
+            warnings.warn("\"%s\": Mesh attribute \"%s\" has integer fields: color attributes are expected to be in the [0, 1] range." % (filename, prefix + "color"))
+    reserved = set(reserved) | {"r", "g", "b", "a"}
+    if prefix == "face_":
+        reserved |= {"vertex_index.count", "vertex_indices.count", "i0", "i1", "i2"}
+    postfixes = ("xr01", "yg12", "zb23", "wa34")
+    seen = set(); state = dict(prefix="", scheme=0, level=0, reading=False, cols=[], is_float=True)
+
+    def ignore():
+        state.update(prefix="", scheme=0, level=0, reading=False, cols=[])
+
+    def flush():
+        if state["level"] not in (1, 3):
+            warnings.warn("\"%s\": attribute must have either 1 or 3 fields (had %d) : attribute \"%s\" ignored" % (filename, state["level"], prefix + state["prefix"]))
+            ignore(); return
+        if not state["is_float"] and state["level"] == 3:
+            warnings.warn("\"%s\": attribute \"%s\" has integer fields: color attributes are expected to be in the [0, 1] range." % (filename, prefix + state["prefix"]))
+        out.append((prefix + state["prefix"] + ("_color" if state["scheme"] == 1 else ""), list(state["cols"])))
+        seen.add(state["prefix"]); ignore()
+
+    i = 0; n = len(names)
+    while i < n:
+        name = names[i]
+        if name in reserved:
+            i += 1; continue
+        state["is_float"] = fields[i][1]
+        pos = name.rfind("_")
+        if pos < 0:
+            warnings.warn("\"%s\": attributes without postfix are not handled for now: attribute \"%s\" ignored." % (filename, name))
+            if state["reading"]:
+                flush()
+            i += 1; continue
+        post = name[pos + 1:]
+        if len(post) != 1:
+            warnings.warn("\"%s\": attribute postfix can only be one letter long." % filename)
+            if state["reading"]:
+                flush()
+            i += 1; continue
+        pre = name[:pos]
+        if state["reading"] and pre != state["prefix"]:
+            flush()
+        if not state["reading"] and pre in seen:
+            warnings.warn("\"%s\": attribute prefix has already been encountered: attribute \"%s\" ignored." % (filename, name))
+            while i < n and names[i].startswith(pre):
+                i += 1
+            if i == n:
+                break
+            i += 1; continue           # (the reference's loop increment skips the field it stopped at)
+        if not state["reading"]:
+            if post not in postfixes[0]:
+                warnings.warn("\"%s\": attribute can't start with postfix %s." % (filename, post))
+                i += 1; continue
+            state.update(reading=True, scheme=postfixes[0].index(post), prefix=pre, cols=[])
+        elif state["level"] >= 4 or post != postfixes[state["level"]][state["scheme"]]:
+            warnings.warn("\"%s\": attribute postfix sequence is invalid: attribute \"%s\" ignored." % (filename, state["prefix"]))
+            ignore()
+            while i < n and names[i].startswith(pre):
+                i += 1
+            if i == n:
+                break
+        state["level"] += 1; state["cols"].append(i)
+        i += 1
+    if state["reading"]:
+        flush()
+    return out
 
 
 def _rectangle(props):
@@ -446,7 +600,7 @@ _PLUGIN_KINDS = {
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
-    'rgb': 'texture', 'bitmap': 'texture',
+    'rgb': 'texture', 'bitmap': 'texture', 'mesh_attribute': 'texture',
 }
 _ALL_KINDS = tuple(sorted(set(_PLUGIN_KINDS.values())))
 
@@ -1049,6 +1203,21 @@ def _bitmap_from_props(refl):
     return np.ascontiguousarray(t, np.float32), tex_mode, tex_to_uv
 
 
+def _mesh_attribute_from_props(refl):
+    """MeshAttribute(props) (src/textures/mesh_attribute.cpp:79-86) -> (name, scale).  The attribute itself belongs to the SHAPE that is hit (si.shape->eval_attribute):
+    it is bound when a shape that carries the BSDF joins a scene (Scene._bind_attributes)"""
+    _check_props('mesh_attribute', refl, ('name', 'scale'), free_children=False)
+    if 'name' not in refl:
+        raise RuntimeError("Property \"name\" has not been specified!")
+    name = str(refl['name'])
+    if "vertex_" not in name and "face_" not in name:
+        raise RuntimeError("Invalid mesh attribute name: must be start with either \"vertex_\" or \"face_\" but was \"%s\"." % name)
+    scale = float(np.float32(refl.get('scale', 1.0)))
+    if not math.isfinite(scale):
+        raise RuntimeError("mesh_attribute: `scale` must be finite")
+    return name, scale
+
+
 class _RecordFlags(int):
     """BlendBSDF.flags: an int (the record's flag word, as on every BSDF) that answers BSDF::flags() / BSDF::flags(i) when called"""
 
@@ -1079,13 +1248,17 @@ class BSDF:
         if isinstance(refl, (int, float)):
             refl = {'type': 'rgb', 'value': [refl] * 3}
         self.texture = None; self.tex_mode = 0; self.tex_to_uv = None
+        self.attr = None; self.attr_mesh = None          # slot 0 is a `mesh_attribute`: (name, scale), and the scene's mesh it was bound to
         if refl['type'] == 'rgb':
             self.value = _rgb_value(refl, def0)
         elif refl['type'] == 'bitmap':
             self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(refl)
             self.value = _f32([0.5, 0.5, 0.5])
+        elif refl['type'] == 'mesh_attribute':
+            self.attr = _mesh_attribute_from_props(refl)
+            self.value = _f32([0.5, 0.5, 0.5])
         else:
-            raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb (textures: rgb, bitmap)" % refl['type'])
+            raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb (textures: rgb, bitmap, mesh_attribute)" % refl['type'])
         self.value2 = _rgb_value(props.get(slot1[0]), slot1[1]) if slot1 else _f32([0, 0, 0])
         self.flags = 0; self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
         self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
@@ -1214,8 +1387,13 @@ class BlendBSDF(BSDF):
     def __init__(self, weight, nested, id=None):
         self.id = id; self.kind = self._plugin; self.slot0_name = self._weight_name; self.slot1_name = None
         self.texture = None; self.tex_mode = 0; self.tex_to_uv = None; self.weight_channels = 0
+        self.attr = None; self.attr_mesh = None
         if isinstance(weight, (int, float)) and not isinstance(weight, bool):
             self.value = _f32([float(weight)] * 3)
+        elif isinstance(weight, dict) and weight.get('type') == 'mesh_attribute':
+            # Texture::eval_1 of a mesh attribute (Mesh::eval_attribute_1, mesh.cpp:2619-2624): the value of a one-channel attribute, 0 for any other
+            self.attr = _mesh_attribute_from_props(weight); self.weight_channels = 1
+            self.value = _f32([0.5, 0.5, 0.5])
         elif isinstance(weight, dict) and weight.get('type') == 'bitmap':
             self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(weight)
             src = weight['data'] if 'data' in weight else (weight['bitmap'].data if isinstance(weight.get('bitmap'), Bitmap) else Bitmap(weight['filename']).data)
@@ -1225,7 +1403,7 @@ class BlendBSDF(BSDF):
             self.weight_channels = ch
             self.value = _f32([0.5, 0.5, 0.5])
         else:
-            raise RuntimeError("%s: `%s` is a float or a `bitmap` texture" % (self._plugin, self._weight_name))
+            raise RuntimeError("%s: `%s` is a float, a `bitmap` or a `mesh_attribute` texture" % (self._plugin, self._weight_name))
         self.value2 = _f32([0, 0, 0]); self.flags = 16 if self.weight_channels == 1 else 0          # (16: slot 0 is a one-channel bitmap, read channel 0)
         self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
         self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
@@ -1430,6 +1608,8 @@ class SpotLight:
         _check_props("spot", props, ('to_world', 'intensity', 'cutoff_angle', 'beam_width', 'texture', 'sampling_weight'), free_children=False)
         self.sampling_weight = _sampling_weight(props)
         if 'texture' in props:
+            if isinstance(props['texture'], dict) and props['texture'].get('type') == 'mesh_attribute':
+                raise RuntimeError("spot: a `mesh_attribute` as property \"texture\" is not implemented by hip_ad_rgb")
             raise RuntimeError("spot: property \"texture\" is not implemented by hip_ad_rgb")
         self.to_world = props.get('to_world', ScalarTransform4f())
         self.intensity = _rgb_value(props.get('intensity', {'type': 'rgb', 'value': 1.0}), 1.0, bounded=False, uniform='intensity')      # get_emissive_texture("intensity", 1.f), :93
@@ -1822,8 +2002,8 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
     w, h = sensor.film().crop_size()
     if tangents is None:
         tangents = {k: v.grad for k, v in (params or {}).items() if getattr(v, 'requires_grad', False) and getattr(v, 'grad', None) is not None}
-    keys = scene._param_keys()
-    unknown = [k for k in tangents if k not in keys]
+    keys = scene._param_keys(); akeys = scene._attr_keys()
+    unknown = [k for k in tangents if k not in keys and k not in akeys]
     if unknown:
         raise RuntimeError("render_forward(): %s are not differentiable parameters of the `prb` forward mode (available: %s)" % (unknown, sorted(keys)))
     t_refl = torch.zeros((max(1, len(scene.bsdfs)), 3), dtype=torch.float32, device=dev)
@@ -1831,6 +2011,20 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
     t_emit = torch.zeros((max(1, len(scene.emitters)), 3), dtype=torch.float32, device=dev)
     any_emit = False
     for k, v in tangents.items():
+        if k in akeys:
+            # the tangent of a mesh attribute, in the rows x 1 x 3 layout of every record that reads it (one channel: stored three times; what evaluates to 0: none)
+            mesh, name = akeys[k]; rows, dim = scene.meshes[mesh]["attributes"][name].shape
+            v = torch.as_tensor(v, dtype=torch.float32, device=dev)
+            if tuple(v.shape) != (rows, dim):
+                raise RuntimeError("render_forward(): %s: expected a tangent of shape %s" % (k, (rows, dim)))
+            for b in scene._attr_readers(mesh, name):
+                if id(b) in scene._blend_nested():
+                    raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` are not produced in hip_ad_rgb (the weight's / opacity's are; use render_backward)" % k)
+                if dim == 1:
+                    t_tex[b.tex_index].copy_(v.expand(rows, 3).reshape(rows, 1, 3))
+                elif dim == 3 and b.kind not in _WEIGHTED_BSDFS:
+                    t_tex[b.tex_index].copy_(v.reshape(rows, 1, 3))
+            continue
         kind, b = keys[k]
         v = torch.as_tensor(v, dtype=torch.float32, device=dev)
         if kind != "emit" and id(b) in scene._blend_nested():
@@ -2112,6 +2306,8 @@ class Scene:
         self.groups = []; self.instances = []; self.instance_keys = []; self.emitters = []
         self.m_sensors = []; self.sensor_keys = []; self.m_integrator = None; self.textures = []; self.texture_modes = []; self.texture_to_uv = []
         self._h = None; self._keep = []
+        self._attr_tex = {}           # texture index -> (mesh index, attribute name, BSDF): the `mesh_attribute` records, one per (BSDF, shape) pair
+        self._device_attrs = {}       # (mesh index, name) -> device tensor: attribute values params.update() pushed device-to-device (sync_host refreshes the mirrors)
         self._device_values = {}      # (kind, index) -> (device tensor, record): values params.update() pushed device-to-device; the numpy mirrors are refreshed by sync_host()
         named = {}
         shapes = []; groups = []; insts = []
@@ -2162,6 +2358,7 @@ class Scene:
         for key, m in shapes:
             self._add_mesh(key, m)
         self.top_mesh_count = len(self.meshes)
+        self._in_group = True
         gindex = {}
         for key, g in groups:
             first = len(self.meshes)
@@ -2181,6 +2378,8 @@ class Scene:
     def _add_bsdf(self, b):
         if b.scene is self:
             return b.index
+        if getattr(b, 'attr', None) is not None:          # a `mesh_attribute` is bound per scene (Scene._bind_attributes): nothing of another scene's binding stays
+            b.texture = None; b.attr_mesh = None
         b.scene = self; b.index = len(self.bsdf_objs)
         if b.texture is not None:
             b.tex_index = len(self.textures); self.textures.append(b.texture); self.texture_modes.append(b.tex_mode); self.texture_to_uv.append(b.tex_to_uv)
@@ -2224,7 +2423,55 @@ class Scene:
             else:                         # any other triangle mesh: Mesh::sample_position (area-weighted face selection)
                 self.emitters[em] = dict(type=3, mesh=len(self.meshes), radiance=m.emitter, to_world=[0.0] * 12, normal=[0.0] * 3, inv_area=0.0,
                                          sampling_weight=getattr(m, 'emitter_weight', 1.0))
-        self.meshes.append(dict(key=key, V=np.ascontiguousarray(m.V), F=np.ascontiguousarray(m.F), bsdf=bi, emitter=em, flags=m.flags, rect=getattr(m, 'rect', None)))
+        attrs = {k: np.ascontiguousarray(v, np.float32).copy() for k, v in getattr(m, 'attributes', {}).items()}
+        self._bind_attributes(key, m.bsdf, attrs, len(self.meshes))
+        self.meshes.append(dict(key=key, V=np.ascontiguousarray(m.V), F=np.ascontiguousarray(m.F), bsdf=bi, emitter=em, flags=m.flags, rect=getattr(m, 'rect', None), attributes=attrs))
+
+    @staticmethod
+    def _bsdf_tree(b):
+        """the BSDF objects a shape's BSDF evaluates: itself, the back side of a `twosided`, the BSDFs nested in a blend / mask (and their back sides)"""
+        out = []; todo = [b]
+        while todo:
+            x = todo.pop(0)
+            if x is None or any(x is y for y in out):
+                continue
+            out.append(x); todo.extend(getattr(x, 'nested', ())); todo.append(getattr(x, 'back', None))
+        return out
+
+    @staticmethod
+    def _attr_rows(b, values):
+        """the rows x 1 x 3 record of a `mesh_attribute` in slot 0 of BSDF `b`.  A colour (Texture::eval -> Mesh::eval_attribute, mesh.cpp:2603-2617): one channel is
+        broadcast, three are the colour, anything else is 0.  A blend weight / mask opacity (eval_1, :2619-2624): the value of a one-channel attribute, else 0."""
+        v = np.asarray(values, np.float32); rows, dim = v.shape
+        if dim == 1:
+            t = np.repeat(v, 3, axis=1)
+        elif dim == 3 and b.kind not in _WEIGHTED_BSDFS:
+            t = v
+        else:
+            t = np.zeros((rows, 3), np.float32)
+        return np.ascontiguousarray(t.reshape(rows, 1, 3), np.float32)
+
+    def _bind_attributes(self, key, bsdf, attrs, mesh_index):
+        """The attribute a `mesh_attribute` texture reads belongs to the shape that was hit (mesh_attribute.cpp:94-107: si.shape->eval_attribute): every BSDF of this
+        shape's tree that holds one gets a texture record of THIS shape's rows.  A BSDF object carries one record, so a BSDF with such a texture that several shapes
+        share is refused by name (docs/widening.md); a shape without the attribute is an error here, not a zero at render time."""
+        for b in self._bsdf_tree(bsdf):
+            if getattr(b, 'attr', None) is None:
+                continue
+            name, scale = b.attr
+            who = self._bsdf_key_base(b) if b.id or b.index is not None else b.kind
+            if getattr(self, '_in_group', False):
+                raise RuntimeError("mesh_attribute: shape \"%s\" lies inside a shapegroup -- a `mesh_attribute` texture (\"%s\", BSDF \"%s\") on an instanced mesh is not supported in hip_ad_rgb" % (key, name, who))
+            if b.attr_mesh is not None:
+                raise RuntimeError("mesh_attribute: BSDF \"%s\" reads the attribute \"%s\" of the shape it is on, and the shapes \"%s\" and \"%s\" share it -- not supported in "
+                                   "hip_ad_rgb: give every shape a BSDF of its own" % (who, name, self.meshes[b.attr_mesh]["key"], key))
+            if name not in attrs:
+                raise RuntimeError("mesh_attribute: shape \"%s\" has no attribute \"%s\" (read by BSDF \"%s\"); it has %s" % (key, name, who, sorted(attrs) or "none"))
+            self._add_bsdf(b)          # (already a record of this scene: Scene._add_mesh added the shape's whole tree, without a texture)
+            b.attr_mesh = mesh_index
+            b.texture = self._attr_rows(b, attrs[name]); b.tex_mode = 8 | (0 if name.startswith("vertex_") else 16); b.tex_to_uv = [scale, 0.0, 0.0, 0.0, 0.0, 0.0]
+            b.tex_index = len(self.textures); self.textures.append(b.texture); self.texture_modes.append(b.tex_mode); self.texture_to_uv.append(b.tex_to_uv)
+            self._attr_tex[b.tex_index] = (mesh_index, name, b)
 
     def sync_host(self):
         """refresh the host mirrors (Scene.textures, BSDF.value / .texture, emitters[i]['radiance']) from the values params.update() pushed device-to-device"""
@@ -2237,6 +2484,9 @@ class Scene:
             else:
                 b.value = np.ascontiguousarray(v.reshape(3))
         self._device_values.clear()
+        for (mesh, name), t in list(self._device_attrs.items()):
+            self.meshes[mesh]["attributes"][name] = np.ascontiguousarray(t.detach().to("cpu").numpy().astype(np.float32).reshape(self.meshes[mesh]["attributes"][name].shape))
+        self._device_attrs.clear()
         self._sync_host_geometry()
 
     def _sync_host_geometry(self):
@@ -2311,6 +2561,8 @@ class Scene:
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
             texs[i].data = _fp(t); texs[i].height = t.shape[0]; texs[i].width = t.shape[1]; texs[i].mode = self.texture_modes[i] if i < len(self.texture_modes) else 0
+            if i in self._attr_tex:               # a `mesh_attribute` record (HAR_TEX_MESH_ATTRIBUTE): the mesh it belongs to; its `scale` rides in to_uv[0]
+                texs[i].reserved = self._attr_tex[i][0]
             if i < len(self.texture_to_uv) and self.texture_to_uv[i] is not None:
                 texs[i].to_uv = (C.c_float * 6)(*self.texture_to_uv[i])
         ems = (M.HarEmitter * max(1, len(self.emitters)))()
@@ -2440,6 +2692,8 @@ class Scene:
         keys = {}
         for b in self.bsdf_objs:
             base = self._bsdf_key_base(b)
+            if getattr(b, 'attr', None) is not None:
+                continue                   # a `mesh_attribute`: its values are the SHAPE's parameter '<shape>.<name>' (_attr_keys), its own is the `scale` (_attr_scale_keys)
             if b.texture is not None:
                 keys[base + "." + b.slot0_name + ".data"] = ("tex", b)
             else:
@@ -2456,6 +2710,59 @@ class Scene:
             elif e["type"] == 6:                                  # DirectionalEmitter::traverse (directional.cpp:93-97)
                 keys[key + ".irradiance.value"] = ("emit", i)
         return keys
+
+    @_static_table
+    def _attr_keys(self):
+        """'<shape>.<name>' -> (mesh index, name) of every mesh attribute (Mesh::traverse, src/render/mesh.cpp:844-845): a (rows, dim) tensor, differentiable"""
+        return {m["key"] + "." + name: (i, name) for i, m in enumerate(self.meshes) for name in m.get("attributes", {})}
+
+    @_static_table
+    def _attr_scale_keys(self):
+        """'<bsdf>.<slot>.scale' of the `mesh_attribute` textures (MeshAttribute::traverse, mesh_attribute.cpp:88-90: NonDifferentiable)"""
+        return {self._bsdf_key_base(b) + "." + b.slot0_name + ".scale": b for b in self.bsdf_objs if getattr(b, 'attr', None) is not None}
+
+    def _attr_readers(self, mesh, name):
+        return [b for (mi_, n, b) in self._attr_tex.values() if mi_ == mesh and n == name]
+
+    def _set_attribute(self, mesh, name, t, key):
+        """params.update() of '<shape>.<name>': the host mirror, and the record of every BSDF that reads the attribute -- device-to-device when the tensor lives on the GPU"""
+        shape = self.meshes[mesh]["attributes"][name].shape
+        if tuple(t.shape) != tuple(shape):
+            raise RuntimeError("%s: expected a tensor of shape %s, got %s" % (key, tuple(shape), tuple(t.shape)))
+        on_gpu = hasattr(t, "is_cuda") and t.is_cuda and self._h is not None
+        if on_gpu:
+            torch = _torch()
+            v = t.detach().to(torch.float32).contiguous()
+            self._device_attrs[(mesh, name)] = v.clone()
+            for b in self._attr_readers(mesh, name):
+                rows, dim = shape
+                if dim == 1:
+                    r = v.expand(rows, 3).contiguous()
+                elif dim == 3 and b.kind not in _WEIGHTED_BSDFS:
+                    r = v if v.data_ptr() != t.data_ptr() else v.clone()
+                else:
+                    r = torch.zeros((rows, 3), dtype=torch.float32, device=v.device)
+                check(lib().har_scene_set_texture_device(self._h, b.tex_index, _ptr(r), _stream()))
+                self._device_values[("tex", b.tex_index)] = (r, b)
+            return
+        v = t.detach().to("cpu").numpy().astype(np.float32) if hasattr(t, "detach") else np.asarray(t, np.float32)
+        self._device_attrs.pop((mesh, name), None)
+        self.meshes[mesh]["attributes"][name] = np.ascontiguousarray(v).copy()
+        for b in self._attr_readers(mesh, name):
+            self._device_values.pop(("tex", b.tex_index), None)
+            b.texture = self._attr_rows(b, v); self.textures[b.tex_index] = b.texture
+            if self._h is not None:
+                check(lib().har_scene_set_texture(self._h, b.tex_index, _fp(b.texture)))
+
+    def _set_attr_scale(self, b, value, key):
+        v = np.asarray(value.detach().cpu().numpy() if hasattr(value, 'detach') else value, np.float32).reshape(-1)
+        if v.size != 1 or not math.isfinite(float(v[0])):
+            raise RuntimeError("%s: expected 1 finite value" % key)
+        b.attr = (b.attr[0], float(v[0]))
+        if b.texture is not None:
+            b.tex_to_uv = [float(v[0]), 0.0, 0.0, 0.0, 0.0, 0.0]; self.texture_to_uv[b.tex_index] = b.tex_to_uv
+            if self._h is not None:
+                check(lib().har_scene_set_texture_to_uv(self._h, b.tex_index, (C.c_float * 6)(*b.tex_to_uv)))
 
     @_static_table
     def _bsdf_param_keys(self):
@@ -2773,7 +3080,7 @@ class Scene:
                                 # integrator's `light_texel_gradients` (switched on by mi.render for a key with requires_grad) produces its gradient
                 keys[key + ".emitter.radiance.data"] = ("emitter_tex", i); keys[key + ".emitter.radiance.to_uv"] = ("emitter_to_uv", i)
         for b in self.bsdf_objs:            # BitmapTexture::traverse: `to_uv` (src/textures/bitmap.cpp), NonDifferentiable
-            if b.texture is not None:
+            if b.texture is not None and getattr(b, 'attr', None) is None:          # (a `mesh_attribute` has no to_uv: its only own parameter is `scale`)
                 keys[self._bsdf_key_base(b) + "." + b.slot0_name + ".to_uv"] = ("to_uv", b)
         return keys
 
@@ -3006,6 +3313,19 @@ class Scene:
                     out[k] = g_refl[b.index].sum().reshape(1)
             else:
                 out[k] = g_tex[b.tex_index] if kind == "tex" else g_refl[b.index]
+        # mesh attributes: the records of the BSDFs that read '<shape>.<name>' hold d L / d (row, channel) of their rows x 1 x 3 copy; back to the parameter's (rows, dim)
+        # -- a one-channel attribute was stored three times (sum), a weight / opacity record holds d L / d w per colour channel (sum), what evaluates to 0 has none
+        for k, (mesh, name) in self._attr_keys().items():
+            rows, dim = self.meshes[mesh]["attributes"][name].shape
+            total = None
+            for b in self._attr_readers(mesh, name):
+                g = g_tex[b.tex_index].reshape(rows, 3)
+                if dim == 1:
+                    g = g.sum(dim=1, keepdim=True)
+                elif not (dim == 3 and b.kind not in _WEIGHTED_BSDFS):
+                    continue
+                total = g if total is None else total + g
+            out[k] = total if total is not None else g_refl.new_zeros((rows, dim))
         return out
 
     @staticmethod
@@ -3054,7 +3374,7 @@ class SceneParameters(dict):
         sc = self.scene
         if key in self._read_only:
             return ParamFlags.ReadOnly | ParamFlags.NonDifferentiable
-        if key in sc._param_keys():
+        if key in sc._param_keys() or key in sc._attr_keys():
             return ParamFlags.Differentiable
         if key in sc._bsdf_param_keys():
             return ParamFlags.NonDifferentiable if sc._bsdf_param_keys()[key][0] == "ior" else (ParamFlags.Differentiable if sc._bsdf_param_keys()[key][0] == "slot1" else ParamFlags.Differentiable | ParamFlags.Discontinuous)
@@ -3092,6 +3412,10 @@ class SceneParameters(dict):
             self[k] = torch.tensor(np.asarray(value, np.float32), dtype=torch.float32, device=dev)
         for k, (what, b) in scene._bsdf_param_keys().items():
             self[k] = torch.tensor(np.asarray(scene._bsdf_param_value(what, b), np.float32), dtype=torch.float32, device=dev)
+        for k, (m, name) in scene._attr_keys().items():
+            self[k] = torch.tensor(scene.meshes[m]["attributes"][name], dtype=torch.float32, device=dev)            # rows x dim (Mesh::traverse, mesh.cpp:844-845)
+        for k, b in scene._attr_scale_keys().items():
+            self[k] = torch.tensor([b.attr[1]], dtype=torch.float32, device=dev)
         for k, m in scene._position_keys().items():
             self[k] = torch.tensor(np.ascontiguousarray(scene.meshes[m]["V"][:, :3]), dtype=torch.float32, device=dev)            # N x 3, as the reference's `positions` tensor
         for k, i in scene._instance_keys().items():
@@ -3156,6 +3480,7 @@ class SceneParameters(dict):
                 t.append((k, "bsdf", (what, b)))
             self._host_table = [e for e in t if e[0] in self]                      # (keep() may have dropped entries)
             self._colour_table = [e for e in sc._param_keys().items() if e[0] in self]
+            self._attr_table = [(k, ("attr", ref)) for k, ref in sc._attr_keys().items() if k in self] + [(k, ("scale", b)) for k, b in sc._attr_scale_keys().items() if k in self]
         return self._host_table
 
     def _changed_keys(self, written):
@@ -3297,6 +3622,17 @@ class SceneParameters(dict):
         sc._validate_spots()
         stream = None
         pushed = self.__dict__.setdefault("_pushed", {})      # key -> (tensor object, version counter, scene handle) of the last push
+        for k, (kind, ref) in self._attr_table:               # mesh attributes ('<shape>.<name>') and the `scale` of the textures that read them
+            t = self[k]
+            mark = pushed.get(k)
+            if k not in written and mark is not None and hasattr(t, "_version") and mark[0] is t and mark[1] == t._version and mark[2] == (sc._h.value if sc._h is not None else None):
+                continue
+            new_mark = (t, getattr(t, "_version", None), sc._h.value if sc._h is not None else None)
+            if kind == "attr":
+                sc._set_attribute(ref[0], ref[1], t if hasattr(t, "shape") else np.asarray(t, np.float32), k)
+            else:
+                sc._set_attr_scale(ref, t, k)
+            pushed[k] = new_mark
         for k, (kind, b) in self._colour_table:
             t = self[k]
             mark = pushed.get(k)
@@ -3639,8 +3975,10 @@ def _mk_serialized(props, named, key):
 
 def _mk_mesh(props, named, key):
     # not a reference plugin: the dict form of mi.Mesh(...) + params (faces / positions / normals / texcoords arrays)
-    _check_props('mesh', props, ('faces', 'positions', 'normals', 'texcoords', 'to_world', 'silhouette_sampling_weight'), children=_SHAPE_CHILDREN)
+    _check_props('mesh', props, ('faces', 'positions', 'normals', 'texcoords', 'attributes', 'to_world', 'silhouette_sampling_weight'), children=_SHAPE_CHILDREN)
     m = Mesh(key or "mesh").from_fields(props['faces'], props['positions'], props.get('normals'), props.get('texcoords'))
+    for name, values in (props.get('attributes') or {}).items():          # {name: (rows, dim) array}: Mesh::add_attribute for each
+        m.add_attribute(name, values)
     if 'to_world' in props:
         m.transform(props['to_world'])
     return _shape_common(m, props, named)
@@ -3664,7 +4002,7 @@ for _name, _fn in {
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
     'shapegroup': _mk_shapegroup,
     'instance': _mk_instance,
-    'gaussian': lambda p, n, k: p, 'box': lambda p, n, k: p, 'rgb': lambda p, n, k: p, 'bitmap': lambda p, n, k: p, 'area': lambda p, n, k: p,
+    'gaussian': lambda p, n, k: p, 'box': lambda p, n, k: p, 'rgb': lambda p, n, k: p, 'bitmap': lambda p, n, k: p, 'mesh_attribute': lambda p, n, k: p, 'area': lambda p, n, k: p,
 }.items():
     register_plugin(_name, VARIANT, _fn)
 

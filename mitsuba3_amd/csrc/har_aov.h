@@ -43,8 +43,8 @@ inline const char *aov_spec_lower(uint32_t n, const uint32_t *types, AovSpec &sp
  *  - `diffuse`: the reflectance texture at si.uv (diffuse.cpp:181); `plastic` / `roughplastic`: `diffuse_reflectance` (plastic.cpp:362, roughplastic.cpp:504);
  *    both are colour slot 0 of the record;
  *  - every other model: the base class, eval(BSDFContext(), si, wo = (0, 0, 1)) * pi (src/render/bsdf.cpp:38-43). */
-template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
-HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
+template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK / HAR_SCENE_ATTR bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
+HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = nullptr) {
     constexpr bool BLEND = (COMP & HAR_SCENE_BLEND) != 0u;
     BsdfSide side;
     if (!bsdf_side(S, S.meshes[si.mesh].bsdf, si.wi, side)) return Vec3(0.f);
@@ -55,14 +55,14 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si) {
     }
     const DBsdf &B = S.bsdfs[side.index];
     TexTaps taps;
-    const BsdfInputs in = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps);
+    const BsdfInputs in = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps, aa);
     if (BLEND && B.type == BSDF_BLEND) {       /* BlendBSDF::eval_diffuse_reflectance (blendbsdf.cpp:228-233): rho_0 * (1 - w) + rho_1 * w of the nested BSDFs' own answers */
         bool inside; const float w = blend_weight(B, in, inside);
         const uint32_t child[2] = { (uint32_t) B.table, B.pad };
         Vec3 rho[2];
         for (int k = 0; k < 2; ++k) {
             const DBsdf &N = S.bsdfs[child[k]];
-            TexTaps nt; const BsdfInputs nin = bsdf_inputs(S, N, si.uv_x, si.uv_y, nt);
+            TexTaps nt; const BsdfInputs nin = bsdf_inputs(S, N, si.uv_x, si.uv_y, nt, aa);
             if (N.type == BSDF_DIFFUSE || N.type == BSDF_ROUGHPLASTIC || N.type == BSDF_PLASTIC) rho[k] = nin.slot0;
             else { BsdfEval ne; bsdf_eval_pdf_one<HAR_BSDF_ALL_TYPES, false>(N, nin, side.wi, Vec3(0.f, 0.f, 1.f), ne); rho[k] = ne.value * HAR_PI; }
         }
@@ -88,7 +88,11 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
     if (valid) {
         si = compute_si(S, ray_d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
         if (need_partials) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
-        if (need_albedo) albedo = aov_albedo<COMP>(S, si);
+        if (need_albedo && (COMP & HAR_SCENE_ATTR) != 0u) {       /* scenes with a `mesh_attribute` texture: the albedo is looked up at the face and the barycentrics of si.p */
+            AttrAddr addr; addr.face = 0u; addr.b1 = 0.f; addr.b2 = 0.f;
+            if (hit.inst == 0xffffffffu) addr = attr_addr(S, si.p, hit.prim, hit.shape);
+            albedo = aov_albedo<COMP>(S, si, &addr);
+        } else if (need_albedo) albedo = aov_albedo<COMP>(S, si);
     }
     size_t c = 0;
     for (uint32_t k = 0; k < spec.n; ++k) {

@@ -312,6 +312,15 @@ HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC &&
 #define HAR_SCENE_MASK_TYPES (HAR_SCENE_BLEND_TYPES | HAR_SCENE_MASK)
 #define HAR_SCENE_COMPOSITE (HAR_SCENE_BLEND | HAR_SCENE_MASK)          /* scenes that run one widest shading kernel per flavour */
 static_assert((HAR_SCENE_MASK & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x80000000u)) == 0u, "HAR_SCENE_MASK collides with another scene bit");
+/* ... and a `mesh_attribute` texture (src/textures/mesh_attribute.cpp): colour slot 0 of a record reads a per-vertex / per-face attribute of the mesh that was hit, which
+ * needs the face and the barycentrics of si.p at every lookup (SurfInt::attr).  A scene with such a texture record (DTexture::mode & HAR_TEX_ATTRIBUTE) sets this bit in
+ * DScene::bsdf_types and runs a widest set of its own, TYPES = HAR_SCENE_ATTR_TYPES = the mask set | HAR_SCENE_ATTR; every line of attribute code sits behind a test of this
+ * bit (an AttrAddr pointer that is null in the kernels of every other scene).  HAR_SCENE_WIDEST: the scenes that are planned on the widest-kernel route. */
+#define HAR_SCENE_ATTR 0x2000u
+#define HAR_SCENE_ATTR_TYPES (HAR_SCENE_MASK_TYPES | HAR_SCENE_ATTR)
+#define HAR_SCENE_ATTR_LEAN_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_ATTR)      /* ... without a blend / mask record in the scene: no composite code */
+#define HAR_SCENE_WIDEST (HAR_SCENE_COMPOSITE | HAR_SCENE_ATTR)
+static_assert((HAR_SCENE_ATTR & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x80000000u)) == 0u, "HAR_SCENE_ATTR collides with another scene bit");
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */

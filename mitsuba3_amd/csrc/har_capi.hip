@@ -669,8 +669,10 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     /* texels of a light's bitmap radiance: committed in place by the re-shading replay as well (the record tape holds neither the sampled uv nor the unit weight) */
     const bool light_texels = I->set.grad_light_texels && (S->ds.bsdf_types & HAR_SCENE_TEXLIGHT) != 0u;
     /* a `blendbsdf` record: the nested records' gradients are deposited by the in-place commit of the re-shading replay (the record tape holds one record per vertex) */
-    const bool blend = (S->ds.bsdf_types & HAR_SCENE_COMPOSITE) != 0u;
-    const char *const comp = (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
+    /* ... and a `mesh_attribute` texture: the transpose of its lookup needs the hit (face, barycentrics), which only the in-place commit has at hand */
+    const bool blend = (S->ds.bsdf_types & HAR_SCENE_WIDEST) != 0u;
+    const bool attr_only = (S->ds.bsdf_types & HAR_SCENE_WIDEST) == HAR_SCENE_ATTR;
+    const char *const comp = attr_only ? "mesh_attribute" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
     int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
     tape = std::min(tape, I->bw_tape_max);
     /* The tapes are the large workspaces (record tape 69 B, state tape 115 B per lane and bounce against 25 B for the lane-indexed cache: 28 - 90 GB for a 2^26-lane chunk
@@ -711,9 +713,10 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
         if (!W.adjoint_inline) return fail("gradients of a light's texels need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (blend) {
+        if (I->set.grad_bsdf_params && attr_only) return fail("mesh_attribute: gradients of alpha / eta / k / specular colours are not produced for scenes with a `mesh_attribute` texture (the attributes' are)");
         if (I->set.grad_bsdf_params) return fail(std::string(comp) + ": gradients of alpha / eta / k / specular colours are not produced for scenes with a " + ((S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask record (the opacity and the nested BSDF's colour slot 0 are)" : "blend record (the weight and the nested BSDFs' colour slot 0 are)"));
         if (!I->set.use_cache || I->shape_on) return fail(std::string(comp) + ": gradients need the replay cache and cannot be combined with vertex-position gradients");
-        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail(std::string(comp) + ": gradients of a scene with a " + ((S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blend") + " record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
+        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail(std::string(comp) + ": gradients of a scene with a " + (attr_only ? "mesh_attribute texture" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blend") + " record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
         if (!W.adjoint_inline) return fail(std::string(comp) + ": gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (I->set.grad_bsdf_params) {
@@ -769,12 +772,17 @@ int har_render_forward(HarScene S, HarIntegrator I, const HarSensor *sensor, uin
     if (I->set.type != HAR_INTEGRATOR_PRB) return fail("render_forward is implemented by the `prb` integrator");
     if (!film || !tangent_reflectance) return fail("null film / tangent buffers");
     if (I->shape_on) return fail("render_forward: tangents of vertex positions are not implemented (use render_backward for shape gradients)");
+    /* forward mode commits through items, which carry a uv and no face: in a scene with a `mesh_attribute` texture the face comes from the replay cache's hit records,
+     * so every bounce must be a cached one */
+    if ((S->ds.bsdf_types & HAR_SCENE_ATTR) && (!I->set.use_cache || bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES))
+        return fail("mesh_attribute: render_forward of a scene with a `mesh_attribute` texture needs the replay cache and max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
     hipStream_t s = (hipStream_t) stream;
     if (I->set.max_depth == 0) {        /* no interaction, no derivative: a zero image with the filter weights */
         return har_render_weights(sensor, seed, spp, lb, le, film, stream);
     }
     uint32_t chunk = (uint32_t) std::min<uint64_t>(I->set.chunk, (std::max<uint64_t>(le - lb, 2048) + 2047) / 2048 * 2048);
     if (ensure_workspace(I, chunk, true)) return 1;
+    if ((S->ds.bsdf_types & HAR_SCENE_ATTR) && I->cache_bounces < bounce_limit(I)) return fail("mesh_attribute: render_forward of a scene with a `mesh_attribute` texture needs every bounce in the replay cache");
     const size_t nt = S->hs.textures.size();
     if (I->grad_tex_cap < std::max<size_t>(nt, 1)) { if (ws_alloc(I, &I->d_grad_tex, std::max<size_t>(nt, 1))) return 1; I->grad_tex_cap = std::max<size_t>(nt, 1); }
     if (nt) {
@@ -828,6 +836,8 @@ int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const 
          * attached si.wi (prb.py:128-140) */
         const size_t nm = S->hs.meshes.size();
         /* their adjoint goes through items, which carry one (record, direct, relative) triple per vertex: a blend vertex has three */
+        /* ... and the barycentrics an attribute is looked up at move with the positions (Mesh::barycentric_coordinates): not differentiated */
+        if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("vertex-position gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_MASK) return fail("vertex-position gradients are not produced for a scene with a `mask` record");
         if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("vertex-position gradients are not produced for a scene with a `blendbsdf` record");
         offset.assign(nm, -1); user.assign(nm, nullptr); count.assign(nm, 0);
@@ -870,6 +880,7 @@ int har_integrator_set_grad_instances(HarIntegrator I, HarScene S, float *grad_t
     uint32_t n = 0;
     if (grad_to_world) {
         if (!S) return fail("null scene");
+        if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("instance to_world gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_MASK) return fail("instance to_world gradients are not produced for a scene with a `mask` record");
         if (S->ds.bsdf_types & HAR_SCENE_BLEND) return fail("instance to_world gradients are not produced for a scene with a `blendbsdf` record");
         /* as for the vertex positions: any BSDF with a non-delta lobe on the moving geometry, i.e. on the meshes of the shape groups */

@@ -940,8 +940,9 @@ struct TexelRecord { bool has; uint32_t q, cell, tex; float w1x, w1y; Vec3 g; };
 /* the reverse-mode commit of one vertex with the lane's L and dL in REGISTERS (the in-place commit of k_shade keeps them there across the emission
  * term, this commit and the extra-parameter terms; the tape hands them from slot to slot): L <- L - [visible] Lr_dir, `dirty` says whether L changed */
 __device__ __forceinline__ void adjoint_commit_regs(const DScene &S, bool pred, bool visible, float4 s2, float4 s3, float4 s4, Vec3 &L, bool &dirty, Vec3 dl,
-                                                    float *grad_refl, float *const *grad_tex, float *gacc, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr) {
-    Vec3 g(0.f); float *dst = grad_refl; bool tex = false; TexTaps taps; float *tdst = nullptr;
+                                                    float *grad_refl, float *const *grad_tex, float *gacc, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr,
+                                                    const AttrAddr *aa = nullptr) {         /* aa: scenes with a `mesh_attribute` texture -- where the vertex looks attributes up */
+    Vec3 g(0.f); float *dst = grad_refl; bool tex = false; TexTaps taps; float *tdst = nullptr; bool attribute = false;
     bool em_lds = false; uint32_t em_slot = 0; Vec3 ge(0.f);
     if (pred) {
         const uint32_t tag = __float_as_uint(s2.w), bsdf = tag & 0xfffffu, emitter = (tag >> 20) & 0x7ffu;
@@ -961,7 +962,7 @@ __device__ __forceinline__ void adjoint_commit_regs(const DScene &S, bool pred, 
         g = g * dl;
         const DBsdf B = S.bsdfs[bsdf];
         dst = grad_refl + 3 * (size_t) bsdf;
-        if (B.texture >= 0) { tex = true; tex_taps(S.textures[B.texture], s3.w, s4.w, taps); tdst = grad_tex[B.texture]; }
+        if (B.texture >= 0) { tex = true; attribute = tex_taps_at(S, S.textures[B.texture], s3.w, s4.w, aa, taps); tdst = grad_tex[B.texture]; }
     }
     if (__ballot(em_lds)) wave_slot_add3(gacc, em_slot, ge, em_lds);
     const bool nz = pred && (g.x != 0.f || g.y != 0.f || g.z != 0.f);
@@ -986,9 +987,11 @@ __device__ __forceinline__ void adjoint_commit_regs(const DScene &S, bool pred, 
         if (flat && !lds) { atomicAdd(dst, g.x); atomicAdd(dst + 1, g.y); atomicAdd(dst + 2, g.z); }
     }
     if (__ballot(nz_direct && tex)) {
-        const float w[4] = { taps.w0x * taps.w0y, taps.w1x * taps.w0y, taps.w0x * taps.w1y, taps.w1x * taps.w1y };
-        for (int k = 0; k < 4; ++k)
-            wave_aggregated_add3(nz_direct && tex ? tdst + 3 * (size_t) taps.idx[k] : grad_refl, nz_direct && tex ? g * w[k] : Vec3(0.f), nz_direct && tex);
+        float w[4]; tap_weights(taps, attribute, w);
+        for (int k = 0; k < 4; ++k) {
+            const bool on = nz_direct && tex && !(attribute && k == 3);        /* an attribute has three taps: b0, b1, b2 (times `scale`) into the face's vertex rows, or 1 into the face's row */
+            wave_aggregated_add3(on ? tdst + 3 * (size_t) taps.idx[k] : grad_refl, on ? g * w[k] : Vec3(0.f), on);
+        }
     }
 }
 /* g * d radiance(u, v) / d texels into the gradient buffer of emitter `index`'s bitmap (type 7): the transpose of the lookup (nearest: four coincident taps of weight 1, 0, 0, 0);
@@ -1008,27 +1011,30 @@ __device__ __forceinline__ void light_texel_commit(const DScene &S, float *const
 /* g = d L / d (slot 0 of BSDF record `rec`, evaluated at (u, v)) deposited where that record's gradient lives: its row of `grad_slots`, or -- a bitmap -- its entry of
  * `grad_tex` through the transpose of the lookup.  What the in-place commit of a BLEND vertex does for the two nested records (the weight's own gradient rides in the
  * vertex's ordinary commit, adjoint_commit_regs): it only deposits -- no update of L, no emitter part.  Called by whole waves; lanes aimed at the same address are pre-reduced. */
-__device__ __forceinline__ void blend_child_commit(const DScene &S, float *grad_slots, float *const *grad_tex, bool pred, uint32_t rec, float u, float v, Vec3 g) {
+__device__ __forceinline__ void blend_child_commit(const DScene &S, float *grad_slots, float *const *grad_tex, bool pred, uint32_t rec, float u, float v, Vec3 g, const AttrAddr *aa = nullptr) {
     pred = pred && (g.x != 0.f || g.y != 0.f || g.z != 0.f);
     if (!__ballot(pred)) return;
-    TexTaps taps; float *dst = nullptr; bool tex = false;
+    TexTaps taps; float *dst = nullptr; bool tex = false, attribute = false;
     taps.idx[0] = taps.idx[1] = taps.idx[2] = taps.idx[3] = 0u; taps.w0x = taps.w1x = taps.w0y = taps.w1y = 0.f;
     if (pred) {
         const int32_t t = S.bsdfs[rec].texture;
-        if (t >= 0) { tex = true; tex_taps(S.textures[t], u, v, taps); dst = grad_tex[t]; }
+        if (t >= 0) { tex = true; attribute = tex_taps_at(S, S.textures[t], u, v, aa, taps); dst = grad_tex[t]; }
         else dst = grad_slots + 3 * (size_t) rec;
     }
     wave_aggregated_add3(dst, g, pred && !tex);
     if (!__ballot(pred && tex)) return;
-    const float w[4] = { taps.w0x * taps.w0y, taps.w1x * taps.w0y, taps.w0x * taps.w1y, taps.w1x * taps.w1y };
+    float w[4]; tap_weights(taps, attribute, w);
     for (int k = 0; k < 4; ++k) {
         const bool on = pred && tex && w[k] != 0.f;
         wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
     }
 }
-template <bool FWD = false>
+/* ATTR (forward mode of a scene with a `mesh_attribute` texture, k_resolve_forward_attr): the item of a vertex whose record reads an attribute carries the barycentrics
+ * (b1, b2) in its uv words (shade_lane), and the face comes from the bounce's replay-cache hit record of the item's lane, `hits` */
+template <bool FWD = false, bool ATTR = false>
 __device__ __forceinline__ void adjoint_commit_values(const DScene &S, bool pred, bool visible, uint32_t lane, float4 s2, float4 s3, float4 s4, float4 *result, const float4 *dL,
-                                                      float *grad_refl, float *const *grad_tex, float *gacc, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr) {
+                                                      float *grad_refl, float *const *grad_tex, float *gacc, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr,
+                                                      const ReplayCache *hits = nullptr) {
     if (FWD) {
         /* FORWARD mode (RBIntegrator.render_forward, common.py:497-623; prb.py:313 `dL += dr.forward_to(Lo)`): `grad_refl` / `grad_tex` hold the
          * TANGENTS of the parameters (same layout as the gradient buffers: slots of the BSDFs, then of the emitters; one array per bitmap) and are
@@ -1048,9 +1054,13 @@ __device__ __forceinline__ void adjoint_commit_values(const DScene &S, bool pred
             const DBsdf B = S.bsdfs[bsdf];
             Vec3 tan;
             if (B.texture >= 0) {
-                TexTaps taps; tex_taps(S.textures[B.texture], s3.w, s4.w, taps);
+                TexTaps taps; bool attribute = false;
+                if (ATTR && (S.textures[B.texture].mode & HAR_TEX_ATTRIBUTE)) {          /* the tangents of the attribute through the same three taps as the lookup */
+                    AttrAddr a; a.face = S.meshes[hits->h1[lane].x].foff + __float_as_uint(hits->h0[lane].w); a.b1 = s3.w; a.b2 = s4.w;
+                    attr_taps(S, S.textures[B.texture], a, taps); attribute = true;
+                } else tex_taps(S.textures[B.texture], s3.w, s4.w, taps);
                 const float *tt = grad_tex[B.texture];
-                const float w[4] = { taps.w0x * taps.w0y, taps.w1x * taps.w0y, taps.w0x * taps.w1y, taps.w1x * taps.w1y };
+                float w[4]; tap_weights(taps, ATTR && attribute, w);
                 tan = Vec3(0.f);
                 for (int k = 0; k < 4; ++k) { const float *q = tt + 3 * (size_t) taps.idx[k]; tan = Vec3(fma_(q[0], w[k], tan.x), fma_(q[1], w[k], tan.y), fma_(q[2], w[k], tan.z)); }
             } else { const float *q = grad_refl + 3 * (size_t) bsdf; tan = Vec3(q[0], q[1], q[2]); }
@@ -1103,13 +1113,14 @@ __device__ __forceinline__ void texel_queue_append(const DScene &S, const TexelQ
     }
     texel_record_direct(S, grad_tex, grad_slots, rec, overflow);
 }
-template <bool FWD = false>
+template <bool FWD = false, bool ATTR = false>
 __device__ __forceinline__ void adjoint_commit(const DScene &S, const ItemArrays &items, uint32_t i, bool pred, bool visible, float4 *result, const float4 *dL,
-                                               float *grad_refl, float *const *grad_tex, float *gacc, uint8_t *item_vis, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr) {
+                                               float *grad_refl, float *const *grad_tex, float *gacc, uint8_t *item_vis, const TexelQueues *tq = nullptr, TexelRecord *rec = nullptr,
+                                               const ReplayCache *hits = nullptr) {
     if (pred && item_vis) item_vis[i] = visible ? 1 : 0;
     float4 s2 = make_float4(0.f, 0.f, 0.f, 0.f), s3 = s2, s4 = s2; uint32_t lane = 0;
     if (pred) { lane = __float_as_uint(items.s1[i].w); s2 = items.s2[i]; s3 = items.s3[i]; s4 = items.s4[i]; }
-    adjoint_commit_values<FWD>(S, pred, visible, lane, s2, s3, s4, result, dL, grad_refl, grad_tex, gacc, tq, rec);
+    adjoint_commit_values<FWD, ATTR>(S, pred, visible, lane, s2, s3, s4, result, dL, grad_refl, grad_tex, gacc, tq, rec, hits);
 }
 
 /* ---------------------------------------------------------------- classify */
@@ -1359,7 +1370,7 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
             TexelRecord rec; rec.has = false;
             adjoint_commit_regs(S, item_pred, visible, make_float4(c.x, c.y, c.z, __uint_as_float(tag)), make_float4(R.dLr_drho.x, R.dLr_drho.y, R.dLr_drho.z, R.uv_x),
                                 make_float4(R.rel_grad.x, R.rel_grad.y, R.rel_grad.z, R.uv_y), Lr, L_dirty, dlr, grad_slots, grad_tex, gacc,      /* forward mode never commits in place (host) */
-                                tq.nq ? &tq : nullptr, &rec);
+                                tq.nq ? &tq : nullptr, &rec, (TYPES & HAR_SCENE_ATTR) != 0u ? &R.attr : nullptr);
             if ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && (P.flags & HAR_SHADE_LIGHT_TEXELS)) {
                 /* the texels of a bitmap `radiance` (area.cpp:64-70): d Le / d radiance(si.uv) = beta mis at an emitter hit, d Lr_dir / d radiance(ds.uv) = beta mis f / pdf at a
                  * VISIBLE emitter sample -- scattered through the transpose of the bilinear lookup, pre-reduced over the wave (all lanes of a block sample the same few texels) */
@@ -1387,7 +1398,7 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                     const bool on = item_pred && R.bl_rec[k] != 0xffffffffu;
                     Vec3 g = (on && visible) ? R.bl_dir[k] : Vec3(0.f);
                     if (on) g = g + Vec3(Lr.x * R.bl_rel[k].x, Lr.y * R.bl_rel[k].y, Lr.z * R.bl_rel[k].z);
-                    blend_child_commit(S, grad_slots, grad_tex, on, on ? R.bl_rec[k] : 0u, R.uv_x, R.uv_y, g * dlr);
+                    blend_child_commit(S, grad_slots, grad_tex, on, on ? R.bl_rec[k] : 0u, R.uv_x, R.uv_y, g * dlr, (TYPES & HAR_SCENE_ATTR) != 0u ? &R.attr : nullptr);
                 }
             }
             /* write-back: replay -> the survivor's slot of the next bounce (the primal pass's compaction, TapeArrays::next); otherwise the lane's result */
@@ -1667,6 +1678,21 @@ __global__ __launch_bounds__(kBlock) void k_resolve_adjoint_cached(DScene S, con
     for (uint32_t k = threadIdx.x; k < 3 * min(S.n_bsdfs + S.n_emitters, (uint32_t) HAR_LDS_GRAD_BSDFS); k += kBlock) {
         const float v = gacc[k];
         if (v != 0.f) atomicAdd(grad_refl + k, v);
+    }
+}
+
+/* ... in FORWARD mode for a scene with a `mesh_attribute` texture: the tangents of an attribute are read through the lookup's three taps, with the face from the bounce's
+ * replay-cache hit record (har_render_forward keeps every bounce of such a scene cached).  A kernel of its own, so that the one above keeps its code and its name */
+__global__ __launch_bounds__(kBlock) void k_resolve_forward_attr(DScene S, const uint32_t *item_count, uint32_t shard_cap, ItemArrays items, float4 *result,
+                                                                 const float4 *dL, float *grad_refl, float *const *grad_tex, ReplayCache rc, uint8_t *item_vis) {
+    const ShardLoop Q(item_count, shard_cap);
+    for (uint32_t tile = Q.first_tile(); tile * kBlock < Q.n; tile += Q.tile_step()) {
+        const uint32_t local = tile * kBlock + threadIdx.x;
+        const bool pred = local < Q.n;
+        const uint32_t i = Q.base + (pred ? local : 0u);
+        bool visible = false;
+        if (pred && items.s0[i].w >= 0.f) visible = rc.vis[__float_as_uint(items.s1[i].w)] != 0;
+        adjoint_commit<true, true>(S, items, i, pred, visible, result, dL, grad_refl, grad_tex, nullptr, item_vis, nullptr, nullptr, &rc);
     }
 }
 
@@ -2368,6 +2394,23 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_ATTR) {
+        /* a scene with a `mesh_attribute` texture: the four flavours of a mask scene (below) in a set that also looks attributes up.  Every backward pass takes the in-place
+         * commit (it has the hit at hand).  Two sets: scenes that also hold a blend / mask record run the mask set plus the lookup (HAR_SCENE_ATTR_TYPES); the others -- a
+         * plain BSDF over vertex colours, the feature's main use -- run the generic set plus the lookup and do not carry the composite code (HAR_SCENE_ATTR_LEAN_TYPES) */
+#define HAR_LAUNCH_SHADE_ATTR(T) do { \
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4)) \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape); \
+        else if (mode == MODE_PATH) \
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags of a scene that also holds a mask record, or null (run_chunk) */, no_mq, 0u, tape); \
+        else if (mode == MODE_PRB_PRIMAL) \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape); \
+        else \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape); } while (0)
+        if (S.bsdf_types & HAR_SCENE_COMPOSITE) HAR_LAUNCH_SHADE_ATTR(HAR_SCENE_ATTR_TYPES); else HAR_LAUNCH_SHADE_ATTR(HAR_SCENE_ATTR_LEAN_TYPES);
+#undef HAR_LAUNCH_SHADE_ATTR
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_MASK) {
         /* a scene with a `mask` record: the same four flavours as for a blend scene (below), in the set that carries the mask code as well -- such a scene may hold blend
          * records on other meshes, so this set is the blend set plus the null lobe: four more shading kernels, not eight */
@@ -2510,7 +2553,8 @@ void launch_resolve(int mode, hipStream_t s, uint32_t grid, uint2 *spill, const 
     dim3 g(grid), b(kBlock);
     if (mode == MODE_PRB_ADJOINT && rc.mode == 2) {
         const TexelQueues no_tq{ nullptr, nullptr, nullptr, nullptr, 0u, 0u, nullptr };
-        if (fwd) hipLaunchKernelGGL(k_resolve_adjoint_cached<true>, g, b, 0, s, S, item_count, shard_cap, items, result, dL, grad_refl, grad_tex, rc, item_vis, no_tq);
+        if (fwd && (S.bsdf_types & HAR_SCENE_ATTR)) hipLaunchKernelGGL(k_resolve_forward_attr, g, b, 0, s, S, item_count, shard_cap, items, result, dL, grad_refl, grad_tex, rc, item_vis);
+        else if (fwd) hipLaunchKernelGGL(k_resolve_adjoint_cached<true>, g, b, 0, s, S, item_count, shard_cap, items, result, dL, grad_refl, grad_tex, rc, item_vis, no_tq);
         else hipLaunchKernelGGL(k_resolve_adjoint_cached<false>, g, b, 0, s, S, item_count, shard_cap, items, result, dL, grad_refl, grad_tex, rc, item_vis, tq ? *tq : no_tq);
         return;
     }

@@ -8,7 +8,7 @@
  *                             (Mesh::pack: normal_index = position_index, src/render/mesh.cpp:573-582), i.e. UV seams stay smooth.
  *   har_mesh_load_serialized  SerializedMesh ctor + load_legacy (src/shapes/serialized.cpp:225-370): Mitsuba 0.x / 2 / 3 `.serialized`
  *                             container versions 3 and 4 (zlib stream per sub-mesh, offset table at the end of the file).
- * Output: the packed layout har_scene_create ingests (8 f32 per vertex, 4 u32 per face), malloc'ed.
+ * Output: the packed layout har_scene_create ingests (8 f32 per vertex, 4 u32 per face), malloc'ed; har_mesh_load_serialized_fields also returns a v5 sub-mesh's custom attributes.
  */
 #include "../../include/hip_ad_rgb.h"
 #include "har_math.h"
@@ -69,13 +69,31 @@ void fetch_key(const std::vector<float> &pool, uint32_t index, int dim, uint32_t
 extern "C" {
 
 static int mesh_load_obj_impl(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out);
-static int mesh_load_serialized_impl(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out);
+/* the custom attributes of a version-5 sub-mesh: names ("<name>:<dim>" per line) and their rows x dim arrays back to back, per-vertex and per-face ones apart */
+struct SerializedAttrs { std::string vertex_names, face_names; std::vector<float> vertex_data, face_data; uint32_t vertex_count = 0, face_count = 0; };
+static int mesh_load_serialized_impl(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out, SerializedAttrs *attrs = nullptr);
 static void mesh_reset(HarMeshData *out) { if (out) { free(out->vertices); free(out->faces); out->vertices = nullptr; out->faces = nullptr; out->vertex_count = out->face_count = out->flags = out->reserved = 0; } }
 /* no C++ exception (std::bad_alloc of a file-controlled size, ...) crosses the C boundary */
 int har_mesh_load_obj(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out) {
     try { return mesh_load_obj_impl(filename, face_normals, flip_tex_coords, to_world, flip_normals, out); }
     catch (const std::bad_alloc &) { mesh_reset(out); return har_set_error(std::string("Error while loading OBJ file \"") + (filename ? filename : "") + "\": out of memory"); }
     catch (const std::exception &e) { mesh_reset(out); return har_set_error(std::string("Error while loading OBJ file \"") + (filename ? filename : "") + "\": " + e.what()); }
+}
+int har_mesh_load_serialized_fields(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out, HarMeshFields *fields) {
+    if (!fields) return har_set_error("null argument");
+    memset(fields, 0, sizeof(*fields));
+    try {
+        SerializedAttrs sa;
+        if (mesh_load_serialized_impl(filename, shape_index, face_normals, to_world, flip_normals, out, &sa)) return 1;
+        auto dup = [](const void *src, size_t bytes) -> void * { void *p = malloc(std::max<size_t>(bytes, 1)); if (p && bytes) memcpy(p, src, bytes); return p; };
+        fields->vertex_names = (char *) dup(sa.vertex_names.c_str(), sa.vertex_names.size() + 1); fields->face_names = (char *) dup(sa.face_names.c_str(), sa.face_names.size() + 1);
+        fields->vertex_data = (float *) dup(sa.vertex_data.data(), sa.vertex_data.size() * sizeof(float)); fields->face_data = (float *) dup(sa.face_data.data(), sa.face_data.size() * sizeof(float));
+        fields->vertex_cols = sa.vertex_count; fields->face_cols = sa.face_count;
+        if (!fields->vertex_names || !fields->face_names || !fields->vertex_data || !fields->face_data) { har_mesh_fields_free(fields); mesh_reset(out); return har_set_error("out of memory"); }
+        return 0;
+    }
+    catch (const std::bad_alloc &) { mesh_reset(out); har_mesh_fields_free(fields); return har_set_error(std::string("Error while loading serialized file \"") + (filename ? filename : "") + "\": out of memory!"); }
+    catch (const std::exception &e) { mesh_reset(out); har_mesh_fields_free(fields); return har_set_error(std::string("Error while loading serialized file \"") + (filename ? filename : "") + "\": " + e.what() + "!"); }
 }
 int har_mesh_load_serialized(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out) {
     try { return mesh_load_serialized_impl(filename, shape_index, face_normals, to_world, flip_normals, out); }
@@ -296,7 +314,7 @@ static int mesh_load_obj_impl(const char *filename, int face_normals, int flip_t
     return emit(V, F, ((keep_normals || regenerate) ? 1u : 0u) | (keep_uv ? 2u : 0u), out);
 }
 
-static int mesh_load_serialized_impl(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out) {
+static int mesh_load_serialized_impl(const char *filename, int shape_index, int face_normals, const float *to_world, int flip_normals, HarMeshData *out, SerializedAttrs *attrs) {
     if (!filename || !out) return har_set_error("null argument");
     out->vertices = nullptr; out->faces = nullptr; out->vertex_count = out->face_count = out->flags = out->reserved = 0;
     auto fail = [&](const std::string &d) { return har_set_error("Error while loading serialized file \"" + std::string(filename) + "\": " + d + "!"); };
@@ -363,11 +381,19 @@ static int mesh_load_serialized_impl(const char *filename, int shape_index, int 
         if (nc && !take(nullptr, (size_t) vc * 4)) return fail("unexpected end of stream");
         uint32_t attr_count = 0;
         if (!take(&attr_count, 4)) return fail("unexpected end of stream");
-        for (uint32_t a = 0; a < attr_count; ++a) {          /* custom attributes are read past: nothing on the hip_ad_rgb path looks them up */
+        for (uint32_t a = 0; a < attr_count; ++a) {          /* custom attributes (Mesh::write_serialized: name, flags, dim, rows x dim floats): handed to the caller that asks for them */
             std::string an; uint8_t aflags = 0; uint32_t dim = 0;
             if (!take_string(an) || !take(&aflags, 1) || !take(&dim, 4)) return fail("unexpected end of stream");
-            const uint64_t rows = an.compare(0, 5, "face_") == 0 ? fc : vc;
+            const bool per_face = an.compare(0, 5, "face_") == 0;
+            const uint64_t rows = per_face ? fc : vc;
             if (dim != 0 && rows > (raw.size() - pos) / 4 / dim) return fail("unexpected end of stream");
+            if (attrs && an.find('\n') == std::string::npos && an.find(':') == std::string::npos) {
+                std::vector<float> &dst = per_face ? attrs->face_data : attrs->vertex_data;
+                const size_t n = (size_t) (rows * dim), at = dst.size();
+                dst.resize(at + n); if (n) memcpy(dst.data() + at, raw.data() + pos, n * 4);
+                (per_face ? attrs->face_names : attrs->vertex_names) += an + ":" + std::to_string(dim) + "\n";
+                (per_face ? attrs->face_count : attrs->vertex_count) += 1u;
+            }
             pos += (size_t) (rows * dim * 4);
         }
         for (size_t i = 0; i < (size_t) fc; ++i) for (int k = 0; k < 3; ++k) if (F[4 * i + k] >= vc) return fail("face index out of bounds");

@@ -158,7 +158,32 @@ int har_mesh_finalize(std::vector<float> &V, std::vector<uint32_t> &F, bool stor
 
 extern "C" {
 
-static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out);
+/* the scalar (non-list) properties of the vertex and the face element as the file holds them, converted to float without rescaling: what the attribute grouping of
+ * find_other_fields (src/shapes/ply.h:272-422) works on.  Names: one line per column, "<type class>:<name>" with type class `f` (float / double) or `i` (integer) */
+struct PlyFields { std::string vertex_names, face_names; std::vector<float> vertex_data, face_data; uint32_t vertex_cols = 0, face_cols = 0; };
+static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out, PlyFields *fields = nullptr);
+static bool ply_type_is_float(int type) { return type == F32 || type == F64; }
+void har_mesh_fields_free(HarMeshFields *f) {
+    if (!f) return;
+    free(f->vertex_names); free(f->face_names); free(f->vertex_data); free(f->face_data);
+    memset(f, 0, sizeof(*f));
+}
+int har_mesh_load_ply_fields(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out, HarMeshFields *fields) {
+    if (!fields) return har_set_error("null argument");
+    memset(fields, 0, sizeof(*fields));
+    try {
+        PlyFields pf;
+        if (mesh_load_ply_impl(filename, face_normals, flip_tex_coords, to_world, flip_normals, out, &pf)) return 1;
+        auto dup = [](const void *src, size_t bytes) -> void * { void *p = malloc(std::max<size_t>(bytes, 1)); if (p && bytes) memcpy(p, src, bytes); return p; };
+        fields->vertex_names = (char *) dup(pf.vertex_names.c_str(), pf.vertex_names.size() + 1); fields->face_names = (char *) dup(pf.face_names.c_str(), pf.face_names.size() + 1);
+        fields->vertex_data = (float *) dup(pf.vertex_data.data(), pf.vertex_data.size() * sizeof(float)); fields->face_data = (float *) dup(pf.face_data.data(), pf.face_data.size() * sizeof(float));
+        fields->vertex_cols = pf.vertex_cols; fields->face_cols = pf.face_cols;
+        if (!fields->vertex_names || !fields->face_names || !fields->vertex_data || !fields->face_data) { har_mesh_fields_free(fields); har_mesh_free(out); return har_set_error("out of memory"); }
+        return 0;
+    }
+    catch (const std::bad_alloc &) { if (out) har_mesh_free(out); har_mesh_fields_free(fields); return har_set_error(std::string("Error while loading PLY file \"") + (filename ? filename : "") + "\": out of memory!"); }
+    catch (const std::exception &e) { if (out) har_mesh_free(out); har_mesh_fields_free(fields); return har_set_error(std::string("Error while loading PLY file \"") + (filename ? filename : "") + "\": " + e.what() + "!"); }
+}
 /* file contents are untrusted: element counts are bounded by the bytes that are left in the file and by the 2^32 - 1 indices of the packed layout,
  * and no C++ exception (std::bad_alloc of a header-controlled vector size, ...) crosses the C boundary */
 int har_mesh_load_ply(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out) {
@@ -166,7 +191,7 @@ int har_mesh_load_ply(const char *filename, int face_normals, int flip_tex_coord
     catch (const std::bad_alloc &) { if (out) har_mesh_free(out); return har_set_error(std::string("Error while loading PLY file \"") + (filename ? filename : "") + "\": out of memory!"); }
     catch (const std::exception &e) { if (out) har_mesh_free(out); return har_set_error(std::string("Error while loading PLY file \"") + (filename ? filename : "") + "\": " + e.what() + "!"); }
 }
-static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out) {
+static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_tex_coords, const float *to_world, int flip_normals, HarMeshData *out, PlyFields *fields) {
     if (!filename || !out) return har_set_error("null argument");
     memset(out, 0, sizeof(*out));
     auto fail = [&](const std::string &d) { har_mesh_free(out); return har_set_error("Error while loading PLY file \"" + std::string(filename) + "\": " + d + "!"); };
@@ -227,9 +252,14 @@ static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_t
             has_uv = ix[6] >= 0;
             nv = el.count; V.assign(8 * nv, 0.f);
             std::vector<double> rec(el.props.size());
+            if (fields) {          /* (a vertex element has no list properties: every column is kept) */
+                fields->vertex_cols = (uint32_t) el.props.size(); fields->vertex_data.assign(el.props.size() * nv, 0.f);
+                for (const Prop &p : el.props) fields->vertex_names += std::string(ply_type_is_float(p.type) ? "f:" : "i:") + p.name + "\n";
+            }
             for (size_t i = 0; i < nv; ++i) {
                 for (size_t k = 0; k < el.props.size(); ++k) rec[k] = R.read(el.props[k].type);
                 if (R.fail) return fail("unexpected end of file");
+                if (fields) for (size_t k = 0; k < el.props.size(); ++k) fields->vertex_data[i * el.props.size() + k] = (float) rec[k];
                 float *o = V.data() + 8 * i;
                 for (int c = 0; c < 3; ++c) { o[c] = (float) rec[ix[c]]; if (!finite_(o[c])) return fail("mesh contains invalid vertex position data"); }
                 if (has_normals) for (int c = 0; c < 3; ++c) o[3 + c] = (float) rec[ix[3 + c]];
@@ -240,10 +270,16 @@ static int mesh_load_ply_impl(const char *filename, int face_normals, int flip_t
             for (size_t k = 0; k < el.props.size(); ++k) if (el.props[k].is_list && (el.props[k].name == "vertex_index" || el.props[k].name == "vertex_indices")) il = (int) k;
             if (il < 0) return fail("vertex_index/vertex_indices property not found");
             nf = el.count; F.assign(4 * nf, 0u);
+            std::vector<int> col(el.props.size(), -1);
+            if (fields) {
+                uint32_t nc = 0;
+                for (size_t k = 0; k < el.props.size(); ++k) if (!el.props[k].is_list) { col[k] = (int) nc++; fields->face_names += std::string(ply_type_is_float(el.props[k].type) ? "f:" : "i:") + el.props[k].name + "\n"; }
+                fields->face_cols = nc; fields->face_data.assign((size_t) nc * nf, 0.f);
+            }
             for (size_t i = 0; i < nf; ++i) {
                 for (size_t k = 0; k < el.props.size(); ++k) {
                     const Prop &p = el.props[k];
-                    if (!p.is_list) { (void) R.read(p.type); continue; }
+                    if (!p.is_list) { const double v = R.read(p.type); if (fields) fields->face_data[i * fields->face_cols + (size_t) col[k]] = (float) v; continue; }
                     double cnt = R.read(p.count_type);
                     if ((int) k == il) {
                         if (R.fail || cnt != 3.0) return fail("incompatible contents -- is this a triangle mesh?");

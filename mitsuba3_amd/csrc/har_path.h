@@ -87,6 +87,9 @@ struct ShadeResult {
      * the BSDF sample drawn there is not the null lobe (path.cpp:307-308; JIT order: drawn at the last vertex, depth + 1 == max_depth, too).  A mask vertex files the
      * opacity's gradient pair in dLr_drho / rel_grad and the nested LEAF record's in bl_*[0] (bl_rec[1] stays 0xffffffff), as a blend vertex does */
     bool non_null;
+    /* ... kernels of scenes with a `mesh_attribute` texture (HAR_SCENE_ATTR), MODE_PRB_ADJOINT: where the vertex looks attributes up (face, barycentrics of si.p) -- what
+     * uv_x / uv_y are for a bitmap; the in-place commit deposits through it */
+    AttrAddr attr;
 };
 #define HAR_EXTRA_GROUPS 5
 
@@ -161,6 +164,12 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     SurfInt si = hx ? compute_si_record(S, st.d, hit.t, hit.u, hit.v, hx->gface, HAR_MATINFO_FLAGS(hx->matinfo), hit.shape, hit.inst)
                     : compute_si(S, st.d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
     const bool valid = si.valid();
+    /* scenes with a `mesh_attribute` texture: the face and the barycentrics of si.p (Mesh::barycentric_coordinates) for the lookups of this vertex; such a texture sits
+     * on top-level meshes only, so an instanced hit never reads the address */
+    AttrAddr addr; addr.face = 0u; addr.b1 = 0.f; addr.b2 = 0.f;
+    if ((TYPES & HAR_SCENE_ATTR) != 0u && valid && hit.inst == 0xffffffffu) addr = attr_addr(S, si.p, hit.prim, hit.shape);
+    const AttrAddr *const aa = (TYPES & HAR_SCENE_ATTR) != 0u ? &addr : nullptr;
+    if ((TYPES & HAR_SCENE_ATTR) != 0u && MODE == MODE_PRB_ADJOINT) R.attr = addr;
     DMesh M{};
     if (valid && hx) { M.bsdf = HAR_MATINFO_BSDF(hx->matinfo); M.emitter = HAR_MATINFO_EMITTER(hx->matinfo) ? S.meshes[si.mesh].emitter : -1; }
     else if (valid) M = S.meshes[si.mesh];
@@ -212,7 +221,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
             BsdfSide vs; R.non_null = true;
             if (bsdf_side(S, M.bsdf, si.wi, vs) && S.bsdfs[vs.index].type == BSDF_MASK) {
                 const DBsdf VB = S.bsdfs[vs.index];
-                TexTaps vt; const BsdfInputs vin = bsdf_inputs(S, VB, si.uv_x, si.uv_y, vt);
+                TexTaps vt; const BsdfInputs vin = bsdf_inputs(S, VB, si.uv_x, si.uv_y, vt, aa);
                 bool inside; const float o = mask_opacity(VB, vin, inside);
                 uint64_t r = rng; pcg32_next_float(r, inc); pcg32_next_float(r, inc);
                 R.non_null = pcg32_next_float(r, inc) < o;
@@ -228,7 +237,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     else side_ok = bsdf_side(S, M.bsdf, si.wi, side);
     const DBsdf B = S.bsdfs[side.index];
     TexTaps taps;
-    const BsdfInputs bin = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps);
+    const BsdfInputs bin = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps, aa);
 
     /* ---- emitter sampling (path.cpp:238-258, prb.py:163-175; scene.cpp:316-366).  The two samples are drawn by
      * every active lane; only BSDFs with a Smooth lobe use them (path.cpp:237, prb.py:169) */
@@ -301,9 +310,9 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     float s1 = pcg32_next_float(rng, inc);
     float s2x = pcg32_next_float(rng, inc), s2y = pcg32_next_float(rng, inc);
     BlendChildGrad cg;          /* blend vertex, prb: d value / d slot 0 of the two nested records (both passes of a backward step: the shadow-ray condition below reads it) */
-    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr);
+    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr, aa);
     BsdfSample bs; bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
-    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y);
+    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y, aa);
     if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH) R.non_null = !(mask && bs.type == LOBE_NULL);        /* path.cpp:307-308 (si is valid here) */
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
@@ -395,11 +404,14 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT) {
         /* Lr_ind = L * relative_grad(bsdf.eval(si, wo, active_next)) (prb.py:288-297): d/d slot0 = L * (df/dslot0) / f */
         Vec3 wo = si.to_local(wo_world);
-        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2, BsdfCtx(), si.uv_x, si.uv_y, (TYPES & HAR_SCENE_BLEND) != 0u ? &cg : nullptr);
+        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2, BsdfCtx(), si.uv_x, si.uv_y, (TYPES & HAR_SCENE_BLEND) != 0u ? &cg : nullptr, aa);
         R.rel_grad = Vec3(e2.value.x != 0.f ? e2.d_slot0.x / e2.value.x : 0.f, e2.value.y != 0.f ? e2.d_slot0.y / e2.value.y : 0.f,
                           e2.value.z != 0.f ? e2.d_slot0.z / e2.value.z : 0.f);
         R.ind_active = alive && (R.rel_grad.x != 0.f || R.rel_grad.y != 0.f || R.rel_grad.z != 0.f);
         R.bsdf = side.index; R.uv_x = si.uv_x; R.uv_y = si.uv_y;
+        /* forward mode of a scene with a `mesh_attribute` texture runs through items: a vertex whose record reads an attribute files the barycentrics in the uv words
+         * (the face comes from the replay cache, k_resolve_forward_attr) */
+        if ((TYPES & HAR_SCENE_ATTR) != 0u && (P.flags & HAR_SHADE_FORWARD_MODE) && B.texture >= 0 && (S.textures[B.texture].mode & HAR_TEX_ATTRIBUTE)) { R.uv_x = addr.b1; R.uv_y = addr.b2; }
         if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
             BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok && alive, wo, x);
             const Vec3 dv[5] = { x.d_alpha_u, x.d_alpha_v, x.d_eta, x.d_k, e2.d_slot1 };

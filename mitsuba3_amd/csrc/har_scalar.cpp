@@ -64,6 +64,7 @@ struct BoundScene {
         S.n_bsdfs = (uint32_t) hs.bsdfs.size(); S.n_insts = (uint32_t) hs.insts.size(); S.n_textures = (uint32_t) hs.textures.size();
         S.env_emitter = hs.env_emitter;
         S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+        for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) S.bsdf_types |= HAR_SCENE_ATTR;
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
         hs.bind_tables(S, hs.emitter_distr.data());
         if (hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) S.bsdf_types |= HAR_SCENE_ENVMAP;
@@ -116,7 +117,8 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         if (stats) { stats->vertices++; stats->closest_rays++; }   /* one loop iteration of PathIntegrator::sample: what the wavefront's bounce counters add up to */
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
-        shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
+        if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
+        else shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
         /* path.cpp:307-308; in a scene with a `mask` record the vertex decides (a null lobe does not make the sample valid: ShadeResult::non_null, which also follows the
          * scalar branch's early exit, :227-231, where HAR_SHADE_SCALAR_DRAWS is set) */
         valid_ray = valid_ray || ((S.bsdf_types & HAR_SCENE_MASK) ? R.non_null : hit.t != HAR_INF);
@@ -291,12 +293,39 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
             const bool act = !(active && !active[i]);
             Hit hit; hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
             if (act) { ScalarStack stack; accel_trace<false>(S.accel, O, D, maxt[i], hit, stack, status); }
-            aov_lane<HAR_SCENE_COMPOSITE>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            if (S.bsdf_types & HAR_SCENE_ATTR) aov_lane<HAR_SCENE_WIDEST>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            else aov_lane<HAR_SCENE_COMPOSITE>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
         }
         if (status) return har_set_error("har_aov_sample_host: traversal stack overflow");
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_aov_sample_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_aov_sample_host: ") + ex.what()); }
+}
+
+/* The lookup of a `mesh_attribute` record and its transpose on the host, by the functions the kernels run (attr_addr, attr_taps, attr_fetch, tap_weights): n hits on the
+ * record's mesh, face `prim[i]` at point p (3 x n).  value (3 x n, may be NULL) = the looked-up colour; with g (3 x n) and grad (rows x 3, ACCUMULATED into) the deposit of
+ * the in-place commit: grad[row_k] += g * b_k * scale for the three rows of the lookup (a face attribute: its row, weight scale) */
+extern "C" int har_attribute_lookup_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const uint32_t *prim, const float *p, float *value, const float *g, float *grad) {
+    try {
+        if (!desc || (n && (!prim || !p)) || (!g != !grad)) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (texture >= B.hs.textures.size() || !(B.hs.textures[texture].mode & HAR_TEX_ATTRIBUTE)) return har_set_error("mesh_attribute: not a HAR_TEX_MESH_ATTRIBUTE record");
+        const DScene &S = B.ds; const DTexture T = S.textures[texture]; const uint32_t shape = B.hs.textures[texture].mesh;
+        for (uint32_t i = 0; i < n; ++i) {
+            if (prim[i] >= S.meshes[shape].face_count) return har_set_error("mesh_attribute: face index out of bounds");
+            const AttrAddr a = attr_addr(S, Vec3(p[i], p[n + i], p[2 * (size_t) n + i]), prim[i], shape);
+            TexTaps taps; attr_taps(S, T, a, taps);
+            if (value) { const Vec3 v = attr_fetch(T, taps); value[i] = v.x; value[n + i] = v.y; value[2 * (size_t) n + i] = v.z; }
+            if (grad) {
+                float w[4]; tap_weights(taps, true, w);
+                for (int k = 0; k < 3; ++k) for (int c = 0; c < 3; ++c) grad[3 * (size_t) taps.idx[k] + c] += g[c * (size_t) n + i] * w[k];
+            }
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_attribute_lookup_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_attribute_lookup_host: ") + ex.what()); }
 }
 
 /* BSDF::eval_pdf / BSDF::sample of record `bsdf` of a scene on the host: the functions k_api_bsdf_eval_pdf / k_api_bsdf_sample run per lane (bsdf_side, bsdf_inputs,
@@ -317,6 +346,7 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
         if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
         B.bind();
         if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
         BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
         if (n == 0) return 0;
         if (!wi || !uv || !wo) return har_set_error("null input arrays");
@@ -343,6 +373,7 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
         if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
         B.bind();
         if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
         BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
         if (n == 0) return 0;
         if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return har_set_error("null input / output arrays");

@@ -15,6 +15,11 @@ struct DMesh    { uint32_t voff, foff, bsdf; int32_t emitter; uint32_t flags, fa
 /* mode: HarTexture::mode (bit 0 nearest, bit 1 mirror, bit 2 clamp), bit 31 (HAR_TEX_HAS_UV_XF): `uvm` is not the identity; uvm = BitmapTexture's `to_uv`
  * (bitmap.cpp:175), row-major 2 x 3 -- tex_taps applies it to the surface's uv before the lookup (bitmap.cpp:565,792,831,847) */
 #define HAR_TEX_HAS_UV_XF 0x80000000u
+/* bit 3 (HAR_TEX_ATTRIBUTE): not a bitmap but an attribute of ONE mesh (the `mesh_attribute` texture, src/textures/mesh_attribute.cpp): `data` = h rows of three floats
+ * (w = 1; a one-channel attribute is stored three times), one row per vertex -- or, with bit 4 (HAR_TEX_ATTRIBUTE_FACE), per face -- of that mesh; pad = the mesh's first
+ * face in DScene::faces, uvm[0] = `scale`.  Looked up by attr_taps / attr_fetch from an AttrAddr, never from a uv */
+#define HAR_TEX_ATTRIBUTE 8u
+#define HAR_TEX_ATTRIBUTE_FACE 16u
 struct DTexture { const float *data; uint32_t w, h; uint32_t mode, pad; float uvm[6]; };
 /* type 0: AreaLight on a rectangle (to_world, normal, inv_area, mesh); type 1: ConstantBackgroundEmitter
  * (src/emitters/constant.cpp): to_world[0..2] = bounding sphere centre, to_world[3] = radius, mesh = 0xffffffff; type 2: environment map
@@ -344,17 +349,65 @@ HAR_HD Vec3 tex_fetch(const DTexture &T, const TexTaps &l) {
     }
     return Vec3(out[0], out[1], out[2]);
 }
-/* Texture::eval for `reflectance`: srgb constant (src/spectra/srgb.cpp) or bitmap */
-HAR_HD Vec3 bsdf_reflectance(const DScene &S, const DBsdf &B, float u, float v, TexTaps &taps) {
+/* ---- the `mesh_attribute` texture (src/textures/mesh_attribute.cpp -> Mesh::eval_attribute*, src/render/mesh.cpp:2464-2631).  Where a hit looks an attribute up:
+ * `face` = the face's index in DScene::faces (the mesh's first face + si.prim_index), (b1, b2) = Mesh::barycentric_coordinates(si) (mesh.cpp:2227-2251): the
+ * least-squares solve of si.p against the face's vertex positions, NOT the hit's prim_uv.  Filled by attr_addr in the kernels of scenes with such a texture only. */
+struct AttrAddr { uint32_t face; float b1, b2; };
+HAR_HD uint32_t min_u32(uint32_t a, uint32_t b) { return a < b ? a : b; }       /* (rows are clamped to the record: no lookup or deposit leaves it, whatever the caller bound) */
+HAR_HD AttrAddr attr_addr(const DScene &S, Vec3 p, uint32_t prim, uint32_t shape) {
+    AttrAddr a; a.face = S.meshes[shape].foff + prim;
+    const uint32_t *f = S.faces + 4 * (size_t) a.face; const uint32_t voff = S.meshes[shape].voff;
+    const float *v0 = S.verts + 8 * (size_t) (voff + f[0]), *v1 = S.verts + 8 * (size_t) (voff + f[1]), *v2 = S.verts + 8 * (size_t) (voff + f[2]);
+    const Vec3 p0(v0[0], v0[1], v0[2]), rel = p - p0, du = Vec3(v1[0], v1[1], v1[2]) - p0, dv = Vec3(v2[0], v2[1], v2[2]) - p0;
+    const float b1 = dot3(du, rel), b2 = dot3(dv, rel), a11 = dot3(du, du), a12 = dot3(du, dv), a22 = dot3(dv, dv);
+    const float inv_det = rcp_(fms_(a11, a22, a12 * a12));
+    a.b1 = fms_(a22, b1, a12 * b2) * inv_det; a.b2 = fnma_(a12, b1, a11 * b2) * inv_det;
+    return a;
+}
+/* the rows and weights of Mesh::interpolate_attribute (mesh.cpp:2470-2515) in a TexTaps: idx[0..2] = the three rows (a face attribute: its row three times, weights
+ * 1, 0, 0), w0x / w1x / w0y = b0 / b1 / b2, w1y = `scale`; idx[3] repeats row 0 and carries no weight (tap_weights) */
+HAR_HD void attr_taps(const DScene &S, const DTexture &T, const AttrAddr &a, TexTaps &l) {
+    l.w1y = T.uvm[0];
+    if (T.mode & HAR_TEX_ATTRIBUTE_FACE) {
+        const uint32_t row = min_u32(a.face - T.pad, T.h - 1u);
+        l.idx[0] = l.idx[1] = l.idx[2] = l.idx[3] = row; l.w0x = 1.f; l.w1x = 0.f; l.w0y = 0.f;
+        return;
+    }
+    const uint32_t *f = S.faces + 4 * (size_t) a.face;
+    l.idx[0] = min_u32(f[0], T.h - 1u); l.idx[1] = min_u32(f[1], T.h - 1u); l.idx[2] = min_u32(f[2], T.h - 1u); l.idx[3] = l.idx[0];
+    l.w0x = 1.f - a.b1 - a.b2; l.w1x = a.b1; l.w0y = a.b2;
+}
+/* fmadd(a0, b0, fmadd(a1, b1, a2 * b2)) (mesh.cpp:2495-2497) times `scale` (mesh_attribute.cpp eval) */
+HAR_HD Vec3 attr_fetch(const DTexture &T, const TexTaps &l) {
+    float out[3];
+    for (int c = 0; c < 3; ++c) {
+        const float a0 = T.data[3 * (size_t) l.idx[0] + c], a1 = T.data[3 * (size_t) l.idx[1] + c], a2 = T.data[3 * (size_t) l.idx[2] + c];
+        out[c] = fma_(a0, l.w0x, fma_(a1, l.w1x, a2 * l.w0y)) * l.w1y;
+    }
+    return Vec3(out[0], out[1], out[2]);
+}
+/* d value / d (row idx[k]) of a lookup: the four bilinear products, or -- `attribute` -- the three barycentric weights times `scale` */
+HAR_HD void tap_weights(const TexTaps &l, bool attribute, float w[4]) {
+    if (attribute) { w[0] = l.w0x * l.w1y; w[1] = l.w1x * l.w1y; w[2] = l.w0y * l.w1y; w[3] = 0.f; return; }
+    w[0] = l.w0x * l.w0y; w[1] = l.w1x * l.w0y; w[2] = l.w0x * l.w1y; w[3] = l.w1x * l.w1y;
+}
+/* the taps of texture record T at a vertex: an attribute record from `aa` (null in every kernel of a scene without one: the branch folds away), a bitmap from (u, v) */
+HAR_HD bool tex_taps_at(const DScene &S, const DTexture &T, float u, float v, const AttrAddr *aa, TexTaps &l) {
+    if (aa && (T.mode & HAR_TEX_ATTRIBUTE)) { attr_taps(S, T, *aa, l); return true; }
+    tex_taps(T, u, v, l);
+    return false;
+}
+/* Texture::eval for `reflectance`: srgb constant (src/spectra/srgb.cpp), bitmap or mesh attribute */
+HAR_HD Vec3 bsdf_reflectance(const DScene &S, const DBsdf &B, float u, float v, TexTaps &taps, const AttrAddr *aa = nullptr) {
     if (B.texture < 0) return Vec3(B.r, B.g, B.b);
     const DTexture T = S.textures[B.texture];
-    tex_taps(T, u, v, taps);
+    if (tex_taps_at(S, T, u, v, aa, taps)) return attr_fetch(T, taps);
     return tex_fetch(T, taps);
 }
 /* evaluated colour parameters of a BSDF record at (u, v) */
-HAR_HD BsdfInputs bsdf_inputs(const DScene &S, const DBsdf &B, float u, float v, TexTaps &taps) {
+HAR_HD BsdfInputs bsdf_inputs(const DScene &S, const DBsdf &B, float u, float v, TexTaps &taps, const AttrAddr *aa = nullptr) {
     BsdfInputs in;
-    in.slot0 = bsdf_reflectance(S, B, u, v, taps);
+    in.slot0 = bsdf_reflectance(S, B, u, v, taps, aa);
     in.slot1 = Vec3(B.r2, B.g2, B.b2);
     in.table = B.table >= 0 ? S.bsdf_tables + B.table : nullptr;      /* (a blend record keeps a record index there: its `table` is never read) */
     return in;
@@ -404,7 +457,7 @@ HAR_HD float blend_weight(const DBsdf &B, const BsdfInputs &in, bool &inside) {
 struct BlendChildGrad { Vec3 d[2]; };
 /* eval / pdf / eval_pdf (:162-222).  e.d_slot0 = d value / d weight = v1 - v0 where the weight is not clipped (with a component selected: +/- the nested value) */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr, const AttrAddr *aa = nullptr) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bool inside; const float w = blend_weight(B, in, inside);
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
@@ -415,7 +468,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const float k = first ? 1.f - w : w;
         const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
         bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, e, ctx2);
         const Vec3 nv = e.value;
         if (cg) cg->d[first ? 0 : 1] = e.d_slot0 * k;
@@ -429,7 +482,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
 #endif
     for (int k = 0; k < 2; ++k) {
         const DBsdf &N = S.bsdfs[child[k]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
         BsdfEval ne; bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, ne, ctx);
         val[k] = ne.value; pdf[k] = ne.pdf;
         if (cg) cg->d[k] = ne.d_slot0 * (k == 0 ? 1.f - w : w);
@@ -441,7 +494,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
 /* sample (:108-160): sample1 > w takes nested BSDF 0 with (sample1 - w) / (1 - w), otherwise BSDF 1 with sample1 / w; the other one is evaluated at the sampled direction.
  * eta, sampled_type and sampled_component are the sampled BSDF's own (not offset, as in the reference); delta lobes go through the same arithmetic. */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx, const AttrAddr *aa = nullptr) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bool inside; const float w = blend_weight(B, in, inside);
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
@@ -450,7 +503,7 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
         const bool first = ctx.component < n0;
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
         bsdf_sample_one<LEAF, CTX>(N, nin, wi, s1, s2x, s2y, bs, ctx2);
         bs.weight = bs.weight * (first ? 1.f - w : w);
         return;
@@ -460,9 +513,9 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
     if (!m0 && !m1) return;
     const DBsdf &Ns = S.bsdfs[child[m0 ? 0 : 1]], &No = S.bsdfs[child[m0 ? 1 : 0]];
     TexTaps taps;
-    const BsdfInputs sin = bsdf_inputs(S, Ns, u, v, taps);
+    const BsdfInputs sin = bsdf_inputs(S, Ns, u, v, taps, aa);
     bsdf_sample_one<LEAF, CTX>(Ns, sin, wi, m0 ? (s1 - w) / (1.f - w) : s1 / w, s2x, s2y, bs, ctx);
-    const BsdfInputs oin = bsdf_inputs(S, No, u, v, taps);
+    const BsdfInputs oin = bsdf_inputs(S, No, u, v, taps, aa);
     BsdfEval eo; bsdf_eval_pdf_one<LEAF, CTX>(No, oin, wi, bs.wo, eo, ctx);
     /* :138-141 / :150-153: weight is nested BSDF 1's share in both branches */
     const float pdf_weighted = m0 ? w * eo.pdf + (1.f - w) * bs.pdf : w * bs.pdf + (1.f - w) * eo.pdf;
@@ -485,7 +538,7 @@ HAR_HD uint32_t mask_null_index(const DScene &S, const DBsdf &B) {
 /* eval / pdf / eval_pdf (:169-217): the nested value times the opacity; the pdf is 0 when the context leaves the nested components out and is scaled by the opacity only
  * when the null lobe is enabled.  e.d_slot0 = d value / d opacity = the nested value where the opacity is not clipped; cg->d[0] = d value / d (slot 0 of the nested LEAF) */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr, const AttrAddr *aa = nullptr) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bool inside; const float o = mask_opacity(B, in, inside);
     bool transmission = true, nested = true;
@@ -498,7 +551,7 @@ HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in,
     BsdfSide ns;
     if (bsdf_side(S, B.pad, wi, ns)) {
         const DBsdf &N = S.bsdfs[ns.index];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
         bsdf_eval_pdf_one<LEAF, CTX>(N, nin, ns.wi, Vec3(wo.x, wo.y, wo.z * ns.wo_sign), ne, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
     }
     e.value = ne.value * o;
@@ -509,7 +562,7 @@ HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in,
 /* sample (:121-167): sample1 < o takes the nested BSDF with sample1 / o -- its weight, type, component and eta as they are, its pdf times o --, otherwise the null lobe:
  * wo = -wi (the vertex's own wi, not the mirrored one), pdf = 1 - o, weight = 1, eta = 1.  A context that enables only one of the two makes o 1 or 0. */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx, const AttrAddr *aa = nullptr) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
     bool inside; float o = mask_opacity(B, in, inside);
@@ -523,7 +576,7 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
         BsdfSide ns;
         if (!bsdf_side(S, B.pad, wi, ns)) return;
         const DBsdf &N = S.bsdfs[ns.index];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
         bsdf_sample_one<LEAF, CTX>(N, nin, ns.wi, s1 / o, s2x, s2y, bs, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
         bs.wo.z *= ns.wo_sign; bs.pdf *= o;
         return;
@@ -534,14 +587,14 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
 /* (u, v): the vertex's texture coordinates -- read only by the kernels of blend / mask scenes, whose nested records look up their own colour inputs there */
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx(), float u = 0.f, float v = 0.f,
-                          BlendChildGrad *cg = nullptr) {
+                          BlendChildGrad *cg = nullptr, const AttrAddr *aa = nullptr) {
     if (!side_ok) { e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f); if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); } return; }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) {
-        blend_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        blend_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg, aa);
         return;
     }
     if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) {
-        mask_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        mask_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg, aa);
         return;
     }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
@@ -554,10 +607,10 @@ HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInp
 }
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx = BsdfCtx(),
-                        float u = 0.f, float v = 0.f) {
+                        float u = 0.f, float v = 0.f, const AttrAddr *aa = nullptr) {
     if (!side_ok) { bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u; return; }
-    if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
-    else if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) mask_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
+    if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
+    else if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) mask_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
     else bsdf_sample_one<(TYPES & ~HAR_SCENE_COMPOSITE), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
     bs.wo.z *= side.wo_sign;
 }

@@ -86,6 +86,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
     D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
     if (hs.has_envmap || hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) D.bsdf_types |= HAR_SCENE_ENVMAP;
     for (const DEmitter &e : hs.emitters) if (e.type == 7u) D.bsdf_types |= HAR_SCENE_TEXLIGHT;      /* (has_mesh_emitters is set with it: the generic emitter kernels + the texel-distribution code) */
+    for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) D.bsdf_types |= HAR_SCENE_ATTR;      /* a `mesh_attribute` texture: the widest set that also looks attributes up */
     /* the depth-first bound of the BVH must fit the traversal stacks (LDS entries + HBM spill columns): a deeper scene is refused here instead of
      * rendering with rays that overflow (an overflowing ray is a miss + a status word that only har_render_stats reads) */
     const uint32_t stack_cap = (uint32_t) std::min(HAR_LDS_STACK_DEPTH, HAR_LDS_STACK_SMALL + HAR_STACK_SPILL);
@@ -301,6 +302,13 @@ int har_scene_set_emitter_sampling_weights(HarScene S, const float *weights, uin
 int har_scene_set_texture_to_uv(HarScene S, uint32_t tex, const float to_uv[6]) {
     if (!S || tex >= S->hs.textures.size() || !to_uv) return fail("invalid texture index");
     HostTexture &t = S->hs.textures[tex];
+    if (t.mode & HAR_TEX_ATTRIBUTE) {          /* a `mesh_attribute` record keeps its `scale` there (MeshAttribute::traverse: "scale") */
+        if (!std::isfinite(to_uv[0])) return fail("mesh_attribute: `scale` must be finite");
+        t.uvm[0] = to_uv[0];
+        const DTexture d = S->hs.device_texture(tex, S->tex_dev[tex]);
+        HIP_TRY(hipMemcpy(S->d_textures + tex, &d, sizeof(DTexture), hipMemcpyHostToDevice));
+        return 0;
+    }
     const float id6[6] = { 1.f, 0.f, 0.f, 0.f, 1.f, 0.f };
     bool zero = true, ident = true;
     for (int k = 0; k < 6; ++k) { if (!std::isfinite(to_uv[k])) return fail("HarTexture::to_uv must be finite"); zero = zero && to_uv[k] == 0.f; ident = ident && to_uv[k] == id6[k]; }
@@ -760,6 +768,7 @@ static int lower_ctx(const HarBSDFContext *ctx, BsdfCtx &out) {
 static int bsdf_eval_common(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                             float *value, float *pdf, void *stream) {
     if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
+    if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::eval / pdf see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
     BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
     if (n == 0) return 0;
     if (!wi || !uv || !wo) return fail("null wi / uv / wo");
@@ -783,6 +792,7 @@ int har_bsdf_pdf(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t 
 int har_bsdf_sample(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1, const float *sample2,
                     const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component, void *stream) {
     if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
+    if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::sample sees a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
     BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
     if (n == 0) return 0;
     if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return fail("null input / output arrays");

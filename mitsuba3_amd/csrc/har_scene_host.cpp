@@ -227,6 +227,7 @@ void update_roughplastic_sampling_weight(HostScene &hs, uint32_t index) {
         const HostTexture &t = hs.textures[b.texture];
         double acc = 0; for (float v : t.data) acc += v;
         d_mean = (float) (acc / (double) t.data.size());
+        if (t.mode & HAR_TEX_ATTRIBUTE) d_mean *= t.uvm[0];      /* a mesh attribute: the mean of its rows times `scale` (the reference's MeshAttribute has no mean(): unpinned, docs/parity.md) */
     } else d_mean = (b.r + b.g + b.b) / 3.f;             /* SRGBReflectanceSpectrum::mean, srgb.cpp:117-122 */
     float s_mean = (b.r2 + b.g2 + b.b2) / 3.f;
     b.spec_sampling_weight = s_mean / (d_mean + s_mean);
@@ -326,6 +327,20 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     for (uint32_t i = 0; i < d.texture_count; ++i) {
         const HarTexture &t = d.textures[i];
         if (!t.data || !t.width || !t.height) { err = "empty texture"; return false; }
+        if (t.mode & HAR_TEX_MESH_ATTRIBUTE) {
+            /* an attribute of mesh `reserved` (the `mesh_attribute` texture): rows x 3 floats, one row per vertex or per face of that mesh, `scale` in to_uv[0] */
+            if ((t.mode & ~(uint32_t) (HAR_TEX_MESH_ATTRIBUTE | HAR_TEX_ATTRIBUTE_PER_FACE)) != 0u || t.width != 1u) { err = "mesh_attribute: a HAR_TEX_MESH_ATTRIBUTE record has width 1 and no filter / wrap bits"; return false; }
+            if (t.reserved >= d.mesh_count) { err = "mesh_attribute: the record names a mesh that does not exist"; return false; }
+            if (t.reserved >= d.top_mesh_count) { err = "mesh_attribute: mesh " + std::to_string(t.reserved) + " lies inside a shapegroup; a `mesh_attribute` texture on an instanced mesh is not supported"; return false; }
+            const HarMesh &m = d.meshes[t.reserved];
+            const uint32_t rows = (t.mode & HAR_TEX_ATTRIBUTE_PER_FACE) ? m.face_count : m.vertex_count;
+            if (t.height != rows) { err = "mesh_attribute: the record holds " + std::to_string(t.height) + " rows, mesh " + std::to_string(t.reserved) + " has " + std::to_string(rows) + ((t.mode & HAR_TEX_ATTRIBUTE_PER_FACE) ? " faces" : " vertices"); return false; }
+            if (!std::isfinite(t.to_uv[0])) { err = "mesh_attribute: `scale` must be finite"; return false; }
+            HostTexture ht; ht.w = 1u; ht.h = t.height; ht.mode = t.mode; ht.mesh = t.reserved; ht.data.assign(t.data, t.data + 3 * (size_t) t.height);
+            ht.uvm[0] = t.to_uv[0];
+            hs.textures.push_back(std::move(ht));
+            continue;
+        }
         if ((t.mode & ~7u) != 0u || (t.mode & 6u) == 6u) { err = "HarTexture::mode: HAR_TEX_BILINEAR / _NEAREST combined with HAR_TEX_REPEAT / _MIRROR / _CLAMP"; return false; }
         HostTexture ht; ht.w = t.width; ht.h = t.height; ht.mode = t.mode; ht.data.assign(t.data, t.data + 3 * (size_t) t.width * t.height);
         bool zero = true, ident = true;          /* to_uv (bitmap.cpp:175): six zeros = the identity of a zero-initialised record */
@@ -389,6 +404,33 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             p.inv_eta_2 = 1.f / (p.eta * p.eta);
             p.internal_reflectance = fresnel_diffuse_reflectance(1.f / p.eta);
             update_roughplastic_sampling_weight(hs, i);
+        }
+    }
+    /* a `mesh_attribute` record belongs to ONE mesh: every BSDF record that reads it is reachable from that mesh alone (its record, the back side of a `twosided`, the
+     * records nested in a blend / mask and their back sides) -- a lookup never reads another shape's rows */
+    {
+        bool any = false; for (const HostTexture &t : hs.textures) any = any || (t.mode & HAR_TEX_MESH_ATTRIBUTE) != 0u;
+        if (any) {
+            for (uint32_t m = 0; m < d.mesh_count; ++m) {
+                std::vector<int32_t> todo{ (int32_t) d.meshes[m].bsdf };
+                for (size_t k = 0; k < todo.size(); ++k) {          /* (nested composites are refused above: a tree holds at most seven records) */
+                    if (todo.size() > 64) { err = "mesh_attribute: the BSDF tree of mesh " + std::to_string(m) + " is too deep to validate"; return false; }
+                    const int32_t r = todo[k];
+                    if (r < 0 || r >= (int32_t) d.bsdf_count) continue;
+                    const HarBSDF &b = d.bsdfs[r];
+                    if (b.texture >= 0 && (hs.textures[b.texture].mode & HAR_TEX_MESH_ATTRIBUTE)) {
+                        if (hs.textures[b.texture].mesh != m) { err = "mesh_attribute: BSDF record " + std::to_string(r) + " reads an attribute of mesh " + std::to_string(hs.textures[b.texture].mesh) + " but is carried by mesh " + std::to_string(m) + " (one record per BSDF and shape)"; return false; }
+                    }
+                    if ((b.flags & BF_TWOSIDED) && b.back >= 0) todo.push_back(b.back);
+                    if (b.type == BSDF_BLEND) { todo.push_back(b.nested[0]); todo.push_back(b.nested[1]); }
+                    if (b.type == BSDF_MASK) todo.push_back(b.nested[0]);
+                }
+            }
+            for (uint32_t i = 0; i < d.emitter_count; ++i) {
+                const HarEmitter &e = d.emitters[i];
+                const uint32_t t = e.type == 2u ? e.mesh : e.type == 7u ? e.radiance_texture : 0xffffffffu;
+                if (t < hs.textures.size() && (hs.textures[t].mode & HAR_TEX_MESH_ATTRIBUTE)) { err = "mesh_attribute: an emitter cannot read a mesh attribute (area `radiance`, envmap)"; return false; }
+            }
         }
     }
     /* a `twosided` whose back side is a blend: that record's nested BSDFs must not transmit either */

@@ -9,7 +9,8 @@
 
 namespace har {
 
-struct HostTexture { std::vector<float> data; uint32_t w, h, mode = 0; float uvm[6] = { 1.f, 0.f, 0.f, 0.f, 1.f, 0.f }; };      /* mode carries HAR_TEX_HAS_UV_XF when uvm is not the identity */
+static_assert(HAR_TEX_ATTRIBUTE == HAR_TEX_MESH_ATTRIBUTE && HAR_TEX_ATTRIBUTE_FACE == HAR_TEX_ATTRIBUTE_PER_FACE, "DTexture::mode carries the bits of HarTexture::mode");
+struct HostTexture { std::vector<float> data; uint32_t w, h, mode = 0; float uvm[6] = { 1.f, 0.f, 0.f, 0.f, 1.f, 0.f }; uint32_t mesh = 0; };      /* HAR_TEX_ATTRIBUTE records: `mesh` = the mesh they belong to, uvm[0] = scale */      /* mode carries HAR_TEX_HAS_UV_XF when uvm is not the identity */
 
 /* one bottom-level BVH: its nodes are the range [root, root + node_count) of HostScene::nodes (the root first, children behind their parents), its triangle records
  * [first_tri, first_tri + tri_count); refit order = its nodes sorted by depth, deepest first (level_begin[l] .. level_begin[l + 1] of HostScene::refit_order) */
@@ -48,7 +49,7 @@ struct HostScene {
         if (D.emitter0_valid) D.emitter0 = emitters[0];
     }
     DTexture device_texture(size_t i, const float *data_ptr) const {
-        const HostTexture &t = textures[i]; DTexture d{ data_ptr, t.w, t.h, t.mode, 0u, { t.uvm[0], t.uvm[1], t.uvm[2], t.uvm[3], t.uvm[4], t.uvm[5] } };
+        const HostTexture &t = textures[i]; DTexture d{ data_ptr, t.w, t.h, t.mode, (t.mode & HAR_TEX_ATTRIBUTE) ? meshes[t.mesh].foff : 0u, { t.uvm[0], t.uvm[1], t.uvm[2], t.uvm[3], t.uvm[4], t.uvm[5] } };
         return d;
     }
     uint32_t root = 0;
