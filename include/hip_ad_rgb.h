@@ -39,7 +39,7 @@ typedef struct HarMesh {
     uint32_t vertex_count, face_count;
     uint32_t bsdf;      /* index into HarSceneDesc::bsdfs */
     int32_t  emitter;   /* index into HarSceneDesc::emitters, or -1 */
-    uint32_t flags;     /* bit0: has vertex normals, bit1: has texcoords */
+    uint32_t flags;     /* bit0: has vertex normals, bit1: has texcoords; bit2 / bit3: HAR_MESH_TANGENT_FRAME / HAR_MESH_FRAME_FLIPPED (below, read for meshes under a `normalmap`) */
     uint32_t reserved;
 } HarMesh;
 
@@ -73,6 +73,18 @@ typedef struct HarInstance {
  * MAY carry the twosided flag, with one or two BSDFs; a nested blend / mask, a mask inside a blend and HAR_BSDF_TWOSIDED on the mask record itself are refused.  `path`
  * counts a camera sample as valid when a non-null lobe was sampled at one of its vertices (path.cpp:307-308).  Gradients (`prb`): the opacity's in the record's own row /
  * bitmap, the nested leaf record's colour slot 0 in its own; the refusals of a blend scene hold for a scene with a mask record as well.
+ *   type 8 normalmap       (src/bsdfs/normalmap.cpp)       slot0 = the normal map: a constant rgb or a THREE-channel bitmap; `nested[0]` = the nested BSDF record
+ * A normalmap record evaluates nested[0] in the shading frame perturbed by n = normalize(2 * slot0 - 1) (frame(), normalmap.cpp:224-244; HAR_BSDF_NM_FLIP =
+ * `flip_invalid_normals`), drops directions for which cos_theta(wo) and cos_theta(wo') disagree in sign and scales values and sample weights by the shadow terminator of
+ * normalmap_helpers.h (HAR_BSDF_NM_SHADOW = `use_shadowing_function`).  nested[0] is a leaf record (types 0 - 5) that MAY carry the twosided flag (bsdf_side sees the PERTURBED
+ * wi); HAR_BSDF_TWOSIDED on the normalmap record itself is `twosided(normalmap(X))` (`back` must be -1 there: the two-BSDF form over a normalmap is refused, as is a dielectric
+ * under it).  A blend / mask / normalmap nested in a normalmap, a normalmap nested in a blend / mask, HAR_BSDF_MONO and a scene that also holds a `mesh_attribute` texture are
+ * refused.  The perturbation is relative to the shading frame: a mesh under such a record with vertex normals AND texcoords must carry HAR_MESH_TANGENT_FRAME -- its frame is
+ * s = the face's dp_du orthogonalised against the shading normal, t = cross(n, s), negated with HAR_MESH_FRAME_FLIPPED xor a mirroring instance transform (interaction.h:570-598,
+ * instance.cpp:218-222); only shapes whose per-vertex tangent IS the direction of dp_du (a `rectangle`) may set it, every other such mesh is refused ("per-vertex tangents").
+ * Meshes without normals or without texcoords keep coordinate_system(n).  Gradients (`prb`): the normal map's in the record's own row / bitmap -- d / d (looked-up colour)
+ * through 2c - 1, the flip, normalize, the frame, the nested model's directional partials and the shadow term, scattered through the bitmap's taps --, the nested leaf
+ * record's colour slot 0 in its own; the refusals of a blend scene hold for a scene with a normalmap record as well, and har_render_forward is refused.
  * flags: bit0 twosided (src/bsdfs/twosided.cpp; `back` = record used for the back side, -1 = the same one),
  *        bit1 GGX distribution (else Beckmann), bit2 sample_visible, bit3 plastic / roughplastic `nonlinear`. */
 #define HAR_BSDF_DIFFUSE        0
@@ -83,11 +95,16 @@ typedef struct HarInstance {
 #define HAR_BSDF_PLASTIC        5
 #define HAR_BSDF_BLEND          6
 #define HAR_BSDF_MASK           7
+#define HAR_BSDF_NORMALMAP      8
 #define HAR_BSDF_TWOSIDED       1u
 #define HAR_BSDF_GGX            2u
 #define HAR_BSDF_SAMPLE_VISIBLE 4u
 #define HAR_BSDF_NONLINEAR      8u
 #define HAR_BSDF_MONO           16u     /* blend / mask: the weight / opacity bitmap has one channel */
+#define HAR_BSDF_NM_FLIP        64u     /* normalmap: flip_invalid_normals */
+#define HAR_BSDF_NM_SHADOW      128u    /* normalmap: use_shadowing_function */
+#define HAR_MESH_TANGENT_FRAME  4u      /* HarMesh::flags: under a `normalmap` the frame's s follows the face's dp_du (a rectangle) */
+#define HAR_MESH_FRAME_FLIPPED  8u      /* HarMesh::flags: SurfaceInteraction::frame_flipped of the shape (to_world mirrors, flip_normals included) */
 typedef struct HarBSDF {
     uint32_t type;
     int32_t  texture;     /* -1: constant slot0 (srgb), else bitmap index */
@@ -98,7 +115,7 @@ typedef struct HarBSDF {
     float    eta;                     /* int_ior / ext_ior */
     float    eta_c[3], k_c[3];        /* conductor: real and imaginary part of the relative IOR */
     int32_t  back;
-    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask: nested[0] (read for types 6 and 7 only) */
+    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask / normalmap: nested[0] (read for types 6 - 8 only) */
 } HarBSDF;
 
 /* BitmapTexture, raw H x W x 3 f32 (src/textures/bitmap.cpp:175-206). HOST pointer.  mode = filter_type | wrap_mode (bitmap.cpp:182-206):
@@ -692,6 +709,17 @@ int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFC
  * at the point p (3 x n).  value (3 x n, may be NULL) = the colour looked up; g (3 x n) with grad (rows x 3, ACCUMULATED into; both or neither) = the deposit of the adjoint:
  * grad[row_k] += g * b_k * scale over the lookup's three rows (a face attribute: its one row).  All pointers HOST. */
 int har_attribute_lookup_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const uint32_t *prim, const float *p, float *value, const float *g, float *grad);
+/* PreliminaryIntersection::compute_surface_interaction on the HOST (no GPU) for n given hits: d = the ray directions (3 x n), t / u / v / prim / shape / inst = the fields
+ * of har_ray_intersect_preliminary, `out` = the 33 x n rows of har_compute_surface_interaction.  Every lane runs the per-lane code that entry's kernel runs in a scene with
+ * a `normalmap` record (the tangent frame of shapes with HAR_MESH_TANGENT_FRAME in sh_frame.s / .t and wi); for every other shape that is the plain interaction.
+ * All pointers HOST; `active` (n bytes) may be NULL. */
+int har_surface_interaction_host(const HarSceneDesc *desc, uint32_t n, const float *d, const float *t, const float *u, const float *v, const uint32_t *prim,
+                                 const uint32_t *shape, const uint32_t *inst, uint32_t ray_flags, const uint8_t *active, float *out);
+/* The derivative of a normalmap record's value with respect to the looked-up normal-map colour, on the HOST (no GPU): for n tuples (wi 3 x n, uv 2 x n, wo 3 x n, A 3 x n)
+ * on record `bsdf` (type 8, possibly with HAR_BSDF_TWOSIDED), F = sum_k A_k value_k(wi, wo) under the default context and grad (3 x n) = dF / dc, c = the record's slot 0
+ * at uv: the chain through n_raw = 2c - 1, the flip (the branch taken), normalize, s, t, wi', wo', the nested model's directional partials and the shadow term (its
+ * min(., 1) takes the branch the value takes); the orientation test carries no derivative; delta models give zero.  value (n) may be NULL.  All pointers HOST. */
+int har_normalmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo, const float *A, float *value, float *grad);
 /* The AOV pass of AOVIntegrator::render (aov.cpp:389-470: one more SamplingIntegrator pass with the same sampler seed): lanes [lane_begin, lane_end) (0, 0 = all) of the
  * wavefront of render() at `seed` / `spp` -- the same lanes, film positions and camera rays as there -- accumulate into `aov_film` (DEVICE, H x W x (C + 1): the C
  * channels, then the reconstruction filter's weight; accumulated, not cleared, not developed).  `integrator` gives the chunk size (chunk_lanes) and the film window

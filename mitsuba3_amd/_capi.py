@@ -198,6 +198,8 @@ SIGNATURES = {
     "har_render_timing": (C.c_int, [vp, f32p, u32p]),
     "har_aov_channel_count": (C.c_int, [C.c_uint32, u32p, u32p]),
     "har_aov_sample": (C.c_int, [vp, C.c_uint32, vp, vp, vp, vp, C.c_uint32, u32p, vp, vp]),
+    "har_surface_interaction_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, f32p, u32p, u32p, u32p, C.c_uint32, vp, f32p]),
+    "har_normalmap_grad_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p]),
     "har_aov_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, vp, C.c_uint32, u32p, f32p]),
     "har_bsdf_eval_pdf_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, vp, f32p, f32p]),
     "har_bsdf_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, u32p, u32p]),

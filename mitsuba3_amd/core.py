@@ -596,7 +596,7 @@ def _cube(props):
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
-    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf',
+    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
@@ -1151,7 +1151,8 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 # BitmapTexture(props) (src/textures/bitmap.cpp:175-260); `raw` only silences a range warning for float data in RGB variants, `accel` picks Dr.Jit's texture
 # hardware path on CUDA (no effect on values), `format` = the storage type of the texels ("auto" / "variant" / "fp16": this path keeps float32)
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
-BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7}
+BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8}
+_NESTING_BSDFS = ('blendbsdf', 'mask', 'normalmap')          # records that name nested records: built by the plugin factory
 _WEIGHTED_BSDFS = ('blendbsdf', 'mask')          # records whose slot 0 is a scalar texture (Texture::eval_1): the blend weight, the mask opacity
 _LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
 # (parameter name of slot 0, default), (parameter name of slot 1, default)
@@ -1237,7 +1238,7 @@ class BSDF:
         props = props or {}
         self.id = id
         self.kind = props.get('type', 'diffuse')
-        if self.kind in _WEIGHTED_BSDFS:
+        if self.kind in _NESTING_BSDFS:
             raise RuntimeError("%s: built by the plugin factory (mi.load_dict), which resolves its nested BSDFs" % self.kind)
         if self.kind not in BSDF_TYPES:
             raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb" % self.kind)
@@ -1458,10 +1459,80 @@ def _mk_mask(props, named, key):
             nested = obj
     if nested is None:
         raise RuntimeError("Child BSDF not specified")
-    if nested.kind in _WEIGHTED_BSDFS or (nested.back is not None and nested.back.kind in _WEIGHTED_BSDFS):
+    if nested.kind in _NESTING_BSDFS or (nested.back is not None and nested.back.kind in _NESTING_BSDFS):
         raise RuntimeError("mask: a nested `%s` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models, or `twosided` over them)"
-                           % (nested.kind if nested.kind in _WEIGHTED_BSDFS else nested.back.kind))
+                           % (nested.kind if nested.kind in _NESTING_BSDFS else nested.back.kind))
     return MaskBSDF(props.get('opacity', 0.5), nested, id=key)
+
+
+class NormalMapBSDF(BSDF):
+    """NormalMap (src/bsdfs/normalmap.cpp:100-132): a BSDF record whose colour slot 0 is the `normalmap` texture -- an `rgb` colour or a three-channel raw `bitmap`, read by
+    Texture::eval_3 -- and which names ONE nested BSDF: a plain model, or a `twosided` over one or two of them; it becomes a record of its own (Scene._add_bsdf).
+    flags: 64 = flip_invalid_normals, 128 = use_shadowing_function (HAR_BSDF_NM_FLIP / _SHADOW), 1 = wrapped by a `twosided`."""
+
+    def __init__(self, normalmap, nested, flip_invalid_normals=True, use_shadowing_function=True, id=None):
+        self.id = id; self.kind = 'normalmap'; self.slot0_name = 'normalmap'; self.slot1_name = None
+        self.texture = None; self.tex_mode = 0; self.tex_to_uv = None
+        self.attr = None; self.attr_mesh = None
+        if isinstance(normalmap, dict) and normalmap.get('type') == 'rgb':
+            self.value = _rgb_value(normalmap, 0.5, bounded=False)
+        elif isinstance(normalmap, dict) and normalmap.get('type') == 'bitmap':
+            src = normalmap['data'] if 'data' in normalmap else (normalmap['bitmap'].data if isinstance(normalmap.get('bitmap'), Bitmap) else Bitmap(normalmap['filename']).data)
+            ch = 1 if len(tuple(src.shape)) == 2 else int(src.shape[2])
+            if ch != 3:
+                raise RuntimeError("normalmap: the `normalmap` bitmap has %d channel%s, expected 3 (a one-channel bitmap is not a normal map)" % (ch, "" if ch == 1 else "s"))
+            self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(normalmap)
+            self.value = _f32([0.5, 0.5, 1.0])
+        else:
+            raise RuntimeError("normalmap: `normalmap` is an `rgb` colour or a three-channel `bitmap` texture")
+        self.value2 = _f32([0, 0, 0]); self.flags = (64 if flip_invalid_normals else 0) | (128 if use_shadowing_function else 0)
+        self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
+        self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
+        self.scene = None; self.index = None
+        self.nested = [nested]
+        if getattr(nested, 'mask_parent', None) is None and nested.scene is None:
+            nested.mask_parent = self          # NAMES its parameters '<normalmap>.nested_bsdf.*' (NormalMap::traverse, normalmap.cpp:129-132): Scene._bsdf_key_base
+
+    def _own_lobes(self):
+        """the nested BSDF's components -- those of its `twosided`, if it is one (normalmap.cpp:117-122); BSDFFlags::NormalMapped marks the BSDF, not a lobe"""
+        n = self.nested[0]
+        return [n._lobe_flags(i) for i in range(n.component_count())]
+
+    # the record's flag word wherever it is read or written, BSDF::flags() / BSDF::flags(i) when called (as on a blend record)
+    @property
+    def flags(self):
+        return _RecordFlags(self._flags, self)
+
+    @flags.setter
+    def flags(self, value):
+        self._flags = int(value)
+
+
+def _mk_normalmap(props, named, key):
+    """the `normalmap` plugin: the `normalmap` texture, exactly one nested BSDF under a free name, `flip_invalid_normals` and `use_shadowing_function` (normalmap.cpp:100-115)"""
+    _check_props('normalmap', props, ('normalmap', 'flip_invalid_normals', 'use_shadowing_function'), children=('bsdf',))
+    nested = None
+    for k, v in props.items():
+        if k in ('type', 'id', 'normalmap', 'flip_invalid_normals', 'use_shadowing_function'):
+            continue
+        obj = _resolve(v, named, k) if isinstance(v, dict) else v
+        if isinstance(obj, BSDF):
+            if nested is not None:
+                raise RuntimeError("Only a single BSDF child object can be specified.")
+            nested = obj
+    if nested is None:
+        raise RuntimeError("Exactly one BSDF child object must be specified.")
+    if 'normalmap' not in props:
+        raise RuntimeError("Property \"normalmap\" has not been specified!")
+    if nested.kind in _NESTING_BSDFS or (nested.back is not None and nested.back.kind in _NESTING_BSDFS):
+        raise RuntimeError("normalmap: a nested `%s` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models, or `twosided` over them)"
+                           % (nested.kind if nested.kind in _NESTING_BSDFS else nested.back.kind))
+    if getattr(nested, 'attr', None) is not None or (nested.back is not None and getattr(nested.back, 'attr', None) is not None):
+        raise RuntimeError("normalmap: a `mesh_attribute` texture on the nested BSDF is not supported in hip_ad_rgb")
+    nm = props['normalmap']
+    if isinstance(nm, (list, tuple, np.ndarray)) and len(nm) == 3:
+        nm = {'type': 'rgb', 'value': [float(x) for x in nm]}
+    return NormalMapBSDF(nm, nested, bool(props.get('flip_invalid_normals', True)), bool(props.get('use_shadowing_function', True)), id=key)
 
 
 def _mk_blendbsdf(props, named, key):
@@ -1483,6 +1554,8 @@ def _mk_blendbsdf(props, named, key):
     for c in nested:
         if c.kind == 'mask':
             raise RuntimeError("blendbsdf: a nested `mask` is not supported in hip_ad_rgb (put the `mask` outside, over plain BSDF models)")
+        if c.kind == 'normalmap':
+            raise RuntimeError("blendbsdf: a nested `normalmap` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models)")
         if c.kind == 'blendbsdf' or (c.flags & 1):
             raise RuntimeError("blendbsdf: nested BSDFs must be plain BSDF models in this variant")
     return BlendBSDF(props['weight'], nested, id=key)
@@ -1490,7 +1563,7 @@ def _mk_blendbsdf(props, named, key):
 
 def _transmits(b):
     """does the BSDF have a transmission lobe (what `twosided` refuses, twosided.cpp:79-83)"""
-    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask'      # (BSDFFlags::Null is part of BSDFFlags::Transmission)
+    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask' or (b.kind == 'normalmap' and _transmits(b.nested[0]))      # (BSDFFlags::Null is part of BSDFFlags::Transmission; a normalmap has its nested BSDF's lobes)
 
 
 def _mk_twosided(props, named, key):
@@ -1508,6 +1581,8 @@ def _mk_twosided(props, named, key):
     for b in nested:
         if _transmits(b):
             raise RuntimeError("Only materials without a transmission component can be nested!")
+    if len(nested) == 2 and nested[1] is not nested[0] and any(b.kind == 'normalmap' for b in nested):
+        raise RuntimeError("twosided: two nested BSDFs with a `normalmap` among them are not supported in hip_ad_rgb (nest ONE normalmap: twosided(normalmap(X)))")
     front = nested[0]
     if front.flags & 1:
         raise RuntimeError("twosided: nested BSDF is already two-sided")
@@ -2019,7 +2094,7 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
                 raise RuntimeError("render_forward(): %s: expected a tangent of shape %s" % (k, (rows, dim)))
             for b in scene._attr_readers(mesh, name):
                 if id(b) in scene._blend_nested():
-                    raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` are not produced in hip_ad_rgb (the weight's / opacity's are; use render_backward)" % k)
+                    raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
                 if dim == 1:
                     t_tex[b.tex_index].copy_(v.expand(rows, 3).reshape(rows, 1, 3))
                 elif dim == 3 and b.kind not in _WEIGHTED_BSDFS:
@@ -2028,7 +2103,7 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
         kind, b = keys[k]
         v = torch.as_tensor(v, dtype=torch.float32, device=dev)
         if kind != "emit" and id(b) in scene._blend_nested():
-            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` are not produced in hip_ad_rgb (the weight's / opacity's are; use render_backward)" % k)
+            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
         if kind != "emit" and b.kind in _WEIGHTED_BSDFS:
             # the tangent of the weight, in every colour channel of the record's slot 0 (a three-channel bitmap: of its luminance)
             if kind == "tex" and b.weight_channels == 3:
@@ -2397,7 +2472,7 @@ class Scene:
     def _blend_nested(self):
         """ids of the BSDF objects whose record is nested in a blend record of this scene -- also one that a shape or another blend references besides"""
         out = {id(c) for b in self.bsdf_objs for c in getattr(b, 'nested', ())}
-        return out | {id(c.back) for b in self.bsdf_objs if b.kind == 'mask' for c in b.nested if c.back is not None}          # (mask: both sides of a nested `twosided` pair)
+        return out | {id(c.back) for b in self.bsdf_objs if b.kind in ('mask', 'normalmap') for c in b.nested if c.back is not None}          # (mask: both sides of a nested `twosided` pair)
 
     def _add_mesh(self, key, m):
         if m.bsdf is None:          # Shape(props), shape.cpp:50-57: a default diffuse BSDF -- black when the shape carries an emitter
@@ -2423,9 +2498,24 @@ class Scene:
             else:                         # any other triangle mesh: Mesh::sample_position (area-weighted face selection)
                 self.emitters[em] = dict(type=3, mesh=len(self.meshes), radiance=m.emitter, to_world=[0.0] * 12, normal=[0.0] * 3, inv_area=0.0,
                                          sampling_weight=getattr(m, 'emitter_weight', 1.0))
+        if m.bsdf.kind == 'normalmap' and (m.flags & 3) == 3 and not hasattr(m, 'rect'):
+            # the perturbation is relative to the shading frame, which such a mesh builds from packed per-vertex tangents in the reference (mesh.cpp:612-623, 1269-1350):
+            # rendering it with another frame would be a silent parity error
+            raise RuntimeError("normalmap: shape \"%s\" has vertex normals and texture coordinates -- under a `normalmap` its shading frame needs per-vertex tangents "
+                               "(Mesh::compute_tangents), which are not implemented in hip_ad_rgb; a `rectangle`, and meshes without vertex normals or without texture "
+                               "coordinates, are supported" % key)
         attrs = {k: np.ascontiguousarray(v, np.float32).copy() for k, v in getattr(m, 'attributes', {}).items()}
         self._bind_attributes(key, m.bsdf, attrs, len(self.meshes))
         self.meshes.append(dict(key=key, V=np.ascontiguousarray(m.V), F=np.ascontiguousarray(m.F), bsdf=bi, emitter=em, flags=m.flags, rect=getattr(m, 'rect', None), attributes=attrs))
+
+    def _tangent_flags(self, m):
+        """HAR_MESH_TANGENT_FRAME / HAR_MESH_FRAME_FLIPPED of a mesh under a `normalmap` (BSDFFlags::NormalMapped: the shape packs a tangent).  A rectangle's is the direction of
+        to_world * (1, 0, 0) at all four vertices (rectangle.cpp:131-153); its FaceUVFlipped bit is toggled by a mirroring to_world, the scale(1, 1, -1) of `flip_normals`
+        included (mesh.cpp:1160-1215).  Taken from the rectangle's current record, so it follows '<rectangle>.to_world' updates."""
+        if self.bsdf_objs[m["bsdf"]].kind != 'normalmap' or m.get("rect") is None:
+            return 0
+        det = float(np.linalg.det(np.asarray(m["rect"]["to_world"].matrix, np.float32)[:3, :3]))
+        return 4 | (8 if (det < 0.0) != bool(m["rect"].get("flip")) else 0)
 
     @staticmethod
     def _bsdf_tree(b):
@@ -2538,7 +2628,7 @@ class Scene:
         for i, m in enumerate(self.meshes):
             meshes[i].vertex_ptr = _fp(m["V"]); meshes[i].index_ptr = _up(m["F"])
             meshes[i].vertex_count = m["V"].shape[0]; meshes[i].face_count = m["F"].shape[0]
-            meshes[i].bsdf = m["bsdf"]; meshes[i].emitter = m["emitter"]; meshes[i].flags = m["flags"]
+            meshes[i].bsdf = m["bsdf"]; meshes[i].emitter = m["emitter"]; meshes[i].flags = m["flags"] | self._tangent_flags(m)
         groups = (M.HarShapeGroup * max(1, len(self.groups)))()
         for i, (a, b) in enumerate(self.groups):
             groups[i].first_mesh = a; groups[i].mesh_count = b
@@ -2556,7 +2646,7 @@ class Scene:
             bsdfs[i].back = b.back.index if b.back is not None else -1
             if b.kind == 'blendbsdf':
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, b.nested[1].index)
-            elif b.kind == 'mask':
+            elif b.kind in ('mask', 'normalmap'):
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, -1)
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
@@ -3852,7 +3942,7 @@ class DeviceGroup:
 # ---------------------------------------------------------------------------
 
 _REGISTRY = {}
-_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask')
+_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask', 'normalmap')
 
 
 def register_plugin(name, variant_name, instantiate):
@@ -3996,7 +4086,7 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
@@ -4059,7 +4149,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
     nested = [k for k in keys if k in scene._bsdf_param_keys() and id(scene._bsdf_param_keys()[k][1]) in scene._blend_nested()]
     if nested:
-        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` have no gradient in hip_ad_rgb (the `weight` / `opacity` and the nested BSDFs' colour slot 0 do)" % nested)
+        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` / `normalmap` have no gradient in hip_ad_rgb (a blend's `weight`, a mask's `opacity` and the colour slot 0 of the BSDFs nested in them do)" % nested)
     if not keys:
         return integrator.render(scene, sensor, seed, spp)
     params.update()

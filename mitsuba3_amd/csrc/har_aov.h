@@ -43,7 +43,7 @@ inline const char *aov_spec_lower(uint32_t n, const uint32_t *types, AovSpec &sp
  *  - `diffuse`: the reflectance texture at si.uv (diffuse.cpp:181); `plastic` / `roughplastic`: `diffuse_reflectance` (plastic.cpp:362, roughplastic.cpp:504);
  *    both are colour slot 0 of the record;
  *  - every other model: the base class, eval(BSDFContext(), si, wo = (0, 0, 1)) * pi (src/render/bsdf.cpp:38-43). */
-template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK / HAR_SCENE_ATTR bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
+template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK / HAR_SCENE_ATTR / HAR_SCENE_NORMALMAP bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
 HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = nullptr) {
     constexpr bool BLEND = (COMP & HAR_SCENE_BLEND) != 0u;
     BsdfSide side;
@@ -52,6 +52,11 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = 
         /* MaskBSDF::eval_diffuse_reflectance (mask.cpp:229-232): the nested BSDF's own answer -- through its `twosided`, if it has one (twosided.cpp:243-259) */
         const uint32_t nested = S.bsdfs[side.index].pad;
         if (!bsdf_side(S, nested, si.wi, side)) return Vec3(0.f);
+    }
+    if ((COMP & HAR_SCENE_NORMALMAP) != 0u && S.bsdfs[side.index].type == BSDF_NORMALMAP) {
+        /* NormalMap::eval_diffuse_reflectance (normalmap.cpp:250-253): the nested BSDF's answer for the UNPERTURBED si (the side an outer `twosided` mirrored) */
+        const uint32_t nested = S.bsdfs[side.index].pad;
+        if (!bsdf_side(S, nested, side.wi, side)) return Vec3(0.f);
     }
     const DBsdf &B = S.bsdfs[side.index];
     TexTaps taps;
@@ -78,6 +83,18 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = 
  * si.p comes from the triangle), `top_meshes` = number of top-level meshes of the scene.
  * shape_index (aov.cpp:288-297, the scalar branch): the 1-based position of the hit instance -- or, without one, of the hit shape -- in the
  * scene's shape list, which here is { top-level meshes, instances }; 0 on a miss. */
+/* BSDF::sh_frame(si).n (aov.cpp:245-256) of a hit in a scene with a `normalmap` record: frame().second.n = si.to_world(frame.n) (normalmap.cpp:224-248), the flip
+ * decided by the camera ray's wi.  Every other record returns si.sh_frame (bsdf.h:602-604) -- and so does a `twosided` OVER a normalmap, which does not forward
+ * sh_frame() to its nested BSDF (twosided.cpp has no override) */
+HAR_HD Vec3 aov_sh_normal_nmap(const DScene &S, const SurfInt &si) {
+    const DBsdf &B = S.bsdfs[S.meshes[si.mesh].bsdf];
+    if (B.type != BSDF_NORMALMAP || (B.flags & BF_TWOSIDED)) return si.sn;
+    TexTaps taps;
+    const BsdfInputs in = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps);
+    const NormalFrame F = normalmap_frame(B, in.slot0, si.wi);
+    return si.to_world(F.n);
+}
+
 template <uint32_t COMP = 0u>
 HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, Vec3 ray_d, const Hit &hit, bool active, float *out, size_t stride) {
     const bool valid = active && hit.t != HAR_INF;
@@ -87,6 +104,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
     Vec3 albedo(0.f);
     if (valid) {
         si = compute_si(S, ray_d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
+        if ((COMP & HAR_SCENE_NORMALMAP) != 0u) si_tangent_frame(S, si, ray_d, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
         if (need_partials) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
         if (need_albedo && (COMP & HAR_SCENE_ATTR) != 0u) {       /* scenes with a `mesh_attribute` texture: the albedo is looked up at the face and the barycentrics of si.p */
             AttrAddr addr; addr.face = 0u; addr.b1 = 0.f; addr.b2 = 0.f;
@@ -105,7 +123,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
                 case AOV_POSITION: v = si.p; break;
                 case AOV_UV: v.x = si.uv_x; v.y = si.uv_y; break;
                 case AOV_GEO_NORMAL: v = si.n; break;
-                case AOV_SH_NORMAL: v = si.sn; break;          /* BSDF::sh_frame(si) = si.sh_frame: no BSDF of this variant perturbs the frame */
+                case AOV_SH_NORMAL: v = (COMP & HAR_SCENE_NORMALMAP) != 0u ? aov_sh_normal_nmap(S, si) : si.sn; break;          /* BSDF::sh_frame(si): si.sh_frame unless a `normalmap` perturbs it */
                 case AOV_DP_DU: v = P.dp_du; break;
                 case AOV_DP_DV: v = P.dp_dv; break;
                 case AOV_PRIM_INDEX: v.x = (float) hit.prim; break;

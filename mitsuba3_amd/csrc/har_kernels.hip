@@ -21,6 +21,8 @@
  * All path logic is in har_path.h (shared with the host test harness); these
  * kernels only move data.  gfx950 only: 64-lane waves are assumed throughout.
  */
+#include <cstdio>
+#include <cstdlib>
 #include "har_kernels.h"
 #include "har_shape_grad.h"
 
@@ -1401,6 +1403,23 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                     blend_child_commit(S, grad_slots, grad_tex, on, on ? R.bl_rec[k] : 0u, R.uv_x, R.uv_y, g * dlr, (TYPES & HAR_SCENE_ATTR) != 0u ? &R.attr : nullptr);
                 }
             }
+            if ((TYPES & HAR_SCENE_NORMALMAP) != 0u) {
+                /* a normalmap vertex: the gradient with respect to the looked-up normal-map colour mixes the radiance channels (ShadeResult::nm_*):
+                 * g = sum_k dL_k ([visible] d Lr_dir,k / d c + L_k (d f_k / d c) / f_k), L already reduced by this vertex's Lr_dir; deposited in the record's own slot 0 --
+                 * its row for a constant `rgb`, the bitmap's taps otherwise (four times three for a bilinear map, one for a nearest one), pre-reduced within the wave where
+                 * lanes meet the same texel (blend_child_commit) */
+                const bool on = item_pred && R.nm_rec != 0xffffffffu;
+                Vec3 g(0.f);
+                if (on) {
+                    const float lk[3] = { Lr.x, Lr.y, Lr.z }, dk[3] = { dlr.x, dlr.y, dlr.z };
+                    for (int k = 0; k < 3; ++k) {
+                        Vec3 v = visible ? R.nm_dir[k] : Vec3(0.f);
+                        if (R.nm_ind) v = v + R.nm_rel[k] * lk[k];
+                        g = g + v * dk[k];
+                    }
+                }
+                blend_child_commit(S, grad_slots, grad_tex, on, on ? R.nm_rec : 0u, R.uv_x, R.uv_y, g);
+            }
             /* write-back: replay -> the survivor's slot of the next bounce (the primal pass's compaction, TapeArrays::next); otherwise the lane's result */
             if (in_range) {
                 if (tape_read) {
@@ -2284,6 +2303,43 @@ __global__ void k_api_bsdf_sample_mask(DScene S, uint32_t bsdf, BsdfCtx ctx, uin
     if (stype) stype[i] = b.type;
     if (scomp) scomp[i] = b.comp;
 }
+/* ... of a scene that holds a `normalmap` record: the two entries over the set that resolves such a record (and blend / mask records), and the surface interaction with
+ * the tangent frame of the shapes that pack one.  Kernels of their own again: the ones above keep their code and names */
+__global__ void k_api_bsdf_eval_pdf_nmap(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active, float *value, float *pdf) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    BsdfEval e; e.value = Vec3(0.f); e.pdf = 0.f;
+    if (!(active && !active[i])) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+    }
+    if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
+    if (pdf) pdf[i] = e.pdf;
+}
+__global__ void k_api_bsdf_sample_nmap(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const uint8_t *active,
+                                       float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
+    if (!(active && !active[i])) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+    }
+    wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
+    weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
+    if (eta) eta[i] = b.eta;
+    if (stype) stype[i] = b.type;
+    if (scomp) scomp[i] = b.comp;
+}
+__global__ void k_api_si_nmap(DScene S, uint32_t n, const float *o, const float *d, const float *t, const float *u, const float *v,
+                              const uint32_t *prim, const uint32_t *shape, const uint32_t *inst, uint32_t ray_flags, const uint8_t *active, float *out) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    (void) o;
+    si_rows_tangent(S, n, i, Vec3(d[i], d[n + i], d[2 * (size_t) n + i]), t[i], u[i], v[i], prim[i], shape[i], inst[i], ray_flags, !(active && !active[i]), out);
+}
 /* `path` in a scene with a mask record: the radiance of a camera sample that stayed invalid is dropped, dr::select(valid_ray, result, 0) (path.cpp:341-345) */
 __global__ void k_drop_invalid(uint32_t n, const float *valid, float4 *result) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2394,6 +2450,24 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_NORMALMAP) {
+        /* a scene with a `normalmap` record: the mask set (blend and mask records may sit on other meshes) plus the perturbed frame and the tangent frame of shapes that
+         * pack one.  Three shading kernels: forward, prb primal and the in-place adjoint commit of a cached / taped bounce, which deposits the normal map's and the
+         * nested colours' gradients (every backward pass of such a scene takes that route, as for a blend scene).  The item-writing adjoint (forward mode, vertex-position
+         * gradients) does not exist: run_chunk, the one caller, refuses those modes with an error before it launches anything (har_capi.hip) */
+        constexpr uint32_t T = HAR_SCENE_NORMALMAP_TYPES;
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PATH)
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags of a scene that also holds a mask record, or null (run_chunk) */, no_mq, 0u, tape);
+        else if (mode == MODE_PRB_PRIMAL)
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else {          /* no such kernel: run_chunk refuses these modes before any launch; a caller that does not must not get a bounce that shades nothing */
+            fprintf(stderr, "hip_ad_rgb: launch_shade: a scene with a `normalmap` record has no shading kernel for mode %d without the in-place commit\n", mode);
+            abort();
+        }
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_ATTR) {
         /* a scene with a `mesh_attribute` texture: the four flavours of a mask scene (below) in a set that also looks attributes up.  Every backward pass takes the in-place
          * commit (it has the hit at hand).  Two sets: scenes that also hold a blend / mask record run the mask set plus the lookup (HAR_SCENE_ATTR_TYPES); the others -- a
@@ -2628,6 +2702,7 @@ void launch_api_ray_test(hipStream_t s, const DScene &S, uint32_t n, const float
 }
 void launch_api_si(hipStream_t s, const DScene &S, uint32_t n, const float *o, const float *d, const float *t, const float *u, const float *v,
                    const uint32_t *prim, const uint32_t *shape, const uint32_t *inst, uint32_t ray_flags, const uint8_t *active, float *out) {
+    if (S.bsdf_types & HAR_SCENE_NORMALMAP) { hipLaunchKernelGGL(k_api_si_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, n, o, d, t, u, v, prim, shape, inst, ray_flags, active, out); return; }
     hipLaunchKernelGGL(k_api_si, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, n, o, d, t, u, v, prim, shape, inst, ray_flags, active, out);
 }
 void launch_api_sampler_seed(hipStream_t s, uint32_t seed, uint32_t lane_offset, uint32_t n, uint64_t *state, uint64_t *inc) {
@@ -2657,13 +2732,15 @@ void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const u
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {
-    if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else hipLaunchKernelGGL(k_api_bsdf_eval_pdf<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
 }
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
-    if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_sample_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_sample_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_sample_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else hipLaunchKernelGGL(k_api_bsdf_sample<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
 }

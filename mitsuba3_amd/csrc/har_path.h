@@ -12,6 +12,7 @@
  */
 #pragma once
 #include "har_scene.h"
+#include "har_normalmap_grad.h"
 
 namespace har {
 
@@ -90,6 +91,13 @@ struct ShadeResult {
     /* ... kernels of scenes with a `mesh_attribute` texture (HAR_SCENE_ATTR), MODE_PRB_ADJOINT: where the vertex looks attributes up (face, barycentrics of si.p) -- what
      * uv_x / uv_y are for a bitmap; the in-place commit deposits through it */
     AttrAddr attr;
+    /* ... kernels of scenes with a `normalmap` record (HAR_SCENE_NORMALMAP), MODE_PRB_ADJOINT: the gradient of a normalmap vertex with respect to the looked-up normal-map
+     * colour c.  It is not a per-channel scale, so it does not fit the (record, direct, relative) triple: nm_dir[k] = d (beta mis value_k em_weight_k) / d c and
+     * nm_rel[k] = (d value_k / d c) / value_k at the sampled direction, one vector over the three components of c per radiance channel k
+     * (normalmap_weighted_value_grad with A = the k-th unit weight); nm_rec = the normalmap record (0xffffffff: none), nm_ind: the second term exists.  The in-place commit
+     * of k_shade forms g = sum_k dL_k ([visible] nm_dir[k] + L_k nm_rel[k]) and scatters it through the record's taps.  The nested LEAF record's colour gradient rides in
+     * bl_*[0] as under a mask. */
+    uint32_t nm_rec; Vec3 nm_dir[3], nm_rel[3]; bool nm_ind;
 };
 #define HAR_EXTRA_GROUPS 5
 
@@ -154,6 +162,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT) { R.lt_hit_emitter = -1; R.lt_nee_emitter = -1; R.lt_hit_uv[0] = R.lt_hit_uv[1] = R.lt_nee_uv[0] = R.lt_nee_uv[1] = 0.f; }
     if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_BLEND) != 0u) { R.bl_rec[0] = R.bl_rec[1] = 0xffffffffu; R.bl_dir[0] = R.bl_dir[1] = R.bl_rel[0] = R.bl_rel[1] = Vec3(0.f); R.bl_ind = false; }
     if ((TYPES & HAR_SCENE_MASK) != 0u) R.non_null = false;
+    if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_NORMALMAP) != 0u) { R.nm_rec = 0xffffffffu; R.nm_ind = false; for (int k = 0; k < 3; ++k) { R.nm_dir[k] = Vec3(0.f); R.nm_rel[k] = Vec3(0.f); } }
     if (MODE == MODE_PRB_ADJOINT) { R.em_index = -1; R.nee_emitter = -1; R.em_unit = Vec3(0.f); R.contrib_unit = Vec3(0.f); R.nee_flags = 0u; R.cos_em = 0.f; R.nee_p = Vec3(0.f); R.nee_n = Vec3(0.f); R.nee_w = Vec3(0.f); }
     uint64_t rng = st.rng;
     const uint64_t inc = sampler_inc(P.seed, st.lane);
@@ -163,6 +172,8 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     /* with a hit record that carries the face index and the material word, nothing below waits for a load of the mesh record (only an emitter hit reads it) */
     SurfInt si = hx ? compute_si_record(S, st.d, hit.t, hit.u, hit.v, hx->gface, HAR_MATINFO_FLAGS(hx->matinfo), hit.shape, hit.inst)
                     : compute_si(S, st.d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
+    /* scenes with a `normalmap` record: a shape that packs a tangent builds its frame from it (si_tangent_frame; every other shape keeps coordinate_system) */
+    if ((TYPES & HAR_SCENE_NORMALMAP) != 0u) si_tangent_frame(S, si, st.d, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
     const bool valid = si.valid();
     /* scenes with a `mesh_attribute` texture: the face and the barycentrics of si.p (Mesh::barycentric_coordinates) for the lookups of this vertex; such a texture sits
      * on top-level meshes only, so an instanced hit never reads the address */
@@ -247,7 +258,9 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     const bool blend = (TYPES & HAR_SCENE_BLEND) != 0u && B.type == BSDF_BLEND;
     /* a mask record (kernels of mask scenes only): Smooth if its nested BSDF is (mask.cpp:113); `composite`: the vertex files gradients for nested records (bl_*) */
     const bool mask = (TYPES & HAR_SCENE_MASK) != 0u && B.type == BSDF_MASK;
-    const bool composite = blend || mask;
+    /* a normalmap record (kernels of normalmap scenes only): Smooth if its nested BSDF is (normalmap.cpp:117-122); it files the nested leaf's colour gradient as a mask does */
+    const bool nmap = (TYPES & HAR_SCENE_NORMALMAP) != 0u && B.type == BSDF_NORMALMAP;
+    const bool composite = blend || mask || nmap;
     const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR)
                                                : (composite ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
@@ -330,6 +343,16 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 R.contrib_unit = ((st.throughput * mis_em) * ev.value) * em_unit;
                 if ((TYPES & HAR_SCENE_BLEND) != 0u && composite)
                     for (int k = 0; k < 2; ++k) R.bl_dir[k] = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
+                if ((TYPES & HAR_SCENE_NORMALMAP) != 0u && nmap && side_ok) {          /* d Lr_dir / d c, channel by channel of the radiance */
+                    const Vec3 w = (st.throughput * mis_em) * em_weight;
+                    const Vec3 wo_f(wo_em.x, wo_em.y, wo_em.z * side.wo_sign);
+                    const float wk[3] = { w.x, w.y, w.z };
+                    for (int k = 0; k < 3; ++k) {
+                        float dc[3];
+                        normalmap_weighted_value_grad(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dc);
+                        R.nm_dir[k] = Vec3(dc[0], dc[1], dc[2]);
+                    }
+                }
                 if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
                     BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok, wo_em, x);
                     const Vec3 w = (st.throughput * mis_em) * em_weight;
@@ -424,6 +447,10 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
         R.item = R.item_ray || R.ind_active || (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE && R.x_ind);   /* otherwise the vertex has a zero gradient */
         if ((TYPES & HAR_SCENE_BLEND) != 0u && composite) {
             R.bl_rec[0] = (uint32_t) B.table; R.bl_rec[1] = B.pad;
+            if (nmap) {          /* one nested record: the leaf that serves the PERTURBED wi' of a nested `twosided` */
+                const NormalFrame NF = normalmap_frame(B, bin.slot0, side.wi);
+                BsdfSide ns; R.bl_rec[0] = (side_ok && bsdf_side(S, B.pad, NF.to_local(side.wi), ns)) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
+            }
             if (mask) {          /* one nested record: the leaf that serves this side of a nested `twosided` (none where a two-BSDF pair is zero, wi.z == 0) */
                 BsdfSide ns; R.bl_rec[0] = bsdf_side(S, B.pad, si.wi, ns) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
             }
@@ -432,6 +459,20 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 R.bl_ind = R.bl_ind || (alive && (R.bl_rel[k].x != 0.f || R.bl_rel[k].y != 0.f || R.bl_rel[k].z != 0.f));
             }
             R.item = R.item || R.bl_ind;
+        }
+        if ((TYPES & HAR_SCENE_NORMALMAP) != 0u && nmap && side_ok) {
+            /* Lr_ind = L * relative_grad(bsdf.eval(si, wo)) with respect to c: (d value_k / d c) / value_k per radiance channel k */
+            R.nm_rec = side.index;
+            const float vk[3] = { e2.value.x, e2.value.y, e2.value.z };
+            const Vec3 wo_f(wo.x, wo.y, wo.z * side.wo_sign);
+            for (int k = 0; k < 3; ++k) {
+                if (!alive || vk[k] == 0.f) continue;
+                float dc[3];
+                normalmap_weighted_value_grad(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f), dc);
+                R.nm_rel[k] = Vec3(dc[0] / vk[k], dc[1] / vk[k], dc[2] / vk[k]);
+                R.nm_ind = R.nm_ind || dc[0] != 0.f || dc[1] != 0.f || dc[2] != 0.f;
+            }
+            R.item = R.item || R.nm_ind;
         }
     }
 }

@@ -8,6 +8,7 @@
  * Scenes with a `mask` record (HAR_SCENE_MASK) are planned the same way, with their own widest set.  In `path` the validity of a camera sample is decided along the
  * path there (a null lobe does not make it valid, path.cpp:307-308): ChunkPlan::valid_shade -- the per-lane flags start at 0 and the shading kernel stores 1 from the vertex
  * at which a non-null lobe was sampled, instead of k_alpha_flags; run_chunk then clears the radiance of the lanes that stayed invalid (path.cpp:341-345).
+ * Scenes with a `normalmap` record (HAR_SCENE_NORMALMAP) take the same route with a set of their own (forward, prb primal and the in-place adjoint commit).
  */
 #pragma once
 #include "../../include/hip_ad_rgb.h"
@@ -110,7 +111,7 @@ inline ChunkPlan plan_chunk(const Switches &W, const Settings &I, const SceneFac
      * shading launch rebuilds the state instead of reading it (k_raygen<.., LITE>, k_shade<.., FIRST>; ShadeParams::sensor).  Plain forward renders and the recording pass of prb, of one pass, whose
      * bounce-0 wavefront nobody else reads (no alpha / validity flags, no material queues, no tape); the passes of a multi-pass forward render resume their samplers from the pass state in both kernels.  HAR_FIRST_VERTEX=0 switches it off (A/B) */
     P.first_regen = W.first_vertex && ((mode == MODE_PATH && J.cache_mode == CACHE_NONE) || (mode == MODE_PRB_PRIMAL && rec_w && J.adjoint_image && !J.forward_mode && !J.pass_rng)) && !J.rays && !J.valid_lane && !(I.alpha_film && J.alpha_lane) && !I.batch.n && J.projection != 2u /* thin lens: k_raygen_lens stores the full state, as k_raygen_batch does */ &&
-                    !P.mq_on && !(F.bsdf_types & HAR_SCENE_WIDEST) /* scenes with a `blendbsdf` / `mask` record or a `mesh_attribute` texture run one widest shading kernel per flavour (launch_shade): no FIRST instantiation */;
+                    !P.mq_on && !(F.bsdf_types & HAR_SCENE_WIDE_ROUTE) /* scenes with a `blendbsdf` / `mask` / `normalmap` record or a `mesh_attribute` texture run one widest shading kernel per flavour (launch_shade): no FIRST instantiation */;
     P.fwd = mode == MODE_PRB_ADJOINT && J.forward_mode;
     P.shade_flags = ((mode != MODE_PATH && I.grad_emitters) ? HAR_SHADE_EMITTER_GRADS : 0u)      /* (the primal pass of a backward step too: it traces the shadow rays of samples that only carry a radiance gradient, shade_lane) */ | (I.hide_emitters ? HAR_SHADE_HIDE_EMITTERS : 0u) |
                     (P.fwd ? HAR_SHADE_FORWARD_MODE : 0u) | ((mode == MODE_PRB_ADJOINT && I.grad_bsdf_params && !P.fwd) ? HAR_SHADE_EXTRA_GRADS : 0u) |
@@ -127,7 +128,7 @@ inline ChunkPlan plan_chunk(const Switches &W, const Settings &I, const SceneFac
     P.inline_commit = W.adjoint_inline && mode == MODE_PRB_ADJOINT && !P.shape && !J.forward_mode;      /* forward mode commits in the resolve kernels (own instantiation) */
     /* per-material shading queues: scenes with more than one BSDF model, `path` and the primal pass of `prb` (the adjoint kernels keep the generic code:
      * their in-place commit is bound by memory traffic, not by the model code).  HAR_MATERIAL_QUEUES=0: the generic kernel with its block-local sort (A/B) */
-    P.use_mq = P.mq_on && mode != MODE_PRB_ADJOINT && J.cache_mode != RECORD_WRITE && __builtin_popcount(F.mat_classes) >= 2 && !(F.bsdf_types & (HAR_SCENE_ENVMAP | HAR_SCENE_WIDEST));
+    P.use_mq = P.mq_on && mode != MODE_PRB_ADJOINT && J.cache_mode != RECORD_WRITE && __builtin_popcount(F.mat_classes) >= 2 && !(F.bsdf_types & (HAR_SCENE_ENVMAP | HAR_SCENE_WIDE_ROUTE));
     P.overlap = mode != MODE_PRB_ADJOINT && !J.rays && overlap_applies(W, F, I.hide_emitters, J.n);
     /* LATE OVERLAP (jobs too large for the full overlap above): from bounce `late_from` on, bounce b's shadow rays run on the second stream NEXT TO bounce b + 1's
      * closest-hit rays, and bounce b + 1's shading waits for them -- so both kernels keep writing the one `result` array (no second item set, no result2, no final add:

@@ -17,6 +17,7 @@
 #include "har_cpu.h"
 #include "har_path.h"
 #include "har_aov.h"
+#include "har_normalmap_grad.h"
 #include "har_scene_host.h"
 
 #include <algorithm>
@@ -63,7 +64,7 @@ struct BoundScene {
         S.n_emitters = (uint32_t) hs.emitters.size(); S.n_meshes = (uint32_t) hs.meshes.size();
         S.n_bsdfs = (uint32_t) hs.bsdfs.size(); S.n_insts = (uint32_t) hs.insts.size(); S.n_textures = (uint32_t) hs.textures.size();
         S.env_emitter = hs.env_emitter;
-        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
         for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) S.bsdf_types |= HAR_SCENE_ATTR;
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
         hs.bind_tables(S, hs.emitter_distr.data());
@@ -118,6 +119,7 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
         if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
+        else if (S.bsdf_types & HAR_SCENE_NORMALMAP) shade_lane<MODE_PATH, HAR_SCENE_NORMALMAP_TYPES>(S, P, st, hit, R);      /* ... with a `normalmap` record the perturbed and the tangent frames */
         else shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
         /* path.cpp:307-308; in a scene with a `mask` record the vertex decides (a null lobe does not make the sample valid: ShadeResult::non_null, which also follows the
          * scalar branch's early exit, :227-231, where HAR_SHADE_SCALAR_DRAWS is set) */
@@ -294,12 +296,70 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
             Hit hit; hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
             if (act) { ScalarStack stack; accel_trace<false>(S.accel, O, D, maxt[i], hit, stack, status); }
             if (S.bsdf_types & HAR_SCENE_ATTR) aov_lane<HAR_SCENE_WIDEST>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            else if (S.bsdf_types & HAR_SCENE_NORMALMAP) aov_lane<HAR_SCENE_RECORD_BITS>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
             else aov_lane<HAR_SCENE_COMPOSITE>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
         }
         if (status) return har_set_error("har_aov_sample_host: traversal stack overflow");
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_aov_sample_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_aov_sample_host: ") + ex.what()); }
+}
+
+/* PreliminaryIntersection::compute_surface_interaction on the host for n given hits (t, prim_uv, prim, shape, inst as Scene::ray_intersect_preliminary returns them;
+ * d = the ray directions, 3 x n): the 33 rows of har_compute_surface_interaction, by the function its kernel runs in a scene with a `normalmap` record (si_rows_tangent:
+ * compute_si + the tangent frame of the shapes that pack one; for every other shape that IS compute_si).  The twin of that entry: the frames without a GPU. */
+extern "C" int har_surface_interaction_host(const HarSceneDesc *desc, uint32_t n, const float *d, const float *t, const float *u, const float *v, const uint32_t *prim,
+                                            const uint32_t *shape, const uint32_t *inst, uint32_t ray_flags, const uint8_t *active, float *out) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        if (ray_flags & ~(uint32_t) RAY_KNOWN_FLAGS) return har_set_error("unknown RayFlags bits");
+        if (n == 0) return 0;
+        if (!d || !t || !u || !v || !prim || !shape || !inst || !out) return har_set_error("null input / output arrays");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            const bool act = !(active && !active[i]);
+            if (act && t[i] != HAR_INF) {
+                if (shape[i] >= S.n_meshes || prim[i] >= S.meshes[shape[i]].face_count || (inst[i] != 0xffffffffu && inst[i] >= S.n_insts)) return har_set_error("har_surface_interaction_host: hit record out of bounds");
+            }
+            si_rows_tangent(S, n, i, Vec3(d[i], d[n + i], d[2 * (size_t) n + i]), t[i], u[i], v[i], prim[i], shape[i], inst[i], ray_flags, act, out);
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_surface_interaction_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_surface_interaction_host: ") + ex.what()); }
+}
+
+/* d F / d c of a `normalmap` record on the host (normalmap_weighted_value_grad, har_normalmap_grad.h): n tuples (wi 3 x n, uv 2 x n, wo 3 x n, A 3 x n) on record
+ * `bsdf` -- a normalmap record, possibly under an outer one-BSDF `twosided` --, c = the record's colour looked up at uv.  value (n, may be NULL) = F = sum_k A_k value_k,
+ * grad (3 x n) = the three partials with respect to the looked-up colour.  Default context. */
+extern "C" int har_normalmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo, const float *A,
+                                       float *value, float *grad) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.hs.bsdfs[bsdf].type != BSDF_NORMALMAP) return har_set_error("har_normalmap_grad_host: not a normalmap record");
+        if (n == 0) return 0;
+        if (!wi || !uv || !wo || !A || !grad) return har_set_error("null input / output arrays");
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            const size_t i1 = n + (size_t) i, i2 = 2 * (size_t) n + i;
+            float dc[3] = { 0.f, 0.f, 0.f }, f = 0.f;
+            BsdfSide side;
+            if (bsdf_side(S, bsdf, Vec3(wi[i], wi[i1], wi[i2]), side)) {
+                TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[i1], taps);
+                f = normalmap_weighted_value_grad(S, S.bsdfs[side.index], in.slot0, side.wi, Vec3(wo[i], wo[i1], wo[i2] * side.wo_sign), uv[i], uv[i1], Vec3(A[i], A[i1], A[i2]), dc);
+            }
+            if (value) value[i] = f;
+            grad[i] = dc[0]; grad[i1] = dc[1]; grad[i2] = dc[2];
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_normalmap_grad_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_normalmap_grad_host: ") + ex.what()); }
 }
 
 /* The lookup of a `mesh_attribute` record and its transpose on the host, by the functions the kernels run (attr_addr, attr_taps, attr_fetch, tap_weights): n hits on the
@@ -356,7 +416,7 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_COMPOSITE, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             if (value) { value[i] = ev.value.x; value[n + i] = ev.value.y; value[2 * (size_t) n + i] = ev.value.z; }
             if (pdf) pdf[i] = ev.pdf;
@@ -383,7 +443,7 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_COMPOSITE, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
             weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;

@@ -286,6 +286,54 @@ HAR_HD void compute_si_partials(const DScene &S, float bu, float bv, uint32_t pr
     }
 }
 
+/* The shading frame of a shape that packs a tangent for a BSDFFlags::NormalMapped material (kernels of scenes with a `normalmap` record only).  The reference packs
+ * per-vertex tangents (mesh.cpp:612-623, 2417-2429); here only shapes whose tangent IS the direction of the face's dp_du carry MESH_TANGENT_FRAME -- a rectangle, whose four
+ * vertices share normalize(to_world * (1, 0, 0)) (rectangle.cpp:131-153) -- and every other mesh with normals and texcoords under a normalmap is refused at load.
+ * finalize_surface_interaction (interaction.h:570-598): s = fnmadd(n, dot(n, s), s), normalised (coordinate_system(n) -- what compute_si left -- when it vanishes),
+ * t = cross(n, s), negated where frame_flipped: the shape's bit (MESH_FRAME_FLIPPED: a mirroring to_world, flip_normals included, mesh.cpp:1160-1215) xor a mirroring
+ * instance transform (instance.cpp:218-222).  Leaves every other mesh's interaction as it is. */
+enum { MESH_TANGENT_FRAME = 4u, MESH_FRAME_FLIPPED = 8u };
+HAR_HD void si_tangent_frame(const DScene &S, SurfInt &si, Vec3 ray_d, float bu, float bv, uint32_t prim, uint32_t shape, uint32_t inst) {
+    if (si.t == HAR_INF) return;
+    const uint32_t mf = S.meshes[shape].flags;
+    if (!(mf & MESH_TANGENT_FRAME)) return;
+    SurfPartials P; compute_si_partials(S, bu, bv, prim, shape, inst, false, P);
+    bool flipped = (mf & MESH_FRAME_FLIPPED) != 0u;
+    if (inst != 0xffffffffu) {
+        const DInst &I = S.insts[inst];
+        const Vec3 c0 = xf_vector(I.to_world, Vec3(1.f, 0.f, 0.f)), c1 = xf_vector(I.to_world, Vec3(0.f, 1.f, 0.f)), c2 = xf_vector(I.to_world, Vec3(0.f, 0.f, 1.f));
+        if (dot3(c0, cross3(c1, c2)) < 0.f) flipped = !flipped;
+    }
+    const Vec3 s0 = normalize3(P.dp_du);
+    const Vec3 s = fma3(si.sn, -dot3(si.sn, s0), s0);
+    const float sqr_norm = dot3(s, s);
+    if (sqr_norm > 0.f) { si.ss = s * rsqrt_(sqr_norm); si.st = cross3(si.sn, si.ss); }
+    if (flipped) si.st = -si.st;
+    si.wi = si.to_local(-ray_d);
+}
+
+/* One lane of the array-valued PreliminaryIntersection::compute_surface_interaction in a scene with a `normalmap` record (k_api_si_nmap and its host twin,
+ * har_surface_interaction_host): the 33 rows of k_api_si (har_kernels.hip) with the tangent frame above in sh_frame.s / .t and wi */
+HAR_HD void si_rows_tangent(const DScene &S, uint32_t n, uint32_t i, Vec3 D, float t, float u, float v, uint32_t prim, uint32_t shape, uint32_t inst, uint32_t ray_flags, bool active, float *out) {
+    const bool shading = (ray_flags & RAY_SHADING) != 0u, valid = active && t != HAR_INF;
+    Vec3 vs[6] = { Vec3(0.f), Vec3(0.f), Vec3(0.f), Vec3(0.f), Vec3(0.f), Vec3(0.f) };
+    float uvx = 0.f, uvy = 0.f;
+    SurfPartials P; P.dp_du = Vec3(0.f); P.dp_dv = Vec3(0.f); P.dn_du = Vec3(0.f); P.dn_dv = Vec3(0.f);
+    if (valid) {
+        SurfInt si = compute_si(S, D, t, u, v, prim, shape, inst);
+        vs[0] = si.p; vs[1] = si.n;
+        if (shading) {
+            si_tangent_frame(S, si, D, u, v, prim, shape, inst);
+            vs[2] = si.sn; vs[3] = si.ss; vs[4] = si.st; vs[5] = si.wi; uvx = si.uv_x; uvy = si.uv_y;
+            compute_si_partials(S, u, v, prim, shape, inst, (ray_flags & RAY_NORMAL_PARTIALS) != 0u, P);
+        }
+    } else if (shading) { coordinate_system(Vec3(0.f), vs[3], vs[4]); vs[5] = -D; }
+    for (int k = 0; k < 6; ++k) { out[(3 * k) * (size_t) n + i] = vs[k].x; out[(3 * k + 1) * (size_t) n + i] = vs[k].y; out[(3 * k + 2) * (size_t) n + i] = vs[k].z; }
+    out[18 * (size_t) n + i] = uvx; out[19 * (size_t) n + i] = uvy; out[20 * (size_t) n + i] = valid ? t : HAR_INF;
+    const Vec3 ps[4] = { P.dp_du, P.dp_dv, P.dn_du, P.dn_dv };
+    for (int k = 0; k < 4; ++k) { out[(21 + 3 * k) * (size_t) n + i] = ps[k].x; out[(22 + 3 * k) * (size_t) n + i] = ps[k].y; out[(23 + 3 * k) * (size_t) n + i] = ps[k].z; }
+}
+
 /* Interaction::offset_p / spawn_ray / spawn_ray_to (interaction.h:161-191) */
 HAR_HD Vec3 offset_p(const SurfInt &si, Vec3 d) {
     float mag = (1.f + hmax3(abs3(si.p))) * HAR_RAY_EPS;
@@ -584,6 +632,73 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
     bs.wo = Vec3(-wi.x, -wi.y, -wi.z); bs.pdf = 1.f - o; bs.weight = Vec3(1.f); bs.eta = 1.f; bs.delta = true; bs.type = LOBE_NULL; bs.comp = null_index;
 }
 
+/* ---- NormalMap (src/bsdfs/normalmap.cpp), record type 8: slot 0 is the normal-map colour (Texture::eval_3: a constant rgb or a three-channel bitmap), DBsdf::pad names
+ * the nested record -- a leaf model that may carry the twosided flag: bsdf_side is applied to it with the PERTURBED wi', as twosided.cpp sees perturbed_si.  Only the kernels
+ * of scenes that hold such a record carry this code (TYPES & HAR_SCENE_NORMALMAP).  Components and flags are the nested BSDF's (:117-122): the context passes through.
+ * frame() (:224-244), in the reference's order of operations: n = fmadd(c, 2, -1); with flip_invalid_normals n <- (-n.x, -n.y, n.z) where cos_theta(wi) * dot(wi, n) <= 0;
+ * n = normalize(n); s = normalize(fnmadd(n, n.x, (1, 0, 0))); t = cross(n, s) -- the frame relative to si.sh_frame, which is all eval / pdf / sample read. */
+struct NormalFrame {
+    Vec3 s, t, n;
+    HAR_HD Vec3 to_local(Vec3 v) const { return Vec3(dot3(v, s), dot3(v, t), dot3(v, n)); }       /* frame.h:34 */
+    HAR_HD Vec3 to_world(Vec3 v) const { return fma3(n, v.z, fma3(t, v.y, s * v.x)); }             /* frame.h:39 */
+};
+HAR_HD NormalFrame normalmap_frame(const DBsdf &B, Vec3 c, Vec3 wi) {
+    Vec3 n(fma_(c.x, 2.f, -1.f), fma_(c.y, 2.f, -1.f), fma_(c.z, 2.f, -1.f));
+    if ((B.flags & BF_NM_FLIP) && wi.z * dot3(wi, n) <= 0.f) n = Vec3(-n.x, -n.y, n.z);
+    NormalFrame F;
+    F.n = normalize3(n);
+    F.s = normalize3(Vec3(fnma_(F.n.x, F.n.x, 1.f), fnma_(F.n.y, F.n.x, 0.f), fnma_(F.n.z, F.n.x, 0.f)));
+    F.t = cross3(F.n, F.s);
+    return F;
+}
+/* Frame::tan_theta_2 (frame.h:80-83) and eval_shadow_terminator (normalmap_helpers.h:20-25) */
+HAR_HD float frame_tan_theta_2(Vec3 v) { return fmaxf(fnma_(v.z, v.z, 1.f), 0.f) / sqr_(v.z); }
+HAR_HD float normalmap_shadow_terminator(Vec3 perturbed_n, Vec3 wo) {
+    const float alpha2 = fminf(0.125f * frame_tan_theta_2(perturbed_n), 1.f);
+    return 2.f / (1.f + sqrtf(1.f + alpha2 * frame_tan_theta_2(wo)));
+}
+/* eval / pdf / eval_pdf (:163-219): the nested BSDF at wi' = frame.to_local(wi), wo' = frame.to_local(wo); zero unless cos_theta(wo) * cos_theta(wo') > 0; the value -- not
+ * the pdf -- times the shadow terminator of (frame.n, wo).  d_slot0 stays zero (the record's slot 0 is the normal map: its derivative is not a per-channel scale; it
+ * comes from normalmap_weighted_value_grad, har_normalmap_grad.h); cg->d[0] = d value / d (slot 0 of the nested LEAF). */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void normalmap_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_RECORD_BITS;
+    e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f);
+    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
+    const Vec3 pwi = F.to_local(wi), pwo = F.to_local(wo);
+    if (!(wo.z * pwo.z > 0.f)) return;
+    BsdfSide ns;
+    if (!bsdf_side(S, B.pad, pwi, ns)) return;
+    const DBsdf &N = S.bsdfs[ns.index];
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    BsdfEval ne; bsdf_eval_pdf_one<LEAF, CTX>(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), ne, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
+    const float shadow = (B.flags & BF_NM_SHADOW) ? normalmap_shadow_terminator(F.n, wo) : 1.f;
+    e.value = (B.flags & BF_NM_SHADOW) ? ne.value * shadow : ne.value;
+    e.pdf = ne.pdf;
+    if (cg) cg->d[0] = ne.d_slot0 * shadow;          /* d value / d (slot 0 of the nested LEAF): the leaf receives shadow * d_slot0(nested at wi', wo') */
+}
+/* sample (:134-160): the nested sample at wi'; nothing when its weight is zero; wo = frame.to_world(wo') -- back in the UNPERTURBED frame --, pdf and weight zero unless
+ * cos_theta(wo') * cos_theta(wo) > 0 (wo, eta, sampled_type and sampled_component stay what the nested BSDF returned), the weight times the shadow terminator */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void normalmap_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+    constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_RECORD_BITS;
+    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
+    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
+    const Vec3 pwi = F.to_local(wi);
+    BsdfSide ns;
+    if (!bsdf_side(S, B.pad, pwi, ns)) return;
+    const DBsdf &N = S.bsdfs[ns.index];
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    bsdf_sample_one<LEAF, CTX>(N, nin, ns.wi, s1, s2x, s2y, bs, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
+    bs.wo.z *= ns.wo_sign;
+    const bool nonzero = bs.weight.x != 0.f || bs.weight.y != 0.f || bs.weight.z != 0.f;                             /* :146 (a lane of a wavefront: the rest still runs, masked) */
+    const Vec3 pwo = bs.wo, wo = F.to_world(pwo);
+    const bool active = nonzero && pwo.z * wo.z > 0.f;
+    bs.wo = wo;
+    if (!active) { bs.pdf = 0.f; bs.weight = Vec3(0.f); return; }
+    if (B.flags & BF_NM_SHADOW) bs.weight = bs.weight * normalmap_shadow_terminator(F.n, wo);
+}
+
 /* (u, v): the vertex's texture coordinates -- read only by the kernels of blend / mask scenes, whose nested records look up their own colour inputs there */
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx(), float u = 0.f, float v = 0.f,
@@ -598,7 +713,11 @@ HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInput
         return;
     }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
-    bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_COMPOSITE), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
+    if ((TYPES & HAR_SCENE_NORMALMAP) != 0u && S.bsdfs[side.index].type == BSDF_NORMALMAP) {
+        normalmap_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        return;
+    }
+    bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_RECORD_BITS), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
 }
 /* d value / d {alpha, eta, k} of the record serving this side (see bsdf_eval_extra_one) */
 HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEvalExtra &x) {
@@ -611,7 +730,8 @@ HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs 
     if (!side_ok) { bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u; return; }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
     else if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) mask_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
-    else bsdf_sample_one<(TYPES & ~HAR_SCENE_COMPOSITE), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
+    else if ((TYPES & HAR_SCENE_NORMALMAP) != 0u && S.bsdfs[side.index].type == BSDF_NORMALMAP) normalmap_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
+    else bsdf_sample_one<(TYPES & ~HAR_SCENE_RECORD_BITS), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
     bs.wo.z *= side.wo_sign;
 }
 

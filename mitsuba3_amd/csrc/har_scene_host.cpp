@@ -206,6 +206,7 @@ bool scene_set_bsdf_params_host(HostScene &hs, uint32_t index, const HarBSDF &in
     DBsdf &b = hs.bsdfs[index];
     if (b.type == BSDF_BLEND) { err = "blendbsdf: the record has no parameter besides its weight (slot 0)"; return false; }
     if (b.type == BSDF_MASK) { err = "mask: the record has no parameter besides its opacity (slot 0)"; return false; }
+    if (b.type == BSDF_NORMALMAP) { err = "normalmap: the record has no parameter besides its normal map (slot 0)"; return false; }
     for (float v : { in.alpha_u, in.alpha_v, in.eta, in.eta_c[0], in.eta_c[1], in.eta_c[2], in.k_c[0], in.k_c[1], in.k_c[2], in.reflectance2[0], in.reflectance2[1], in.reflectance2[2] })
         if (!std::isfinite(v)) { err = "BSDF parameter is not finite"; return false; }
     const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
@@ -302,6 +303,10 @@ static bool build_envmap(HostScene &hs, const HarTexture &img, const HarEmitter 
     return true;
 }
 
+/* the two mesh bits of the public header are the ones the kernels test (har_scene.h) */
+static_assert((uint32_t) MESH_TANGENT_FRAME == HAR_MESH_TANGENT_FRAME && (uint32_t) MESH_FRAME_FLIPPED == HAR_MESH_FRAME_FLIPPED, "HarMesh::flags and DMesh::flags disagree");
+static_assert((uint32_t) BF_NM_FLIP == HAR_BSDF_NM_FLIP && (uint32_t) BF_NM_SHADOW == HAR_BSDF_NM_SHADOW && (uint32_t) BSDF_NORMALMAP == HAR_BSDF_NORMALMAP, "HarBSDF and DBsdf disagree");
+
 bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     if (d.top_mesh_count > d.mesh_count) { err = "top_mesh_count exceeds mesh_count"; return false; }
     for (uint32_t i = 0; i < d.mesh_count; ++i) {
@@ -355,11 +360,13 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.bsdf_count; ++i) {
         const HarBSDF &b = d.bsdfs[i];
-        if (b.type > BSDF_MASK) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask and twosided are implemented in hip_ad_rgb)"; return false; }
+        if (b.type > BSDF_NORMALMAP) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask, normalmap and twosided are implemented in hip_ad_rgb)"; return false; }
         if (b.texture >= (int32_t) d.texture_count) { err = "BSDF references a texture that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
         /* ... and BSDFFlags::Null is part of BSDFFlags::Transmission: `twosided` over a `mask`, on either side */
         if ((b.flags & BF_TWOSIDED) && (b.type == BSDF_MASK || (b.back >= 0 && d.bsdfs[b.back].type == BSDF_MASK))) { err = "twosided over `mask`: Only materials without a transmission component can be nested!"; return false; }
+        /* `twosided` over a `normalmap`: the one-BSDF form, twosided(normalmap(X)); a pair with a normalmap on either side is not supported */
+        if ((b.flags & BF_TWOSIDED) && b.back >= 0 && (b.type == BSDF_NORMALMAP || d.bsdfs[b.back].type == BSDF_NORMALMAP)) { err = "twosided over `normalmap`: the two-BSDF form is not supported (nest ONE normalmap: twosided(normalmap(X)))"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
         if ((b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC) && !(b.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
         if (b.type == BSDF_ROUGHPLASTIC && b.eta == 1.f) { err = "The interior and exterior indices of refraction must be positive and differ!"; return false; }
@@ -376,6 +383,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             for (int k = 0; k < 2; ++k) {
                 const HarBSDF &c = d.bsdfs[b.nested[k]];
                 if (c.type == BSDF_MASK) { err = "blendbsdf: a nested `mask` BSDF is not supported (put the `mask` outside, over plain BSDF models)"; return false; }
+                if (c.type == BSDF_NORMALMAP) { err = "blendbsdf: a nested `normalmap` BSDF is not supported (nested BSDFs are plain BSDF models)"; return false; }
                 if (c.type >= BSDF_TYPE_COUNT || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
                 if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
                 if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_BLEND_SMOOTH;
@@ -387,6 +395,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             const HarBSDF &c = d.bsdfs[b.nested[0]];
             if (c.type == BSDF_BLEND) { err = "mask: unsupported BSDF type of the nested record: a nested `blendbsdf` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type == BSDF_MASK) { err = "mask: unsupported BSDF type of the nested record: a nested `mask` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
+            if (c.type == BSDF_NORMALMAP) { err = "mask: unsupported BSDF type of the nested record: a nested `normalmap` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type >= BSDF_TYPE_COUNT) { err = "mask: unsupported BSDF type of the nested record"; return false; }
             if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
             if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
@@ -396,7 +405,27 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
             }
             db.pad = (uint32_t) b.nested[0];
-        } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH);
+        } else if (b.type == BSDF_NORMALMAP) {              /* NormalMap (normalmap.cpp:100-127): one nested record, named by index; it may be a `twosided` (one BSDF or a pair) */
+            if (b.flags & BF_MONO) { err = "normalmap: the `normalmap` texture must have three channels (a one-channel bitmap is not a normal map)"; return false; }
+            if (b.texture >= 0 && (d.textures[b.texture].mode & HAR_TEX_MESH_ATTRIBUTE)) { err = "normalmap: a `mesh_attribute` texture as the normal map is not supported"; return false; }
+            db.flags &= BF_TWOSIDED | BF_NM_FLIP | BF_NM_SHADOW;
+            if (b.nested[0] < 0 || b.nested[0] >= (int32_t) d.bsdf_count) { err = "normalmap: the nested BSDF index is out of range"; return false; }
+            const HarBSDF &c = d.bsdfs[b.nested[0]];
+            if (c.type == BSDF_BLEND || c.type == BSDF_MASK || c.type == BSDF_NORMALMAP) {
+                err = std::string("normalmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
+                return false;
+            }
+            if (c.type >= BSDF_TYPE_COUNT) { err = "normalmap: unsupported BSDF type of the nested record"; return false; }
+            if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
+            if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
+            if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
+                if (c.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
+                const HarBSDF &k = d.bsdfs[c.back];
+                if (k.type >= BSDF_TYPE_COUNT) { err = "normalmap: the back side of a nested `twosided` must be a plain BSDF model (a `blendbsdf`, `mask` or `normalmap` there is not supported)"; return false; }
+                if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
+            }
+            db.pad = (uint32_t) b.nested[0];
+        } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH | BF_NM_FLIP | BF_NM_SHADOW);
         hs.bsdfs.push_back(db);
         if (b.type == BSDF_ROUGHPLASTIC) { build_roughplastic_tables(hs, i); update_roughplastic_sampling_weight(hs, i); }
         if (b.type == BSDF_PLASTIC) {                       /* SmoothPlastic::parameters_changed (plastic.cpp:188-205) */
@@ -404,6 +433,24 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             p.inv_eta_2 = 1.f / (p.eta * p.eta);
             p.internal_reflectance = fresnel_diffuse_reflectance(1.f / p.eta);
             update_roughplastic_sampling_weight(hs, i);
+        }
+    }
+    /* a `normalmap` record perturbs the shading frame, so the frame's tangent matters (BSDFFlags::NormalMapped, normalmap.cpp:124-126).  A mesh under such a record keeps
+     * coordinate_system(n) where the reference packs no tangent (no vertex normals, or no texcoords); with both it must carry HAR_MESH_TANGENT_FRAME -- set by the caller
+     * for a shape whose per-vertex tangent is the direction of dp_du (a rectangle) -- and is refused otherwise: per-vertex tangents (Mesh::compute_tangents) are not
+     * implemented.  Every other mesh loses the two bits: its interaction stays what it was */
+    {
+        bool any = false; for (const DBsdf &b : hs.bsdfs) any = any || b.type == BSDF_NORMALMAP;
+        if (any) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "normalmap: a scene with a `normalmap` BSDF and a `mesh_attribute` texture is not supported"; return false; }
+        for (uint32_t m = 0; m < d.mesh_count; ++m) {
+            DMesh &dm = hs.meshes[m];
+            const bool under = hs.bsdfs[dm.bsdf].type == BSDF_NORMALMAP;
+            if (!under) { dm.flags &= 3u; continue; }
+            if ((dm.flags & 3u) == 3u && !(dm.flags & HAR_MESH_TANGENT_FRAME)) {
+                err = "normalmap: mesh " + std::to_string(m) + " has vertex normals and texture coordinates: under a `normalmap` its shading frame needs per-vertex tangents, which are not implemented (a `rectangle`, and meshes without normals or without texture coordinates, are)";
+                return false;
+            }
+            if ((dm.flags & 3u) != 3u) dm.flags &= 3u;
         }
     }
     /* a `mesh_attribute` record belongs to ONE mesh: every BSDF record that reads it is reachable from that mesh alone (its record, the back side of a `twosided`, the
