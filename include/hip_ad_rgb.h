@@ -85,6 +85,16 @@ typedef struct HarInstance {
  * Meshes without normals or without texcoords keep coordinate_system(n).  Gradients (`prb`): the normal map's in the record's own row / bitmap -- d / d (looked-up colour)
  * through 2c - 1, the flip, normalize, the frame, the nested model's directional partials and the shadow term, scattered through the bitmap's taps --, the nested leaf
  * record's colour slot 0 in its own; the refusals of a blend scene hold for a scene with a normalmap record as well, and har_render_forward is refused.
+ *   type 9 bumpmap         (src/bsdfs/bumpmap.cpp)         `texture` = the height map: a bitmap, ONE channel (HAR_BSDF_MONO) or three (their luminance); `nested[0]` = the nested
+ *                          BSDF record; `alpha_u` = `scale`
+ * A bumpmap record evaluates nested[0] in the shading frame tilted by grad_uv = scale * Texture::eval_1_grad (frame(), bumpmap.cpp:224-253: dp_du' = fmadd(sh_n, grad_uv.x -
+ * dot(sh_n, dp_du), dp_du), likewise dp_dv'; n = normalize(cross(dp_du', dp_dv')), towards si.n, into the local frame; HAR_BSDF_NM_FLIP; s = normalize(fnmadd(n, dot(n,
+ * si.dp_du), si.dp_du)) taken literally; t = cross(n, s)); eval / pdf / sample behind the frame are the normalmap's, HAR_BSDF_NM_SHADOW included.  It sets no
+ * BSDFFlags::NormalMapped: ANY mesh may carry it, and no shape's frame changes.  nested[0] as for a normalmap; HAR_BSDF_TWOSIDED on the record is `twosided(bumpmap(X))`.
+ * Nesting it in a blend / mask / normalmap / bumpmap or those in it, the two-BSDF `twosided` over it, a constant or `mesh_attribute` height map and a scene that also
+ * holds a `mesh_attribute` texture are refused.  Gradients (`prb`): the height map's texels -- d / d grad_uv by a reverse sweep through the frame, the nested model's
+ * directional partials and the shadow term, scattered through the transpose of eval_1_grad --, the nested leaf record's colour slot 0 in its own; the refusals of a
+ * normalmap scene hold.  har_bsdf_eval_pdf / har_bsdf_sample refuse such a record: its frame reads the interaction (har_bsdf_eval_pdf_si / har_bsdf_sample_si).
  * flags: bit0 twosided (src/bsdfs/twosided.cpp; `back` = record used for the back side, -1 = the same one),
  *        bit1 GGX distribution (else Beckmann), bit2 sample_visible, bit3 plastic / roughplastic `nonlinear`. */
 #define HAR_BSDF_DIFFUSE        0
@@ -96,13 +106,14 @@ typedef struct HarInstance {
 #define HAR_BSDF_BLEND          6
 #define HAR_BSDF_MASK           7
 #define HAR_BSDF_NORMALMAP      8
+#define HAR_BSDF_BUMPMAP        9
 #define HAR_BSDF_TWOSIDED       1u
 #define HAR_BSDF_GGX            2u
 #define HAR_BSDF_SAMPLE_VISIBLE 4u
 #define HAR_BSDF_NONLINEAR      8u
-#define HAR_BSDF_MONO           16u     /* blend / mask: the weight / opacity bitmap has one channel */
-#define HAR_BSDF_NM_FLIP        64u     /* normalmap: flip_invalid_normals */
-#define HAR_BSDF_NM_SHADOW      128u    /* normalmap: use_shadowing_function */
+#define HAR_BSDF_MONO           16u     /* blend / mask: the weight / opacity bitmap has one channel; bumpmap: the height bitmap has */
+#define HAR_BSDF_NM_FLIP        64u     /* normalmap / bumpmap: flip_invalid_normals */
+#define HAR_BSDF_NM_SHADOW      128u    /* normalmap / bumpmap: use_shadowing_function */
 #define HAR_MESH_TANGENT_FRAME  4u      /* HarMesh::flags: under a `normalmap` the frame's s follows the face's dp_du (a rectangle) */
 #define HAR_MESH_FRAME_FLIPPED  8u      /* HarMesh::flags: SurfaceInteraction::frame_flipped of the shape (to_world mirrors, flip_normals included) */
 typedef struct HarBSDF {
@@ -115,7 +126,7 @@ typedef struct HarBSDF {
     float    eta;                     /* int_ior / ext_ior */
     float    eta_c[3], k_c[3];        /* conductor: real and imaginary part of the relative IOR */
     int32_t  back;
-    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask / normalmap: nested[0] (read for types 6 - 8 only) */
+    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask / normalmap / bumpmap: nested[0] (read for types 6 - 9 only) */
 } HarBSDF;
 
 /* BitmapTexture, raw H x W x 3 f32 (src/textures/bitmap.cpp:175-206). HOST pointer.  mode = filter_type | wrap_mode (bitmap.cpp:182-206):
@@ -404,6 +415,13 @@ int har_bsdf_pdf(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint3
 int har_bsdf_sample(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv,
                     const float *sample1, const float *sample2 /*[2][n]*/, const uint8_t *active, float *wo /*[3][n]*/,
                     float *pdf, float *weight /*[3][n]*/, float *eta, uint32_t *sampled_type, uint32_t *sampled_component, void *stream);
+/* BSDF::eval_pdf / sample with more of the interaction: geom (DEVICE, 18 x n) = si.n, si.sh_frame.n, .s, .t, si.dp_du, si.dp_dv, three rows each -- what a `bumpmap`
+ * record's frame reads besides wi and uv (bumpmap.cpp:224-253).  Any record may be evaluated through them (only a bumpmap record reads geom); value OR pdf may be NULL. */
+int har_bsdf_eval_pdf_si(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom /*[18][n]*/,
+                         const uint8_t *active, float *value /*[3][n]*/, float *pdf, void *stream);
+int har_bsdf_sample_si(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1, const float *sample2 /*[2][n]*/,
+                       const float *geom /*[18][n]*/, const uint8_t *active, float *wo /*[3][n]*/, float *pdf, float *weight /*[3][n]*/, float *eta, uint32_t *sampled_type,
+                       uint32_t *sampled_component, void *stream);
 
 /* ------------------------------------------------------------------------
  *  Sensor / film
@@ -720,6 +738,23 @@ int har_surface_interaction_host(const HarSceneDesc *desc, uint32_t n, const flo
  * at uv: the chain through n_raw = 2c - 1, the flip (the branch taken), normalize, s, t, wi', wo', the nested model's directional partials and the shadow term (its
  * min(., 1) takes the branch the value takes); the orientation test carries no derivative; delta models give zero.  value (n) may be NULL.  All pointers HOST. */
 int har_normalmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo, const float *A, float *value, float *grad);
+/* The HOST twins of har_bsdf_eval_pdf_si / har_bsdf_sample_si (no GPU): the per-lane code of their kernels.  All pointers HOST. */
+int har_bsdf_eval_pdf_si_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo,
+                              const float *geom, const uint8_t *active, float *value, float *pdf);
+int har_bsdf_sample_si_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
+                            const float *sample2, const float *geom, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta,
+                            uint32_t *sampled_type, uint32_t *sampled_component);
+/* BitmapTexture::eval_1_grad (bitmap.cpp:543-599) of bitmap record `texture` and its transpose on the HOST (no GPU), by the per-lane code of the kernels: n lookups at uv
+ * (2 x n); grad (2 x n) = the gradient with respect to the surface's uv (no `scale`).  The bitmap counts as one-channel when a BSDF record that names it carries
+ * HAR_BSDF_MONO, else the luminance of its three channels is differentiated.  g (2 x n) with deposit (h x w x 3, ACCUMULATED into; both or neither) = the adjoint:
+ * deposit += the four signed tap weights of g at every lookup, times the channel's luminance coefficient (one channel: channel 0).  All pointers HOST. */
+int har_texture_eval_1_grad_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const float *uv, float *grad, const float *g, float *deposit);
+/* The derivative of a bumpmap record's value with respect to grad_uv = scale * eval_1_grad, on the HOST (no GPU): n tuples (wi 3 x n, uv 2 x n, wo 3 x n, geom 18 x n,
+ * A 3 x n) on record `bsdf` (type 9, possibly with HAR_BSDF_TWOSIDED); F = sum_k A_k value_k(wi, wo) under the default context, grad (2 x n) = dF / d grad_uv by the
+ * reverse sweep of har_bumpmap_grad.h (the selects carry no derivative; delta models give zero).  grad_uv (2 x n, may be NULL) replaces the looked-up gradient.
+ * value (n) may be NULL.  All pointers HOST. */
+int har_bumpmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom, const float *A,
+                          const float *grad_uv, float *value, float *grad);
 /* The AOV pass of AOVIntegrator::render (aov.cpp:389-470: one more SamplingIntegrator pass with the same sampler seed): lanes [lane_begin, lane_end) (0, 0 = all) of the
  * wavefront of render() at `seed` / `spp` -- the same lanes, film positions and camera rays as there -- accumulate into `aov_film` (DEVICE, H x W x (C + 1): the C
  * channels, then the reconstruction filter's weight; accumulated, not cleared, not developed).  `integrator` gives the chunk size (chunk_lanes) and the film window

@@ -147,6 +147,8 @@ SIGNATURES = {
     "har_bsdf_eval_pdf": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp, vp]),
     "har_bsdf_eval": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp]),
     "har_bsdf_pdf": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp]),
+    "har_bsdf_eval_pdf_si": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "har_bsdf_sample_si": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "har_bsdf_sample": (C.c_int, [vp, C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "har_image_write_exr": (C.c_int, [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_uint32]),
     "har_image_write_pfm": (C.c_int, [C.c_char_p, vp, C.c_uint32, C.c_uint32, C.c_uint32]),
@@ -201,6 +203,10 @@ SIGNATURES = {
     "har_surface_interaction_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, f32p, u32p, u32p, u32p, C.c_uint32, vp, f32p]),
     "har_normalmap_grad_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p]),
     "har_aov_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, f32p, f32p, vp, C.c_uint32, u32p, f32p]),
+    "har_bsdf_eval_pdf_si_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, vp, f32p, f32p]),
+    "har_bsdf_sample_si_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, u32p, u32p]),
+    "har_texture_eval_1_grad_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p]),
+    "har_bumpmap_grad_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
     "har_bsdf_eval_pdf_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, vp, f32p, f32p]),
     "har_bsdf_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, u32p, u32p]),
     "har_render_aovs": (C.c_int, [vp, vp, C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, u32p, vp, vp]),

@@ -596,7 +596,7 @@ def _cube(props):
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
-    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf',
+    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf', 'bumpmap': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
@@ -1151,8 +1151,10 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 # BitmapTexture(props) (src/textures/bitmap.cpp:175-260); `raw` only silences a range warning for float data in RGB variants, `accel` picks Dr.Jit's texture
 # hardware path on CUDA (no effect on values), `format` = the storage type of the texels ("auto" / "variant" / "fp16": this path keeps float32)
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
-BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8}
-_NESTING_BSDFS = ('blendbsdf', 'mask', 'normalmap')          # records that name nested records: built by the plugin factory
+BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8, 'bumpmap': 9}
+_NESTING_BSDFS = ('blendbsdf', 'mask', 'normalmap', 'bumpmap')          # records that name nested records: built by the plugin factory
+_MONO_TEX_BSDFS = ('blendbsdf', 'mask', 'bumpmap')          # records whose bitmap may have ONE channel (stored three times; `weight_channels`)
+_NOGRAD_PARAMS = ('ior', 'scale')          # non-colour parameters that are updatable and carry no gradient (ParamFlags::NonDifferentiable)
 _WEIGHTED_BSDFS = ('blendbsdf', 'mask')          # records whose slot 0 is a scalar texture (Texture::eval_1): the blend weight, the mask opacity
 _LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
 # (parameter name of slot 0, default), (parameter name of slot 1, default)
@@ -1316,13 +1318,34 @@ class BSDF:
         a = _mask(active, n); c = _ctx(ctx)
         val = torch.empty((3, n), dtype=torch.float32, device=dev) if which != 'pdf' else None
         pdf = torch.empty(n, dtype=torch.float32, device=dev) if which != 'eval' else None
-        if which == 'eval_pdf':
+        if self._reads_interaction():
+            # a `bumpmap` (also under a `twosided`): its frame reads si.n, si.sh_frame, si.dp_du and si.dp_dv (bumpmap.cpp:224-253) -- the entries that carry them
+            geom = self._geom(si, n)
+            check(lib().har_bsdf_eval_pdf_si(h, idx, c, n, _ptr(wi), _ptr(uv), _ptr(wo), _ptr(geom), _ptr(a), _ptr(val), _ptr(pdf), _stream()))
+        elif which == 'eval_pdf':
             check(lib().har_bsdf_eval_pdf(h, idx, c, n, _ptr(wi), _ptr(uv), _ptr(wo), _ptr(a), _ptr(val), _ptr(pdf), _stream()))
         elif which == 'eval':
             check(lib().har_bsdf_eval(h, idx, c, n, _ptr(wi), _ptr(uv), _ptr(wo), _ptr(a), _ptr(val), _stream()))
         else:
             check(lib().har_bsdf_pdf(h, idx, c, n, _ptr(wi), _ptr(uv), _ptr(wo), _ptr(a), _ptr(pdf), _stream()))
         return val, pdf
+
+    def _reads_interaction(self):
+        return self.kind == 'bumpmap'
+
+    @staticmethod
+    def _geom(si, n):
+        """the 18 x n rows a bumpmap's frame reads: si.n, si.sh_frame.n / .s / .t, si.dp_du, si.dp_dv"""
+        torch = _torch(); dev = _device()
+        frame = getattr(si, 'sh_frame', None)
+        rows = []
+        for name, v in (("n", getattr(si, 'n', None)), ("sh_frame.n", getattr(frame, 'n', None)), ("sh_frame.s", getattr(frame, 's', None)),
+                        ("sh_frame.t", getattr(frame, 't', None)), ("dp_du", getattr(si, 'dp_du', None)), ("dp_dv", getattr(si, 'dp_dv', None))):
+            if v is None:
+                raise RuntimeError("bumpmap: BSDF::eval / pdf / sample read si.%s (bumpmap.cpp:224-253), which this interaction does not carry" % name)
+            v = torch.as_tensor(v, dtype=torch.float32, device=dev).reshape(3, -1)
+            rows.append(v.expand(3, n) if v.shape[1] != n else v)
+        return torch.cat(rows, 0).contiguous()
 
     def eval_pdf(self, ctx, si, wo, active=True):
         """BSDF::eval_pdf(ctx, si, wo, active) (bsdf.h:431-465)"""
@@ -1345,7 +1368,11 @@ class BSDF:
         eta = torch.empty(n, dtype=torch.float32, device=dev)
         st = torch.empty(n, dtype=torch.int32, device=dev); sc = torch.empty(n, dtype=torch.int32, device=dev)
         a = _mask(active, n)
-        check(lib().har_bsdf_sample(h, idx, _ctx(ctx), n, _ptr(wi), _ptr(uv), _ptr(s1), _ptr(s2), _ptr(a), _ptr(wo), _ptr(pdf), _ptr(w), _ptr(eta), _ptr(st), _ptr(sc), _stream()))
+        if self._reads_interaction():
+            geom = self._geom(si, n)
+            check(lib().har_bsdf_sample_si(h, idx, _ctx(ctx), n, _ptr(wi), _ptr(uv), _ptr(s1), _ptr(s2), _ptr(geom), _ptr(a), _ptr(wo), _ptr(pdf), _ptr(w), _ptr(eta), _ptr(st), _ptr(sc), _stream()))
+        else:
+            check(lib().har_bsdf_sample(h, idx, _ctx(ctx), n, _ptr(wi), _ptr(uv), _ptr(s1), _ptr(s2), _ptr(a), _ptr(wo), _ptr(pdf), _ptr(w), _ptr(eta), _ptr(st), _ptr(sc), _stream()))
         bs = type("BSDFSample3f", (), dict(wo=wo, pdf=pdf, eta=eta, sampled_type=st, sampled_component=sc, delta=(st & BSDFFlags.Delta) != 0))()
         return bs, w
 
@@ -1535,6 +1562,115 @@ def _mk_normalmap(props, named, key):
     return NormalMapBSDF(nm, nested, bool(props.get('flip_invalid_normals', True)), bool(props.get('use_shadowing_function', True)), id=key)
 
 
+class Texture(dict):
+    """A texture plugin as mi.load_dict returns it: the plugin's properties (every consumer reads them as a dict), with the one method of the Texture interface that a
+    `bumpmap` calls.  eval_1_grad(si): BitmapTexture::eval_1_grad (bitmap.cpp:543-599) for a `bitmap` -- the gradient of eval_1 with respect to si.uv, a 2 x n tensor,
+    computed by the library's host entry (har_texture_eval_1_grad_host: the per-lane code of the kernels).  The call does NOT run on the device: it is a convenience entry
+    (uv is copied to the host and the result back); renders evaluate the gradient inside the shading kernels.  Every other texture raises
+    NotImplementedError("eval_1_grad"), as the base class does (src/render/texture.cpp:38-39)."""
+
+    def eval_1_grad(self, si, active=True):
+        if self.get('type') != 'bitmap':
+            raise NotImplementedError("eval_1_grad")
+        torch = _torch()
+        uv = torch.as_tensor(si.uv, dtype=torch.float32).reshape(2, -1)
+        n = uv.shape[1]
+        host = np.ascontiguousarray(uv.detach().cpu().numpy(), np.float32)
+        probe = self.__dict__.get('_probe')          # the private scene that holds the bitmap: lowered once per Texture object
+        if probe is None:
+            probe = BumpMapBSDF(dict(self), BSDF({'type': 'diffuse'}))
+            Scene({'_bsdf': probe})
+            self.__dict__['_probe'] = probe
+        d = probe.scene.desc()
+        out = np.zeros((2, n), np.float32)
+        check(lib().har_texture_eval_1_grad_host(C.byref(d), int(probe.tex_index), n, _fp(host), _fp(out), None, None))
+        if active is not True:
+            out = out * np.asarray(torch.as_tensor(active).detach().cpu().numpy(), np.float32).reshape(1, -1)
+        return torch.as_tensor(out, device=uv.device)
+
+
+class BumpMapBSDF(BSDF):
+    """BumpMap (src/bsdfs/bumpmap.cpp:102-135): a BSDF record whose texture is the height map -- a raw `bitmap` of one or three channels, read by Texture::eval_1_grad -- and
+    which names ONE nested BSDF: a plain model, or a `twosided` over one or two of them; it becomes a record of its own (Scene._add_bsdf).  `scale` rides in the record's
+    alpha_u.  flags: 16 = a one-channel height map, 64 = flip_invalid_normals, 128 = use_shadowing_function, 1 = wrapped by a `twosided`."""
+
+    def __init__(self, texture, nested, scale=1.0, flip_invalid_normals=True, use_shadowing_function=True, id=None):
+        self.id = id; self.kind = 'bumpmap'; self.slot0_name = 'nested_texture'; self.slot1_name = None
+        self.attr = None; self.attr_mesh = None
+        if not (isinstance(texture, dict) and texture.get('type') == 'bitmap'):
+            what = texture.get('type') if isinstance(texture, dict) else type(texture).__name__
+            raise RuntimeError("bumpmap: the nested texture is a `%s`: only a `bitmap` texture is supported in hip_ad_rgb (Texture::eval_1_grad is implemented by bitmaps; "
+                               "`rgb`, a float and `mesh_attribute` have none)" % what)
+        src = texture['data'] if 'data' in texture else (texture['bitmap'].data if isinstance(texture.get('bitmap'), Bitmap) else Bitmap(texture['filename']).data)
+        ch = 1 if len(tuple(src.shape)) == 2 else int(src.shape[2])
+        if ch not in (1, 3):
+            raise RuntimeError("bumpmap: the height bitmap has %d channels, expected 1 or 3" % ch)
+        self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(texture)
+        self.weight_channels = ch
+        self.value = _f32([0.5, 0.5, 0.5]); self.value2 = _f32([0, 0, 0])
+        self.flags = (16 if ch == 1 else 0) | (64 if flip_invalid_normals else 0) | (128 if use_shadowing_function else 0)
+        scale = float(np.float32(scale))
+        if not math.isfinite(scale):
+            raise RuntimeError("bumpmap: `scale` must be finite")
+        self.alpha_u = self.alpha_v = scale; self.eta = 1.0; self.anisotropic = False
+        self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
+        self.scene = None; self.index = None
+        self.nested = [nested]
+        if getattr(nested, 'mask_parent', None) is None and nested.scene is None:
+            nested.mask_parent = self          # NAMES its parameters '<bumpmap>.nested_bsdf.*' (BumpMap::traverse, bumpmap.cpp:131-135): Scene._bsdf_key_base
+
+    def _own_lobes(self):
+        """the nested BSDF's components -- those of its `twosided`, if it is one (bumpmap.cpp:124-128)"""
+        n = self.nested[0]
+        return [n._lobe_flags(i) for i in range(n.component_count())]
+
+    @property
+    def flags(self):
+        return _RecordFlags(self._flags, self)
+
+    @flags.setter
+    def flags(self, value):
+        self._flags = int(value)
+
+
+def _mk_bumpmap(props, named, key):
+    """the `bumpmap` plugin: exactly one nested texture and exactly one nested BSDF, both under free names (the constructor walks props.objects()), `scale`,
+    `flip_invalid_normals` and `use_shadowing_function` (bumpmap.cpp:102-122)"""
+    known = ('scale', 'flip_invalid_normals', 'use_shadowing_function')
+    for k, v in props.items():          # a plain number where the height map belongs: no object in the reference either; refused by name here
+        if k not in ('type', 'id') + known and isinstance(v, (int, float)) and not isinstance(v, bool):
+            raise RuntimeError("bumpmap: the nested texture \"%s\" is a `float`: only a `bitmap` texture is supported in hip_ad_rgb (Texture::eval_1_grad is implemented by "
+                               "bitmaps; `rgb`, a float and `mesh_attribute` have none)" % k)
+    _check_props('bumpmap', props, known, children=('bsdf', 'texture'))
+    nested = None; texture = None
+    for k, v in props.items():
+        if k in ('type', 'id') + known:
+            continue
+        obj = v
+        if isinstance(v, dict) and _PLUGIN_KINDS.get(v.get('type')) == 'texture':
+            obj = Texture(v)
+        elif isinstance(v, dict):
+            obj = _resolve(v, named, k)
+        if isinstance(obj, BSDF):
+            if nested is not None:
+                raise RuntimeError("Only a single BSDF child object can be specified.")
+            nested = obj
+        elif isinstance(obj, dict) and _PLUGIN_KINDS.get(obj.get('type')) == 'texture':
+            if texture is not None:
+                raise RuntimeError("Only a single Texture child object can be specified.")
+            texture = obj
+    if nested is None:
+        raise RuntimeError("Exactly one BSDF child object must be specified.")
+    if texture is None:
+        raise RuntimeError("Exactly one Texture child object must be specified.")
+    if nested.kind in _NESTING_BSDFS or (nested.back is not None and nested.back.kind in _NESTING_BSDFS):
+        raise RuntimeError("bumpmap: a nested `%s` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models, or `twosided` over them)"
+                           % (nested.kind if nested.kind in _NESTING_BSDFS else nested.back.kind))
+    if getattr(nested, 'attr', None) is not None or (nested.back is not None and getattr(nested.back, 'attr', None) is not None):
+        raise RuntimeError("bumpmap: a `mesh_attribute` texture on the nested BSDF is not supported in hip_ad_rgb")
+    return BumpMapBSDF(texture, nested, props.get('scale', 1.0), bool(props.get('flip_invalid_normals', True)), bool(props.get('use_shadowing_function', True)), id=key)
+
+
 def _mk_blendbsdf(props, named, key):
     """the `blendbsdf` plugin: `weight` and exactly two nested BSDFs under free names, in declaration order (blendbsdf.cpp:80-92)"""
     _check_props('blendbsdf', props, ('weight',), children=('bsdf',))
@@ -1554,8 +1690,8 @@ def _mk_blendbsdf(props, named, key):
     for c in nested:
         if c.kind == 'mask':
             raise RuntimeError("blendbsdf: a nested `mask` is not supported in hip_ad_rgb (put the `mask` outside, over plain BSDF models)")
-        if c.kind == 'normalmap':
-            raise RuntimeError("blendbsdf: a nested `normalmap` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models)")
+        if c.kind in ('normalmap', 'bumpmap'):
+            raise RuntimeError("blendbsdf: a nested `%s` is not supported in hip_ad_rgb (nested BSDFs are plain BSDF models)" % c.kind)
         if c.kind == 'blendbsdf' or (c.flags & 1):
             raise RuntimeError("blendbsdf: nested BSDFs must be plain BSDF models in this variant")
     return BlendBSDF(props['weight'], nested, id=key)
@@ -1563,7 +1699,7 @@ def _mk_blendbsdf(props, named, key):
 
 def _transmits(b):
     """does the BSDF have a transmission lobe (what `twosided` refuses, twosided.cpp:79-83)"""
-    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask' or (b.kind == 'normalmap' and _transmits(b.nested[0]))      # (BSDFFlags::Null is part of BSDFFlags::Transmission; a normalmap has its nested BSDF's lobes)
+    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask' or (b.kind in ('normalmap', 'bumpmap') and _transmits(b.nested[0]))      # (BSDFFlags::Null is part of BSDFFlags::Transmission; a normalmap has its nested BSDF's lobes)
 
 
 def _mk_twosided(props, named, key):
@@ -1583,6 +1719,8 @@ def _mk_twosided(props, named, key):
             raise RuntimeError("Only materials without a transmission component can be nested!")
     if len(nested) == 2 and nested[1] is not nested[0] and any(b.kind == 'normalmap' for b in nested):
         raise RuntimeError("twosided: two nested BSDFs with a `normalmap` among them are not supported in hip_ad_rgb (nest ONE normalmap: twosided(normalmap(X)))")
+    if len(nested) == 2 and nested[1] is not nested[0] and any(b.kind == 'bumpmap' for b in nested):
+        raise RuntimeError("twosided: two nested BSDFs with a `bumpmap` among them are not supported in hip_ad_rgb (nest ONE bumpmap: twosided(bumpmap(X)))")
     front = nested[0]
     if front.flags & 1:
         raise RuntimeError("twosided: nested BSDF is already two-sided")
@@ -2018,10 +2156,10 @@ class Integrator:
             check(lib().har_integrator_set_grad_instances(self._handle(), None, None))
         if self.bsdf_parameter_gradients and any(b.kind == 'mask' for b in scene.bsdfs):
             raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `mask` in hip_ad_rgb (its `opacity` and the nested BSDF's colour slot 0 have gradients)"
-                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what != "ior"))
+                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what not in _NOGRAD_PARAMS))
         if self.bsdf_parameter_gradients and any(b.kind == 'blendbsdf' for b in scene.bsdfs):
             raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `blendbsdf` in hip_ad_rgb (its `weight` and the nested BSDFs' colour slot 0 have gradients)"
-                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what != "ior"))
+                               % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what not in _NOGRAD_PARAMS))
         g_extra = torch.zeros((max(1, len(scene.bsdfs)), 15), dtype=torch.float32, device=dev) if self.bsdf_parameter_gradients else None
         try:
             check(lib().har_integrator_set_grad_emitters(self._handle(), _ptr(g_emit) if self.emitter_gradients else None))
@@ -2038,8 +2176,8 @@ class Integrator:
         out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None)
         if g_extra is not None:
             for k, (what, b) in scene._bsdf_param_keys().items():
-                if what == "ior":
-                    continue                  # (no gradient w.r.t. the scalar index of refraction)
+                if what in _NOGRAD_PARAMS:
+                    continue                  # (no gradient w.r.t. the scalar index of refraction or a bump map's `scale`)
                 rec = g_extra[b.index]
                 out[k] = {"alpha": rec[0:6].sum().reshape(1), "alpha_u": rec[0:3].sum().reshape(1), "alpha_v": rec[3:6].sum().reshape(1),
                           "eta": rec[6:9], "k": rec[9:12], "slot1": rec[12:15]}[what]
@@ -2094,7 +2232,7 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
                 raise RuntimeError("render_forward(): %s: expected a tangent of shape %s" % (k, (rows, dim)))
             for b in scene._attr_readers(mesh, name):
                 if id(b) in scene._blend_nested():
-                    raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
+                    raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` / `bumpmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
                 if dim == 1:
                     t_tex[b.tex_index].copy_(v.expand(rows, 3).reshape(rows, 1, 3))
                 elif dim == 3 and b.kind not in _WEIGHTED_BSDFS:
@@ -2103,7 +2241,7 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
         kind, b = keys[k]
         v = torch.as_tensor(v, dtype=torch.float32, device=dev)
         if kind != "emit" and id(b) in scene._blend_nested():
-            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
+            raise RuntimeError("render_forward(): %s -- forward-mode tangents of the BSDFs nested in a `blendbsdf` / `mask` / `normalmap` / `bumpmap` are not produced in hip_ad_rgb (a blend weight's / mask opacity's are; use render_backward)" % k)
         if kind != "emit" and b.kind in _WEIGHTED_BSDFS:
             # the tangent of the weight, in every colour channel of the record's slot 0 (a three-channel bitmap: of its luminance)
             if kind == "tex" and b.weight_channels == 3:
@@ -2472,7 +2610,7 @@ class Scene:
     def _blend_nested(self):
         """ids of the BSDF objects whose record is nested in a blend record of this scene -- also one that a shape or another blend references besides"""
         out = {id(c) for b in self.bsdf_objs for c in getattr(b, 'nested', ())}
-        return out | {id(c.back) for b in self.bsdf_objs if b.kind in ('mask', 'normalmap') for c in b.nested if c.back is not None}          # (mask: both sides of a nested `twosided` pair)
+        return out | {id(c.back) for b in self.bsdf_objs if b.kind in ('mask', 'normalmap', 'bumpmap') for c in b.nested if c.back is not None}          # (mask: both sides of a nested `twosided` pair)
 
     def _add_mesh(self, key, m):
         if m.bsdf is None:          # Shape(props), shape.cpp:50-57: a default diffuse BSDF -- black when the shape carries an emitter
@@ -2646,7 +2784,7 @@ class Scene:
             bsdfs[i].back = b.back.index if b.back is not None else -1
             if b.kind == 'blendbsdf':
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, b.nested[1].index)
-            elif b.kind in ('mask', 'normalmap'):
+            elif b.kind in ('mask', 'normalmap', 'bumpmap'):
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, -1)
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
@@ -2872,6 +3010,8 @@ class Scene:
                 keys[base + ".eta.value"] = ("eta", b); keys[base + ".k.value"] = ("k", b)
             if b.kind == 'roughplastic' and b.slot1_name:
                 keys[base + "." + b.slot1_name + ".value"] = ("slot1", b)
+            if b.kind == 'bumpmap':
+                keys[base + ".scale"] = ("scale", b)                  # BumpMap::traverse (bumpmap.cpp:134): a ScalarFloat, NonDifferentiable
             if b.kind in ('dielectric', 'plastic', 'roughplastic'):
                 # the relative index of refraction int_ior / ext_ior, a plain float: dielectric.cpp:238, plastic.cpp:185 (NonDifferentiable), roughplastic.cpp:211 (Differentiable
                 # there; updatable without a gradient here)
@@ -2879,7 +3019,7 @@ class Scene:
         return keys
 
     def _bsdf_param_value(self, what, b):
-        return {"alpha": [b.alpha_u], "alpha_u": [b.alpha_u], "alpha_v": [b.alpha_v], "eta": b.eta_c, "k": b.k_c, "slot1": b.value2, "ior": [b.eta]}[what]
+        return {"alpha": [b.alpha_u], "alpha_u": [b.alpha_u], "alpha_v": [b.alpha_v], "eta": b.eta_c, "k": b.k_c, "slot1": b.value2, "ior": [b.eta], "scale": [b.alpha_u]}[what]
 
     def _set_bsdf_param(self, what, b, v):
         """params.update() of a non-slot-0 BSDF parameter: the record is re-lowered IN PLACE when a scene handle exists (har_scene_set_bsdf_params), else with the first handle (roughplastic's sampling weights and
@@ -2891,7 +3031,11 @@ class Scene:
             b.eta = float(v[0])
             self._drop_handle()
             return
-        if what == "alpha":
+        if what == "scale":
+            if not math.isfinite(float(v[0])):
+                raise RuntimeError("bumpmap: `scale` must be finite")
+            b.alpha_u = b.alpha_v = float(v[0])
+        elif what == "alpha":
             b.alpha_u = b.alpha_v = float(v[0])
         elif what == "alpha_u":
             b.alpha_u = float(v[0])
@@ -3401,6 +3545,9 @@ class Scene:
                     out[k] = s if b.weight_channels == 1 else s * s.new_tensor(_LUMINANCE).reshape(1, 1, 3)
                 else:
                     out[k] = g_refl[b.index].sum().reshape(1)
+            elif b.kind == 'bumpmap':
+                # the height map: the commit deposited through the transpose of eval_1_grad -- the luminance coefficients are in it; a one-channel map received channel 0
+                out[k] = g_tex[b.tex_index] if b.weight_channels == 3 else g_tex[b.tex_index][:, :, :1].contiguous()
             else:
                 out[k] = g_tex[b.tex_index] if kind == "tex" else g_refl[b.index]
         # mesh attributes: the records of the BSDFs that read '<shape>.<name>' hold d L / d (row, channel) of their rows x 1 x 3 copy; back to the parameter's (rows, dim)
@@ -3421,7 +3568,7 @@ class Scene:
     @staticmethod
     def _colour_view(kind, b, value):
         """the value mi.traverse() shows for slot 0 of a BSDF: the stored one, except a blend's weight -- a scalar, or the H x W x 1 / x 3 bitmap it was given"""
-        if b.kind not in _WEIGHTED_BSDFS:
+        if b.kind not in _MONO_TEX_BSDFS:
             return value
         v = np.asarray(value, np.float32)
         if kind == "tex":
@@ -3431,7 +3578,7 @@ class Scene:
     @staticmethod
     def _colour_store(kind, b, t, key):
         """the inverse for a blend's weight, on a torch tensor or a numpy array: a scalar is stored as (w, w, w), a one-channel bitmap three times"""
-        if b.kind not in _WEIGHTED_BSDFS:
+        if b.kind not in _MONO_TEX_BSDFS:
             return t
         if kind == "tex":
             h, w = b.texture.shape[:2]; c = b.weight_channels
@@ -3467,7 +3614,7 @@ class SceneParameters(dict):
         if key in sc._param_keys() or key in sc._attr_keys():
             return ParamFlags.Differentiable
         if key in sc._bsdf_param_keys():
-            return ParamFlags.NonDifferentiable if sc._bsdf_param_keys()[key][0] == "ior" else (ParamFlags.Differentiable if sc._bsdf_param_keys()[key][0] == "slot1" else ParamFlags.Differentiable | ParamFlags.Discontinuous)
+            return ParamFlags.NonDifferentiable if sc._bsdf_param_keys()[key][0] in _NOGRAD_PARAMS else (ParamFlags.Differentiable if sc._bsdf_param_keys()[key][0] == "slot1" else ParamFlags.Differentiable | ParamFlags.Discontinuous)
         if key in sc._position_keys() or key in sc._instance_keys() or key in sc._rect_keys():
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
         if sc._pose_keys().get(key, (None,))[0] == "emitter_tex":
@@ -3942,7 +4089,7 @@ class DeviceGroup:
 # ---------------------------------------------------------------------------
 
 _REGISTRY = {}
-_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask', 'normalmap')
+_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask', 'normalmap', 'bumpmap')
 
 
 def register_plugin(name, variant_name, instantiate):
@@ -4086,13 +4233,13 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'bumpmap': _mk_bumpmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
     'shapegroup': _mk_shapegroup,
     'instance': _mk_instance,
-    'gaussian': lambda p, n, k: p, 'box': lambda p, n, k: p, 'rgb': lambda p, n, k: p, 'bitmap': lambda p, n, k: p, 'mesh_attribute': lambda p, n, k: p, 'area': lambda p, n, k: p,
+    'gaussian': lambda p, n, k: p, 'box': lambda p, n, k: p, 'rgb': lambda p, n, k: Texture(p), 'bitmap': lambda p, n, k: Texture(p), 'mesh_attribute': lambda p, n, k: Texture(p), 'area': lambda p, n, k: p,
 }.items():
     register_plugin(_name, VARIANT, _fn)
 
@@ -4147,9 +4294,12 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
     if fixed:       # ParamFlags::NonDifferentiable in the reference's traverse(): dr.enable_grad on them has no effect there; here it is said
         raise RuntimeError("%s are not differentiable parameters in hip_ad_rgb (placement of sensors and delta emitters: ParamFlags::NonDifferentiable in the reference; "
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
+    scales = [k for k in keys if scene._bsdf_param_keys().get(k, (None,))[0] == "scale"]
+    if scales:       # BumpMap::traverse registers `scale` as ParamFlags::NonDifferentiable (bumpmap.cpp:134)
+        raise RuntimeError("%s: the `scale` of a `bumpmap` is not a differentiable parameter (ParamFlags::NonDifferentiable; the height map's texels are)" % scales)
     nested = [k for k in keys if k in scene._bsdf_param_keys() and id(scene._bsdf_param_keys()[k][1]) in scene._blend_nested()]
     if nested:
-        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` / `normalmap` have no gradient in hip_ad_rgb (a blend's `weight`, a mask's `opacity` and the colour slot 0 of the BSDFs nested in them do)" % nested)
+        raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` / `normalmap` / `bumpmap` have no gradient in hip_ad_rgb (a blend's `weight`, a mask's `opacity` and the colour slot 0 of the BSDFs nested in them do)" % nested)
     if not keys:
         return integrator.render(scene, sensor, seed, spp)
     params.update()

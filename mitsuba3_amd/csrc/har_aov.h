@@ -43,7 +43,7 @@ inline const char *aov_spec_lower(uint32_t n, const uint32_t *types, AovSpec &sp
  *  - `diffuse`: the reflectance texture at si.uv (diffuse.cpp:181); `plastic` / `roughplastic`: `diffuse_reflectance` (plastic.cpp:362, roughplastic.cpp:504);
  *    both are colour slot 0 of the record;
  *  - every other model: the base class, eval(BSDFContext(), si, wo = (0, 0, 1)) * pi (src/render/bsdf.cpp:38-43). */
-template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK / HAR_SCENE_ATTR / HAR_SCENE_NORMALMAP bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
+template <uint32_t COMP = 0u>        /* COMP: the HAR_SCENE_BLEND / HAR_SCENE_MASK / HAR_SCENE_ATTR / HAR_SCENE_NORMALMAP / HAR_SCENE_BUMPMAP bits of the records the scene may hold (the kernels of other scenes compile those branches out) */
 HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = nullptr) {
     constexpr bool BLEND = (COMP & HAR_SCENE_BLEND) != 0u;
     BsdfSide side;
@@ -55,6 +55,11 @@ HAR_HD Vec3 aov_albedo(const DScene &S, const SurfInt &si, const AttrAddr *aa = 
     }
     if ((COMP & HAR_SCENE_NORMALMAP) != 0u && S.bsdfs[side.index].type == BSDF_NORMALMAP) {
         /* NormalMap::eval_diffuse_reflectance (normalmap.cpp:250-253): the nested BSDF's answer for the UNPERTURBED si (the side an outer `twosided` mirrored) */
+        const uint32_t nested = S.bsdfs[side.index].pad;
+        if (!bsdf_side(S, nested, side.wi, side)) return Vec3(0.f);
+    }
+    if ((COMP & HAR_SCENE_BUMPMAP) != 0u && S.bsdfs[side.index].type == BSDF_BUMPMAP) {
+        /* BumpMap::eval_diffuse_reflectance (bumpmap.cpp:259-262): the nested BSDF's answer for the UNPERTURBED si */
         const uint32_t nested = S.bsdfs[side.index].pad;
         if (!bsdf_side(S, nested, side.wi, side)) return Vec3(0.f);
     }
@@ -95,6 +100,17 @@ HAR_HD Vec3 aov_sh_normal_nmap(const DScene &S, const SurfInt &si) {
     return si.to_world(F.n);
 }
 
+/* ... and in a scene with a `bumpmap` record: BumpMap::sh_frame = frame(si) (bumpmap.cpp:255-257), n = si.to_world(frame.n); plain si.sh_frame under an outer
+ * `twosided`, as above.  P = the hit's position partials */
+HAR_HD Vec3 aov_sh_normal_bump(const DScene &S, const SurfInt &si, const SurfPartials &P) {
+    const DBsdf &B = S.bsdfs[S.meshes[si.mesh].bsdf];
+    if (B.type != BSDF_BUMPMAP) return aov_sh_normal_nmap(S, si);
+    if (B.flags & BF_TWOSIDED) return si.sn;
+    const BumpGeom G = bump_geom(S, B, si.n, si.sn, si.ss, si.st, P.dp_du, P.dp_dv, si.uv_x, si.uv_y);
+    const NormalFrame F = bumpmap_frame(B, G, si.wi);
+    return si.to_world(F.n);
+}
+
 template <uint32_t COMP = 0u>
 HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, Vec3 ray_d, const Hit &hit, bool active, float *out, size_t stride) {
     const bool valid = active && hit.t != HAR_INF;
@@ -105,7 +121,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
     if (valid) {
         si = compute_si(S, ray_d, hit.t, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
         if ((COMP & HAR_SCENE_NORMALMAP) != 0u) si_tangent_frame(S, si, ray_d, hit.u, hit.v, hit.prim, hit.shape, hit.inst);
-        if (need_partials) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
+        if (need_partials || (COMP & HAR_SCENE_BUMPMAP) != 0u) compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, P);
         if (need_albedo && (COMP & HAR_SCENE_ATTR) != 0u) {       /* scenes with a `mesh_attribute` texture: the albedo is looked up at the face and the barycentrics of si.p */
             AttrAddr addr; addr.face = 0u; addr.b1 = 0.f; addr.b2 = 0.f;
             if (hit.inst == 0xffffffffu) addr = attr_addr(S, si.p, hit.prim, hit.shape);
@@ -123,7 +139,7 @@ HAR_HD void aov_lane(const DScene &S, const AovSpec &spec, uint32_t top_meshes, 
                 case AOV_POSITION: v = si.p; break;
                 case AOV_UV: v.x = si.uv_x; v.y = si.uv_y; break;
                 case AOV_GEO_NORMAL: v = si.n; break;
-                case AOV_SH_NORMAL: v = (COMP & HAR_SCENE_NORMALMAP) != 0u ? aov_sh_normal_nmap(S, si) : si.sn; break;          /* BSDF::sh_frame(si): si.sh_frame unless a `normalmap` perturbs it */
+                case AOV_SH_NORMAL: v = (COMP & HAR_SCENE_BUMPMAP) != 0u ? aov_sh_normal_bump(S, si, P) : (COMP & HAR_SCENE_NORMALMAP) != 0u ? aov_sh_normal_nmap(S, si) : si.sn; break;          /* BSDF::sh_frame(si): si.sh_frame unless a `normalmap` perturbs it */
                 case AOV_DP_DU: v = P.dp_du; break;
                 case AOV_DP_DV: v = P.dp_dv; break;
                 case AOV_PRIM_INDEX: v.x = (float) hit.prim; break;

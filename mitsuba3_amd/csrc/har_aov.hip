@@ -113,6 +113,20 @@ __global__ __launch_bounds__(kBlock) void k_aov_fill_nmap(DScene S, AovSpec spec
     else { D = Vec3(d[i], d[n + i], d[2 * (size_t) n + i]); act = !(active && !active[i]); }
     const float4 a = h0[i]; const uint2 b = h1[i];
     Hit hit; hit.t = a.x; hit.u = a.y; hit.v = a.z; hit.prim = __float_as_uint(a.w); hit.shape = b.x; hit.inst = b.y;
+    aov_lane<HAR_SCENE_NMAP_RECORD_BITS>(S, spec, top_meshes, D, hit, act, aov + i, stride);
+}
+
+/* ... of a scene that holds a `bumpmap` record: the bump frame's shading normal (it reads the hit's position partials) and the nested albedo; a kernel of its own again */
+template <bool LANES>
+__global__ __launch_bounds__(kBlock) void k_aov_fill_bump(DScene S, AovSpec spec, uint32_t top_meshes, DSensor C, uint32_t seed, uint32_t spp, uint32_t log_spp, uint32_t lane_base,
+                                                          uint32_t n, const float *d, const uint8_t *active, const float4 *h0, const uint2 *h1, float *aov, size_t stride) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    Vec3 D; bool act = true;
+    if (LANES) { LaneSample ls; D = raygen_lane(C, seed, spp, log_spp, lane_base + i, ls).d; }
+    else { D = Vec3(d[i], d[n + i], d[2 * (size_t) n + i]); act = !(active && !active[i]); }
+    const float4 a = h0[i]; const uint2 b = h1[i];
+    Hit hit; hit.t = a.x; hit.u = a.y; hit.v = a.z; hit.prim = __float_as_uint(a.w); hit.shape = b.x; hit.inst = b.y;
     aov_lane<HAR_SCENE_RECORD_BITS>(S, spec, top_meshes, D, hit, act, aov + i, stride);
 }
 
@@ -234,6 +248,7 @@ void launch_aov_trace_rays(hipStream_t s, const DScene &S, bool deep, uint32_t n
 }
 void launch_aov_fill_lanes(hipStream_t s, const DScene &S, const AovSpec &spec, uint32_t top_meshes, const DSensor &C, uint32_t seed, uint32_t spp, uint32_t log_spp,
                            uint32_t lane_base, uint32_t n, const float4 *h0, const uint2 *h1, float *aov, size_t stride) {
+    if (S.bsdf_types & HAR_SCENE_BUMPMAP) { hipLaunchKernelGGL((k_aov_fill_bump<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
     if (S.bsdf_types & HAR_SCENE_NORMALMAP) { hipLaunchKernelGGL((k_aov_fill_nmap<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
     if (S.bsdf_types & HAR_SCENE_ATTR) { hipLaunchKernelGGL((k_aov_fill_attr<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
     if (S.bsdf_types & HAR_SCENE_MASK) { hipLaunchKernelGGL((k_aov_fill_mask<true>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, seed, spp, log_spp, lane_base, n, nullptr, nullptr, h0, h1, aov, stride); return; }
@@ -243,6 +258,7 @@ void launch_aov_fill_lanes(hipStream_t s, const DScene &S, const AovSpec &spec, 
 void launch_aov_fill_rays(hipStream_t s, const DScene &S, const AovSpec &spec, uint32_t top_meshes, uint32_t n, const float *d, const uint8_t *active,
                           const float4 *h0, const uint2 *h1, float *aov) {
     const DSensor C{};
+    if (S.bsdf_types & HAR_SCENE_BUMPMAP) { hipLaunchKernelGGL((k_aov_fill_bump<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }
     if (S.bsdf_types & HAR_SCENE_NORMALMAP) { hipLaunchKernelGGL((k_aov_fill_nmap<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }
     if (S.bsdf_types & HAR_SCENE_ATTR) { hipLaunchKernelGGL((k_aov_fill_attr<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }
     if (S.bsdf_types & HAR_SCENE_MASK) { hipLaunchKernelGGL((k_aov_fill_mask<false>), dim3(blocks_for(n)), dim3(kBlock), 0, s, S, spec, top_meshes, C, 0u, 1u, 0u, 0u, n, d, active, h0, h1, aov, (size_t) n); return; }

@@ -10,6 +10,7 @@
  *
  *   type 7  mask             src/bsdfs/mask.cpp:93-232                  (one nested record scaled by an opacity, and a null lobe; resolved in har_scene.h)
  *   type 8  normalmap        src/bsdfs/normalmap.cpp:100-253            (one nested record evaluated in a shading frame perturbed by a texel; resolved in har_scene.h)
+ *   type 9  bumpmap          src/bsdfs/bumpmap.cpp:102-253              (one nested record evaluated in a shading frame tilted by the uv-gradient of a height bitmap; resolved in har_scene.h)
  *
  * plus include/mitsuba/render/fresnel.h:35-91 (fresnel), :93-116 (fresnel_conductor), :276-313 (reflect / refract)
  * and  include/mitsuba/render/microfacet.h:185-421 (MicrofacetDistribution eval / pdf / sample / smith_g1).
@@ -27,14 +28,15 @@ namespace har {
 enum { BSDF_DIFFUSE = 0, BSDF_DIELECTRIC = 1, BSDF_ROUGHCONDUCTOR = 2, BSDF_ROUGHPLASTIC = 3, BSDF_CONDUCTOR = 4, BSDF_PLASTIC = 5, BSDF_TYPE_COUNT = 6 /* the leaf models */,
        BSDF_BLEND = 6 /* a record that names two leaf records (DBsdf::table, ::pad) and mixes them by the weight in slot 0 */,
        BSDF_MASK = 7 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and scales it by the opacity in slot 0, with a null lobe for the rest */,
-       BSDF_NORMALMAP = 8 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame perturbed by the normal-map colour in slot 0 */ };
+       BSDF_NORMALMAP = 8 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame perturbed by the normal-map colour in slot 0 */,
+       BSDF_BUMPMAP = 9 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame tilted by `scale` (DBsdf::alpha_u) times the uv-gradient of its height bitmap (DBsdf::texture) */ };
 /* BF_MONO: the bitmap in slot 0 of a blend record has ONE channel (stored three times): Texture::eval_1 reads it instead of taking the luminance (bitmap.cpp:537-540).
  * BF_BLEND_SMOOTH: derived when a blend record is lowered -- one of its nested BSDFs has a smooth lobe (BSDFFlags::Smooth of the union, blendbsdf.cpp:99)
  * BF_MASK_SMOOTH (the same bit, in a mask record): the nested BSDF -- either side of a nested `twosided` pair -- has a smooth lobe (mask.cpp:113) */
 enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u, BF_MONO = 16u, BF_BLEND_SMOOTH = 32u, BF_MASK_SMOOTH = 32u };
 /* a normalmap record: BF_NM_SMOOTH (the same derived bit again: the nested BSDF has a smooth lobe), BF_NM_FLIP = flip_invalid_normals, BF_NM_SHADOW = use_shadowing_function
  * (normalmap.cpp:114-115) */
-enum { BF_NM_SMOOTH = 32u, BF_NM_FLIP = 64u, BF_NM_SHADOW = 128u };
+enum { BF_NM_SMOOTH = 32u, BF_NM_FLIP = 64u, BF_NM_SHADOW = 128u };          /* (a bumpmap record reads the same three bits, and BF_MONO for a one-channel height map) */
 enum { LOBE_NULL = 0x1u };                    /* BSDFFlags::Null (bsdf.h:37): the only lobe of that kind is the mask record's */
 #define HAR_ROUGH_TRANSMITTANCE_RES 64          /* MI_ROUGH_TRANSMITTANCE_RES, include/mitsuba/render/microfacet.h */
 
@@ -50,7 +52,7 @@ struct DBsdf {
     int32_t back;                 /* twosided: BSDF record of the back side (-1: the same record) */
     int32_t table;                /* roughplastic: offset of its 64-entry external transmittance table, else -1; blend: record index of nested BSDF 0 */
     float inv_eta_2, internal_reflectance, spec_sampling_weight;
-    uint32_t pad;                 /* blend: record index of nested BSDF 1; mask / normalmap: record index of its nested BSDF (`table` stays -1) */
+    uint32_t pad;                 /* blend: record index of nested BSDF 1; mask / normalmap / bumpmap: record index of its nested BSDF (`table` stays -1) */
 };
 static_assert(sizeof(DBsdf) == 96, "DBsdf layout");
 
@@ -332,9 +334,17 @@ static_assert((HAR_SCENE_ATTR & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1
  * line of normal-map code sits behind a test of this bit.  HAR_SCENE_RECORD_BITS: the bits a leaf model never sees */
 #define HAR_SCENE_NORMALMAP 0x4000u
 #define HAR_SCENE_NORMALMAP_TYPES (HAR_SCENE_MASK_TYPES | HAR_SCENE_NORMALMAP)
-#define HAR_SCENE_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP)
-#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
-static_assert((HAR_SCENE_NORMALMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x80000000u)) == 0u, "HAR_SCENE_NORMALMAP collides with another scene bit");
+/* ... and a `bumpmap` record (type 9): the frame comes from the uv-gradient of a height bitmap and from the interaction's dp_du / dp_dv / n, which only the vertices on
+ * such a record compute.  A scene with such a record sets this bit and runs a widest set of its own, TYPES = HAR_SCENE_BUMPMAP_TYPES = the normalmap set | HAR_SCENE_BUMPMAP
+ * (normalmap, mask and blend records may sit on other meshes); every line of bump code sits behind a test of this bit.  HAR_SCENE_NMAP_RECORD_BITS: what the kernels of a
+ * normalmap scene resolve (they keep their code) */
+#define HAR_SCENE_BUMPMAP 0x8000u
+#define HAR_SCENE_BUMPMAP_TYPES (HAR_SCENE_NORMALMAP_TYPES | HAR_SCENE_BUMPMAP)
+#define HAR_SCENE_NMAP_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP)
+#define HAR_SCENE_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP)
+#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
+static_assert((HAR_SCENE_NORMALMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x8000u | 0x80000000u)) == 0u, "HAR_SCENE_NORMALMAP collides with another scene bit");
+static_assert((HAR_SCENE_BUMPMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x4000u | 0x80000000u)) == 0u, "HAR_SCENE_BUMPMAP collides with another scene bit");
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */

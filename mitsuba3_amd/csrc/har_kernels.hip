@@ -1031,6 +1031,25 @@ __device__ __forceinline__ void blend_child_commit(const DScene &S, float *grad_
         wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
     }
 }
+/* (gu, gv) = d L / d grad_uv of a vertex on BUMPMAP record `rec` (grad_uv = scale * eval_1_grad of its height bitmap at (u, v)) deposited in that bitmap's gradient
+ * buffer through the transpose of eval_1_grad (tex_eval_1_grad_transpose: four signed tap weights, times the luminance coefficient of the channel, or channel 0 of a
+ * one-channel map).  Called by whole waves; lanes aimed at the same texel are pre-reduced, as in blend_child_commit. */
+__device__ __forceinline__ void bump_texel_commit(const DScene &S, float *const *grad_tex, bool pred, uint32_t rec, float u, float v, float gu, float gv) {
+    pred = pred && (gu != 0.f || gv != 0.f);
+    if (!__ballot(pred)) return;
+    TexTaps taps; float *dst = nullptr; float w[4] = { 0.f, 0.f, 0.f, 0.f }; Vec3 ch(0.f);
+    taps.idx[0] = taps.idx[1] = taps.idx[2] = taps.idx[3] = 0u; taps.w0x = taps.w1x = taps.w0y = taps.w1y = 0.f;
+    if (pred) {
+        const DBsdf &B = S.bsdfs[rec];
+        tex_eval_1_grad_transpose(S.textures[B.texture], u, v, gu, gv, B.alpha_u, taps, w);
+        ch = tex_eval_1_grad_channels((B.flags & BF_MONO) != 0u);
+        dst = grad_tex[B.texture];
+    }
+    for (int k = 0; k < 4; ++k) {
+        const bool on = pred && w[k] != 0.f;
+        wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? ch * w[k] : Vec3(0.f), on);
+    }
+}
 /* ATTR (forward mode of a scene with a `mesh_attribute` texture, k_resolve_forward_attr): the item of a vertex whose record reads an attribute carries the barycentrics
  * (b1, b2) in its uv words (shade_lane), and the face comes from the bounce's replay-cache hit record of the item's lane, `hits` */
 template <bool FWD = false, bool ATTR = false>
@@ -1418,6 +1437,12 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                         g = g + v * dk[k];
                     }
                 }
+                if ((TYPES & HAR_SCENE_BUMPMAP) != 0u) {
+                    /* ... a bumpmap vertex files the two partials with respect to grad_uv in g.x / g.y: deposited through the transpose of eval_1_grad into the height map */
+                    const bool is_bump = on && S.bsdfs[R.nm_rec].type == BSDF_BUMPMAP;
+                    bump_texel_commit(S, grad_tex, is_bump, is_bump ? R.nm_rec : 0u, R.uv_x, R.uv_y, g.x, g.y);
+                    blend_child_commit(S, grad_slots, grad_tex, on && !is_bump, (on && !is_bump) ? R.nm_rec : 0u, R.uv_x, R.uv_y, g);
+                } else
                 blend_child_commit(S, grad_slots, grad_tex, on, on ? R.nm_rec : 0u, R.uv_x, R.uv_y, g);
             }
             /* write-back: replay -> the survivor's slot of the next bounce (the primal pass's compaction, TapeArrays::next); otherwise the lane's result */
@@ -2312,7 +2337,7 @@ __global__ void k_api_bsdf_eval_pdf_nmap(DScene S, uint32_t bsdf, BsdfCtx ctx, u
     if (!(active && !active[i])) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
     }
     if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
     if (pdf) pdf[i] = e.pdf;
@@ -2325,7 +2350,7 @@ __global__ void k_api_bsdf_sample_nmap(DScene S, uint32_t bsdf, BsdfCtx ctx, uin
     if (!(active && !active[i])) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
+        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i]);
     }
     wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
     weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
@@ -2339,6 +2364,19 @@ __global__ void k_api_si_nmap(DScene S, uint32_t n, const float *o, const float 
     if (i >= n) return;
     (void) o;
     si_rows_tangent(S, n, i, Vec3(d[i], d[n + i], d[2 * (size_t) n + i]), t[i], u[i], v[i], prim[i], shape[i], inst[i], ray_flags, !(active && !active[i]), out);
+}
+/* ... the entries that carry the interaction (har_bsdf_eval_pdf_si / har_bsdf_sample_si): the set that also resolves a `bumpmap` record, whose frame reads `geom`
+ * (18 x n: si.n, sh_frame.n / .s / .t, dp_du, dp_dv).  Kernels of their own: the ones above keep their code and names */
+__global__ void k_api_bsdf_eval_pdf_bump(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom, const uint8_t *active, float *value, float *pdf) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_eval_pdf_si_lane(S, bsdf, ctx, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+}
+__global__ void k_api_bsdf_sample_bump(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom, const uint8_t *active,
+                                       float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_sample_si_lane(S, bsdf, ctx, n, i, wi, uv, s1, s2, geom, !(active && !active[i]), wo, pdf, weight, eta, stype, scomp);
 }
 /* `path` in a scene with a mask record: the radiance of a camera sample that stayed invalid is dropped, dr::select(valid_ray, result, 0) (path.cpp:341-345) */
 __global__ void k_drop_invalid(uint32_t n, const float *valid, float4 *result) {
@@ -2450,6 +2488,23 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_BUMPMAP) {
+        /* a scene with a `bumpmap` record: the normalmap set (normalmap, mask and blend records may sit on other meshes) plus the bump frame.  The same three shading
+         * kernels as a normalmap scene (below): forward, prb primal and the in-place adjoint commit, which deposits the height map's gradient through the transpose of
+         * eval_1_grad and the nested colours' as under a mask.  No item-writing adjoint: run_chunk refuses those modes before any launch */
+        constexpr uint32_t T = HAR_SCENE_BUMPMAP_TYPES;
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PATH)
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags of a scene that also holds a mask record, or null (run_chunk) */, no_mq, 0u, tape);
+        else if (mode == MODE_PRB_PRIMAL)
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else {
+            fprintf(stderr, "hip_ad_rgb: launch_shade: a scene with a `bumpmap` record has no shading kernel for mode %d without the in-place commit\n", mode);
+            abort();
+        }
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_NORMALMAP) {
         /* a scene with a `normalmap` record: the mask set (blend and mask records may sit on other meshes) plus the perturbed frame and the tangent frame of shapes that
          * pack one.  Three shading kernels: forward, prb primal and the in-place adjoint commit of a cached / taped bounce, which deposits the normal map's and the
@@ -2729,6 +2784,14 @@ void launch_api_pdf_emitter(hipStream_t s, const DScene &S, uint32_t n, const ui
 }
 void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out, int dims) {
     hipLaunchKernelGGL(k_api_sampler_next, dim3(blocks_for(n)), dim3(kBlock), 0, s, n, state, inc, active, out, dims);
+}
+void launch_api_bsdf_eval_pdf_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom,
+                                 const uint8_t *active, float *value, float *pdf) {
+    hipLaunchKernelGGL(k_api_bsdf_eval_pdf_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf);
+}
+void launch_api_bsdf_sample_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom,
+                               const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    hipLaunchKernelGGL(k_api_bsdf_sample_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp);
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {

@@ -13,6 +13,7 @@
 #pragma once
 #include "har_scene.h"
 #include "har_normalmap_grad.h"
+#include "har_bumpmap_grad.h"
 
 namespace har {
 
@@ -96,7 +97,9 @@ struct ShadeResult {
      * nm_rel[k] = (d value_k / d c) / value_k at the sampled direction, one vector over the three components of c per radiance channel k
      * (normalmap_weighted_value_grad with A = the k-th unit weight); nm_rec = the normalmap record (0xffffffff: none), nm_ind: the second term exists.  The in-place commit
      * of k_shade forms g = sum_k dL_k ([visible] nm_dir[k] + L_k nm_rel[k]) and scatters it through the record's taps.  The nested LEAF record's colour gradient rides in
-     * bl_*[0] as under a mask. */
+     * bl_*[0] as under a mask.
+     * A BUMPMAP vertex (kernels of bump scenes, HAR_SCENE_BUMPMAP) rides in the same fields: nm_rec = the bumpmap record, nm_dir[k] / nm_rel[k] = the two partials with
+     * respect to grad_uv = scale * eval_1_grad in .x / .y (bumpmap_weighted_value_grad), .z unused; the commit deposits through the transpose of eval_1_grad. */
     uint32_t nm_rec; Vec3 nm_dir[3], nm_rel[3]; bool nm_ind;
 };
 #define HAR_EXTRA_GROUPS 5
@@ -260,7 +263,15 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     const bool mask = (TYPES & HAR_SCENE_MASK) != 0u && B.type == BSDF_MASK;
     /* a normalmap record (kernels of normalmap scenes only): Smooth if its nested BSDF is (normalmap.cpp:117-122); it files the nested leaf's colour gradient as a mask does */
     const bool nmap = (TYPES & HAR_SCENE_NORMALMAP) != 0u && B.type == BSDF_NORMALMAP;
-    const bool composite = blend || mask || nmap;
+    /* a bumpmap record (kernels of bump scenes only): Smooth if its nested BSDF is (bumpmap.cpp:124-128); the frame reads dp_du / dp_dv, computed for these vertices only */
+    const bool bump = (TYPES & HAR_SCENE_BUMPMAP) != 0u && B.type == BSDF_BUMPMAP;
+    BumpGeom bgeom; bgeom.gx = 0.f; bgeom.gy = 0.f;
+    if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump) {
+        SurfPartials SP; compute_si_partials(S, hit.u, hit.v, hit.prim, hit.shape, hit.inst, false, SP);
+        bgeom = bump_geom(S, B, si.n, si.sn, si.ss, si.st, SP.dp_du, SP.dp_dv, si.uv_x, si.uv_y);
+    }
+    const BumpGeom *const bg = ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump) ? &bgeom : nullptr;
+    const bool composite = blend || mask || nmap || bump;
     const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR)
                                                : (composite ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
@@ -323,9 +334,9 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     float s1 = pcg32_next_float(rng, inc);
     float s2x = pcg32_next_float(rng, inc), s2y = pcg32_next_float(rng, inc);
     BlendChildGrad cg;          /* blend vertex, prb: d value / d slot 0 of the two nested records (both passes of a backward step: the shadow-ray condition below reads it) */
-    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr, aa);
+    BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr, aa, bg);
     BsdfSample bs; bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
-    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y, aa);
+    if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y, aa, bg);
     if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH) R.non_null = !(mask && bs.type == LOBE_NULL);        /* path.cpp:307-308 (si is valid here) */
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
@@ -351,6 +362,16 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                         float dc[3];
                         normalmap_weighted_value_grad(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dc);
                         R.nm_dir[k] = Vec3(dc[0], dc[1], dc[2]);
+                    }
+                }
+                if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump && side_ok) {          /* d Lr_dir / d grad_uv, channel by channel of the radiance */
+                    const Vec3 w = (st.throughput * mis_em) * em_weight;
+                    const Vec3 wo_f(wo_em.x, wo_em.y, wo_em.z * side.wo_sign);
+                    const float wk[3] = { w.x, w.y, w.z };
+                    for (int k = 0; k < 3; ++k) {
+                        float dg[2];
+                        bumpmap_weighted_value_grad(S, B, bgeom, bgeom.gx, bgeom.gy, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dg);
+                        R.nm_dir[k] = Vec3(dg[0], dg[1], 0.f);
                     }
                 }
                 if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
@@ -427,7 +448,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT) {
         /* Lr_ind = L * relative_grad(bsdf.eval(si, wo, active_next)) (prb.py:288-297): d/d slot0 = L * (df/dslot0) / f */
         Vec3 wo = si.to_local(wo_world);
-        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2, BsdfCtx(), si.uv_x, si.uv_y, (TYPES & HAR_SCENE_BLEND) != 0u ? &cg : nullptr, aa);
+        BsdfEval e2; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok && alive, wo, e2, BsdfCtx(), si.uv_x, si.uv_y, (TYPES & HAR_SCENE_BLEND) != 0u ? &cg : nullptr, aa, bg);
         R.rel_grad = Vec3(e2.value.x != 0.f ? e2.d_slot0.x / e2.value.x : 0.f, e2.value.y != 0.f ? e2.d_slot0.y / e2.value.y : 0.f,
                           e2.value.z != 0.f ? e2.d_slot0.z / e2.value.z : 0.f);
         R.ind_active = alive && (R.rel_grad.x != 0.f || R.rel_grad.y != 0.f || R.rel_grad.z != 0.f);
@@ -451,6 +472,10 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 const NormalFrame NF = normalmap_frame(B, bin.slot0, side.wi);
                 BsdfSide ns; R.bl_rec[0] = (side_ok && bsdf_side(S, B.pad, NF.to_local(side.wi), ns)) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
             }
+            if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump) {          /* likewise, in the bump frame */
+                const NormalFrame NF = bumpmap_frame(B, bgeom, side.wi);
+                BsdfSide ns; R.bl_rec[0] = (side_ok && bsdf_side(S, B.pad, NF.to_local(side.wi), ns)) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
+            }
             if (mask) {          /* one nested record: the leaf that serves this side of a nested `twosided` (none where a two-BSDF pair is zero, wi.z == 0) */
                 BsdfSide ns; R.bl_rec[0] = bsdf_side(S, B.pad, si.wi, ns) ? ns.index : 0xffffffffu; R.bl_rec[1] = 0xffffffffu;
             }
@@ -471,6 +496,20 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 normalmap_weighted_value_grad(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f), dc);
                 R.nm_rel[k] = Vec3(dc[0] / vk[k], dc[1] / vk[k], dc[2] / vk[k]);
                 R.nm_ind = R.nm_ind || dc[0] != 0.f || dc[1] != 0.f || dc[2] != 0.f;
+            }
+            R.item = R.item || R.nm_ind;
+        }
+        if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump && side_ok) {
+            /* Lr_ind = L * relative_grad(bsdf.eval(si, wo)) with respect to grad_uv: (d value_k / d grad_uv) / value_k per radiance channel k */
+            R.nm_rec = side.index;
+            const float vk[3] = { e2.value.x, e2.value.y, e2.value.z };
+            const Vec3 wo_f(wo.x, wo.y, wo.z * side.wo_sign);
+            for (int k = 0; k < 3; ++k) {
+                if (!alive || vk[k] == 0.f) continue;
+                float dg[2];
+                bumpmap_weighted_value_grad(S, B, bgeom, bgeom.gx, bgeom.gy, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? 1.f : 0.f, k == 1 ? 1.f : 0.f, k == 2 ? 1.f : 0.f), dg);
+                R.nm_rel[k] = Vec3(dg[0] / vk[k], dg[1] / vk[k], 0.f);
+                R.nm_ind = R.nm_ind || dg[0] != 0.f || dg[1] != 0.f;
             }
             R.item = R.item || R.nm_ind;
         }

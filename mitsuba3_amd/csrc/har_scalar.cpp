@@ -18,6 +18,7 @@
 #include "har_path.h"
 #include "har_aov.h"
 #include "har_normalmap_grad.h"
+#include "har_bumpmap_grad.h"
 #include "har_scene_host.h"
 
 #include <algorithm>
@@ -64,7 +65,7 @@ struct BoundScene {
         S.n_emitters = (uint32_t) hs.emitters.size(); S.n_meshes = (uint32_t) hs.meshes.size();
         S.n_bsdfs = (uint32_t) hs.bsdfs.size(); S.n_insts = (uint32_t) hs.insts.size(); S.n_textures = (uint32_t) hs.textures.size();
         S.env_emitter = hs.env_emitter;
-        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
         for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) S.bsdf_types |= HAR_SCENE_ATTR;
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
         hs.bind_tables(S, hs.emitter_distr.data());
@@ -119,6 +120,7 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
         if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
+        else if (S.bsdf_types & HAR_SCENE_BUMPMAP) shade_lane<MODE_PATH, HAR_SCENE_BUMPMAP_TYPES>(S, P, st, hit, R);      /* ... with a `bumpmap` record the bump frame as well */
         else if (S.bsdf_types & HAR_SCENE_NORMALMAP) shade_lane<MODE_PATH, HAR_SCENE_NORMALMAP_TYPES>(S, P, st, hit, R);      /* ... with a `normalmap` record the perturbed and the tangent frames */
         else shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
         /* path.cpp:307-308; in a scene with a `mask` record the vertex decides (a null lobe does not make the sample valid: ShadeResult::non_null, which also follows the
@@ -296,7 +298,8 @@ extern "C" int har_aov_sample_host(const HarSceneDesc *desc, uint32_t n, const f
             Hit hit; hit.t = HAR_INF; hit.u = 0.f; hit.v = 0.f; hit.prim = 0; hit.shape = 0; hit.inst = 0xffffffffu;
             if (act) { ScalarStack stack; accel_trace<false>(S.accel, O, D, maxt[i], hit, stack, status); }
             if (S.bsdf_types & HAR_SCENE_ATTR) aov_lane<HAR_SCENE_WIDEST>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
-            else if (S.bsdf_types & HAR_SCENE_NORMALMAP) aov_lane<HAR_SCENE_RECORD_BITS>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            else if (S.bsdf_types & HAR_SCENE_BUMPMAP) aov_lane<HAR_SCENE_RECORD_BITS>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
+            else if (S.bsdf_types & HAR_SCENE_NORMALMAP) aov_lane<HAR_SCENE_NMAP_RECORD_BITS>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
             else aov_lane<HAR_SCENE_COMPOSITE>(S, spec, B.hs.top_mesh_count, D, hit, act, out + i, (size_t) n);
         }
         if (status) return har_set_error("har_aov_sample_host: traversal stack overflow");
@@ -362,6 +365,110 @@ extern "C" int har_normalmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, 
     catch (const std::exception &ex) { return har_set_error(std::string("har_normalmap_grad_host: ") + ex.what()); }
 }
 
+/* The twins of har_bsdf_eval_pdf_si / har_bsdf_sample_si: the lane functions their kernels run (bsdf_eval_pdf_si_lane / bsdf_sample_si_lane, har_scene.h) over HOST arrays;
+ * geom = 18 x n (si.n, sh_frame.n, .s, .t, dp_du, dp_dv), read for a bumpmap record */
+extern "C" int har_bsdf_eval_pdf_si_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo,
+                                         const float *geom, const uint8_t *active, float *value, float *pdf) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+        BsdfCtx c; c = BsdfCtx();
+        if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
+        if (n == 0) return 0;
+        if (!wi || !uv || !wo || !geom) return har_set_error("null input arrays");
+        for (uint32_t i = 0; i < n; ++i) bsdf_eval_pdf_si_lane(B.ds, bsdf, c, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_eval_pdf_si_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_eval_pdf_si_host: ") + ex.what()); }
+}
+extern "C" int har_bsdf_sample_si_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
+                                       const float *sample2, const float *geom, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta,
+                                       uint32_t *sampled_type, uint32_t *sampled_component) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+        BsdfCtx c; c = BsdfCtx();
+        if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
+        if (n == 0) return 0;
+        if (!wi || !uv || !sample2 || !geom || !wo || !pdf || !weight) return har_set_error("null input / output arrays");
+        for (uint32_t i = 0; i < n; ++i) bsdf_sample_si_lane(B.ds, bsdf, c, n, i, wi, uv, sample1, sample2, geom, !(active && !active[i]), wo, pdf, weight, eta, sampled_type, sampled_component);
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_sample_si_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_si_host: ") + ex.what()); }
+}
+
+/* BitmapTexture::eval_1_grad and its transpose on the host, by the functions the kernels run (tex_eval_1_grad, tex_eval_1_grad_transpose): n lookups of texture record
+ * `texture` -- a bitmap; HAR_BSDF_MONO among the flags of a BSDF record that names it: ONE channel, else the luminance of three -- at uv (2 x n).  grad (2 x n) = the
+ * gradient with respect to the surface's uv, WITHOUT a bump map's `scale`.  With g (2 x n) and deposit (h x w x 3, ACCUMULATED into; both or neither) the adjoint:
+ * deposit += the four signed tap weights of (g_u, g_v) at every lookup, times the channel's luminance coefficient (one channel: into channel 0). */
+extern "C" int har_texture_eval_1_grad_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const float *uv, float *grad, const float *g, float *deposit) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        const DScene &S = B.ds;
+        if (texture >= S.n_textures) return har_set_error("invalid texture index");
+        const DTexture T = S.textures[texture];
+        if (T.mode & HAR_TEX_ATTRIBUTE) return har_set_error("eval_1_grad: not a bitmap texture (a `mesh_attribute` record)");
+        bool mono = false; for (const DBsdf &b : B.hs.bsdfs) if (b.texture == (int32_t) texture && (b.flags & BF_MONO)) mono = true;
+        if (n == 0) return 0;
+        if (!uv || !grad || (!g != !deposit)) return har_set_error("null input / output arrays");
+        const Vec3 ch = tex_eval_1_grad_channels(mono);
+        for (uint32_t i = 0; i < n; ++i) {
+            float gu, gv; tex_eval_1_grad(T, mono, uv[i], uv[n + (size_t) i], gu, gv);
+            grad[i] = gu; grad[n + (size_t) i] = gv;
+            if (g) {
+                TexTaps l; float w[4]; tex_eval_1_grad_transpose(T, uv[i], uv[n + (size_t) i], g[i], g[n + (size_t) i], 1.f, l, w);
+                for (int k = 0; k < 4; ++k) { float *q = deposit + 3 * (size_t) l.idx[k]; q[0] += ch.x * w[k]; q[1] += ch.y * w[k]; q[2] += ch.z * w[k]; }
+            }
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_texture_eval_1_grad_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_texture_eval_1_grad_host: ") + ex.what()); }
+}
+
+/* d F / d grad_uv of a `bumpmap` record on the host (bumpmap_weighted_value_grad, har_bumpmap_grad.h): n tuples (wi 3 x n, uv 2 x n, wo 3 x n, geom 18 x n, A 3 x n) on
+ * record `bsdf` -- a bumpmap record, possibly under an outer one-BSDF `twosided`.  grad_uv (2 x n, may be NULL) overrides scale * eval_1_grad of the record's height map
+ * at uv (for finite differences in grad_uv).  value (n, may be NULL) = F = sum_k A_k value_k, grad (2 x n) = the two partials.  Default context. */
+extern "C" int har_bumpmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom, const float *A,
+                                     const float *grad_uv, float *value, float *grad) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.hs.bsdfs[bsdf].type != BSDF_BUMPMAP) return har_set_error("har_bumpmap_grad_host: not a bumpmap record");
+        if (n == 0) return 0;
+        if (!wi || !uv || !wo || !geom || !A || !grad) return har_set_error("null input / output arrays");
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            const size_t i1 = n + (size_t) i, i2 = 2 * (size_t) n + i;
+            float dg[2] = { 0.f, 0.f }, f = 0.f;
+            BsdfSide side;
+            if (bsdf_side(S, bsdf, Vec3(wi[i], wi[i1], wi[i2]), side)) {
+                const DBsdf &R = S.bsdfs[side.index];
+                BumpGeom G = bump_geom_rows(S, R, n, i, geom, uv[i], uv[i1]);
+                if (grad_uv) { G.gx = grad_uv[i]; G.gy = grad_uv[i1]; }
+                f = bumpmap_weighted_value_grad(S, R, G, G.gx, G.gy, side.wi, Vec3(wo[i], wo[i1], wo[i2] * side.wo_sign), uv[i], uv[i1], Vec3(A[i], A[i1], A[i2]), dg);
+            }
+            if (value) value[i] = f;
+            grad[i] = dg[0]; grad[i1] = dg[1];
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bumpmap_grad_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bumpmap_grad_host: ") + ex.what()); }
+}
+
 /* The lookup of a `mesh_attribute` record and its transpose on the host, by the functions the kernels run (attr_addr, attr_taps, attr_fetch, tap_weights): n hits on the
  * record's mesh, face `prim[i]` at point p (3 x n).  value (3 x n, may be NULL) = the looked-up colour; with g (3 x n) and grad (rows x 3, ACCUMULATED into) the deposit of
  * the in-place commit: grad[row_k] += g * b_k * scale for the three rows of the lookup (a face attribute: its row, weight scale) */
@@ -407,6 +514,7 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
         B.bind();
         if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
         if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+        if (B.hs.bsdfs[bsdf].type == BSDF_BUMPMAP) return har_set_error("bumpmap: BSDF::eval / pdf / sample of a `bumpmap` record read si.n, si.sh_frame, si.dp_du and si.dp_dv: use har_bsdf_eval_pdf_si_host / har_bsdf_sample_si_host");
         BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
         if (n == 0) return 0;
         if (!wi || !uv || !wo) return har_set_error("null input arrays");
@@ -416,7 +524,7 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             if (value) { value[i] = ev.value.x; value[n + i] = ev.value.y; value[2 * (size_t) n + i] = ev.value.z; }
             if (pdf) pdf[i] = ev.pdf;
@@ -434,6 +542,7 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
         B.bind();
         if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
         if (B.ds.bsdf_types & HAR_SCENE_ATTR) return har_set_error("mesh_attribute: BSDF::eval / pdf / sample see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+        if (B.hs.bsdfs[bsdf].type == BSDF_BUMPMAP) return har_set_error("bumpmap: BSDF::eval / pdf / sample of a `bumpmap` record read si.n, si.sh_frame, si.dp_du and si.dp_dv: use har_bsdf_eval_pdf_si_host / har_bsdf_sample_si_host");
         BsdfCtx c; if (!lower_ctx_host(ctx, c)) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)");
         if (n == 0) return 0;
         if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return har_set_error("null input / output arrays");
@@ -443,7 +552,7 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
             weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;

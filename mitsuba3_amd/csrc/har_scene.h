@@ -397,6 +397,43 @@ HAR_HD Vec3 tex_fetch(const DTexture &T, const TexTaps &l) {
     }
     return Vec3(out[0], out[1], out[2]);
 }
+/* BitmapTexture::eval_1_grad (bitmap.cpp:543-599), in its order of operations: uv' = to_uv * uv, the four texels of eval_fetch (the taps of tex_taps: f00, f10, f01, f11),
+ * each reduced to one number -- the channel of a one-channel bitmap (`mono`: stored three times, channel 0 is read), luminance() of a three-channel texel --,
+ * df_x = fmadd(w0.y, f10 - f00, w1.y * (f11 - f01)), df_y = fmadd(w0.x, f01 - f00, w1.x * (f11 - f10)), then the TRANSPOSE of to_uv's 2 x 2 block and the resolution
+ * (w, h), component by component.  A nearest-filtered bitmap returns (0, 0) (:558-560).  One difference in rounding: the reference writes each row of the transposed
+ * product as two multiplies and an add (:594-597); here it is fmadd(m0, df_x, m1 * df_y), one rounding less -- inside every bar (docs/parity.md). */
+HAR_HD float tex_value_1(const DTexture &T, uint32_t idx, bool mono) {
+    const float *p = T.data + 3 * (size_t) idx;
+    return mono ? p[0] : p[0] * 0.212671f + p[1] * 0.715160f + p[2] * 0.072169f;           /* luminance(), spectrum.h:439-442 */
+}
+HAR_HD void tex_eval_1_grad(const DTexture &T, bool mono, float u, float v, float &gu, float &gv) {
+    gu = 0.f; gv = 0.f;
+    if (T.mode & 1u) return;
+    TexTaps l; tex_taps(T, u, v, l);
+    const float f00 = tex_value_1(T, l.idx[0], mono), f10 = tex_value_1(T, l.idx[1], mono), f01 = tex_value_1(T, l.idx[2], mono), f11 = tex_value_1(T, l.idx[3], mono);
+    const float dfx = fma_(l.w0y, f10 - f00, l.w1y * (f11 - f01)), dfy = fma_(l.w0x, f01 - f00, l.w1x * (f11 - f10));
+    const bool xf = (T.mode & HAR_TEX_HAS_UV_XF) != 0u;
+    const float m00 = xf ? T.uvm[0] : 1.f, m01 = xf ? T.uvm[1] : 0.f, m10 = xf ? T.uvm[3] : 0.f, m11 = xf ? T.uvm[4] : 1.f;
+    gu = (float) T.w * fma_(m00, dfx, m10 * dfy);
+    gv = (float) T.h * fma_(m01, dfx, m11 * dfy);
+}
+/* ... and its transpose: eval_1_grad is linear in the texels, so for an adjoint (gu, gv) of the gradient the deposit into tap k (texel l.idx[k]) is
+ * w[k] = `scale` * (ax * d df_x / d f_k + ay * d df_y / d f_k), (ax, ay) = the adjoint pushed through the same matrix and the resolution,
+ * d df_x / d f = (-w0.y, +w0.y, -w1.y, +w1.y), d df_y / d f = (-w0.x, -w1.x, +w0.x, +w1.x) over (f00, f10, f01, f11).  A three-channel map multiplies w[k] by the luminance
+ * coefficient of the channel; a one-channel map receives it in channel 0 (tex_eval_1_grad_channels).  A nearest map: zero weights. */
+HAR_HD void tex_eval_1_grad_transpose(const DTexture &T, float u, float v, float gu, float gv, float scale, TexTaps &l, float w[4]) {
+    tex_taps(T, u, v, l);
+    w[0] = w[1] = w[2] = w[3] = 0.f;
+    if (T.mode & 1u) return;
+    const bool xf = (T.mode & HAR_TEX_HAS_UV_XF) != 0u;
+    const float m00 = xf ? T.uvm[0] : 1.f, m01 = xf ? T.uvm[1] : 0.f, m10 = xf ? T.uvm[3] : 0.f, m11 = xf ? T.uvm[4] : 1.f;
+    const float hu = (float) T.w * gu, hv = (float) T.h * gv;
+    const float ax = scale * fma_(m00, hu, m01 * hv), ay = scale * fma_(m10, hu, m11 * hv);
+    w[0] = fma_(-l.w0y, ax, -l.w0x * ay); w[1] = fma_(l.w0y, ax, -l.w1x * ay);
+    w[2] = fma_(-l.w1y, ax, l.w0x * ay);  w[3] = fma_(l.w1y, ax, l.w1x * ay);
+}
+HAR_HD Vec3 tex_eval_1_grad_channels(bool mono) { return mono ? Vec3(1.f, 0.f, 0.f) : Vec3(0.212671f, 0.715160f, 0.072169f); }
+
 /* ---- the `mesh_attribute` texture (src/textures/mesh_attribute.cpp -> Mesh::eval_attribute*, src/render/mesh.cpp:2464-2631).  Where a hit looks an attribute up:
  * `face` = the face's index in DScene::faces (the mesh's first face + si.prim_index), (b1, b2) = Mesh::barycentric_coordinates(si) (mesh.cpp:2227-2251): the
  * least-squares solve of si.p against the face's vertex positions, NOT the hit's prim_uv.  Filled by attr_addr in the kernels of scenes with such a texture only. */
@@ -660,11 +697,10 @@ HAR_HD float normalmap_shadow_terminator(Vec3 perturbed_n, Vec3 wo) {
 /* eval / pdf / eval_pdf (:163-219): the nested BSDF at wi' = frame.to_local(wi), wo' = frame.to_local(wo); zero unless cos_theta(wo) * cos_theta(wo') > 0; the value -- not
  * the pdf -- times the shadow terminator of (frame.n, wo).  d_slot0 stays zero (the record's slot 0 is the normal map: its derivative is not a per-channel scale; it
  * comes from normalmap_weighted_value_grad, har_normalmap_grad.h); cg->d[0] = d value / d (slot 0 of the nested LEAF). */
+/* (the part behind the frame, shared with the bumpmap record: both hand it their NormalFrame) */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void normalmap_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+HAR_HD void perturbed_eval_pdf(const DScene &S, const DBsdf &B, const NormalFrame &F, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_RECORD_BITS;
-    e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f);
-    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
     const Vec3 pwi = F.to_local(wi), pwo = F.to_local(wo);
     if (!(wo.z * pwo.z > 0.f)) return;
     BsdfSide ns;
@@ -677,13 +713,17 @@ HAR_HD void normalmap_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs
     e.pdf = ne.pdf;
     if (cg) cg->d[0] = ne.d_slot0 * shadow;          /* d value / d (slot 0 of the nested LEAF): the leaf receives shadow * d_slot0(nested at wi', wo') */
 }
+template <uint32_t TYPES, bool CTX>
+HAR_HD void normalmap_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+    e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f);
+    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
+    perturbed_eval_pdf<TYPES, CTX>(S, B, F, wi, wo, u, v, e, ctx, cg);
+}
 /* sample (:134-160): the nested sample at wi'; nothing when its weight is zero; wo = frame.to_world(wo') -- back in the UNPERTURBED frame --, pdf and weight zero unless
  * cos_theta(wo') * cos_theta(wo) > 0 (wo, eta, sampled_type and sampled_component stay what the nested BSDF returned), the weight times the shadow terminator */
 template <uint32_t TYPES, bool CTX>
-HAR_HD void normalmap_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+HAR_HD void perturbed_sample(const DScene &S, const DBsdf &B, const NormalFrame &F, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_RECORD_BITS;
-    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
-    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
     const Vec3 pwi = F.to_local(wi);
     BsdfSide ns;
     if (!bsdf_side(S, B.pad, pwi, ns)) return;
@@ -698,11 +738,64 @@ HAR_HD void normalmap_sample(const DScene &S, const DBsdf &B, const BsdfInputs &
     if (!active) { bs.pdf = 0.f; bs.weight = Vec3(0.f); return; }
     if (B.flags & BF_NM_SHADOW) bs.weight = bs.weight * normalmap_shadow_terminator(F.n, wo);
 }
+template <uint32_t TYPES, bool CTX>
+HAR_HD void normalmap_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
+    const NormalFrame F = normalmap_frame(B, in.slot0, wi);
+    perturbed_sample<TYPES, CTX>(S, B, F, wi, u, v, s1, s2x, s2y, bs, ctx);
+}
+
+/* ---- BumpMap (src/bsdfs/bumpmap.cpp), record type 9: DBsdf::texture is the height bitmap (Texture::eval_1_grad: one channel -- BF_MONO -- or the luminance of three),
+ * DBsdf::alpha_u holds `scale`, DBsdf::pad names the nested record (a leaf model that may carry the twosided flag), BF_NM_FLIP / BF_NM_SHADOW are the two switches.
+ * Components and flags are the nested BSDF's (:124-128: no BSDFFlags::NormalMapped, so the shape's frame stays what it is).  Only the kernels of scenes that hold such a
+ * record carry this code (TYPES & HAR_SCENE_BUMPMAP).  The frame needs more of the interaction than wi and uv: BumpGeom, filled for vertices on a bumpmap record only.
+ * frame() (:224-253), line for line:
+ *   grad_uv = scale * eval_1_grad;  dp_du' = fmadd(sh_n, grad_uv.x - dot(sh_n, dp_du), dp_du), likewise dp_dv';  n = normalize(cross(dp_du', dp_dv'));
+ *   n = -n where dot(si.n, n) < 0;  n = si.to_local(n);  with flip_invalid_normals n <- (-n.x, -n.y, n.z) where cos_theta(wi) * dot(wi, n) <= 0;
+ *   s = normalize(fnmadd(n, dot(n, si.dp_du), si.dp_du));  t = cross(n, s).
+ * The `s` line dots the LOCAL n with the WORLD-space dp_du and subtracts a local vector from a world one -- that is what the reference computes (:249), and parity is
+ * with the reference, so it is implemented literally (docs/parity.md). */
+struct BumpGeom { Vec3 n, sn, ss, st, dp_du, dp_dv; float gx, gy; /* grad_uv = scale * eval_1_grad at the vertex's uv */ };
+HAR_HD NormalFrame bumpmap_frame_grad(const DBsdf &B, const BumpGeom &G, float gx, float gy, Vec3 wi) {
+    const Vec3 dpu = fma3(G.sn, gx - dot3(G.sn, G.dp_du), G.dp_du), dpv = fma3(G.sn, gy - dot3(G.sn, G.dp_dv), G.dp_dv);
+    Vec3 n = normalize3(cross3(dpu, dpv));
+    if (dot3(G.n, n) < 0.f) n = -n;
+    n = Vec3(dot3(n, G.ss), dot3(n, G.st), dot3(n, G.sn));
+    if ((B.flags & BF_NM_FLIP) && wi.z * dot3(wi, n) <= 0.f) n = Vec3(-n.x, -n.y, n.z);
+    NormalFrame F;
+    F.n = n;
+    F.s = normalize3(fma3(n, -dot3(n, G.dp_du), G.dp_du));
+    F.t = cross3(F.n, F.s);
+    return F;
+}
+HAR_HD NormalFrame bumpmap_frame(const DBsdf &B, const BumpGeom &G, Vec3 wi) { return bumpmap_frame_grad(B, G, G.gx, G.gy, wi); }
+/* the interaction fields frame() reads, and the height gradient at (u, v) */
+HAR_HD BumpGeom bump_geom(const DScene &S, const DBsdf &B, Vec3 n, Vec3 sn, Vec3 ss, Vec3 st, Vec3 dp_du, Vec3 dp_dv, float u, float v) {
+    BumpGeom G; G.n = n; G.sn = sn; G.ss = ss; G.st = st; G.dp_du = dp_du; G.dp_dv = dp_dv;
+    float gx, gy; tex_eval_1_grad(S.textures[B.texture], (B.flags & BF_MONO) != 0u, u, v, gx, gy);
+    G.gx = B.alpha_u * gx; G.gy = B.alpha_u * gy;
+    return G;
+}
+/* eval / pdf / eval_pdf / sample (:137-222) behind the frame are the normalmap's code */
+template <uint32_t TYPES, bool CTX>
+HAR_HD void bumpmap_eval_pdf(const DScene &S, const DBsdf &B, const BumpGeom *G, Vec3 wi, Vec3 wo, float u, float v, BsdfEval &e, const BsdfCtx &ctx, BlendChildGrad *cg = nullptr) {
+    e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f);
+    if (!G) return;
+    const NormalFrame F = bumpmap_frame(B, *G, wi);
+    perturbed_eval_pdf<TYPES, CTX>(S, B, F, wi, wo, u, v, e, ctx, cg);
+}
+template <uint32_t TYPES, bool CTX>
+HAR_HD void bumpmap_sample(const DScene &S, const DBsdf &B, const BumpGeom *G, Vec3 wi, float u, float v, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx) {
+    bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
+    if (!G) return;
+    const NormalFrame F = bumpmap_frame(B, *G, wi);
+    perturbed_sample<TYPES, CTX>(S, B, F, wi, u, v, s1, s2x, s2y, bs, ctx);
+}
 
 /* (u, v): the vertex's texture coordinates -- read only by the kernels of blend / mask scenes, whose nested records look up their own colour inputs there */
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEval &e, const BsdfCtx &ctx = BsdfCtx(), float u = 0.f, float v = 0.f,
-                          BlendChildGrad *cg = nullptr, const AttrAddr *aa = nullptr) {
+                          BlendChildGrad *cg = nullptr, const AttrAddr *aa = nullptr, const BumpGeom *bg = nullptr /* kernels of bump scenes: the interaction of a vertex on a bumpmap record */) {
     if (!side_ok) { e.value = Vec3(0.f); e.pdf = 0.f; e.d_slot0 = Vec3(0.f); e.d_slot1 = Vec3(0.f); if ((TYPES & HAR_SCENE_BLEND) != 0u && cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); } return; }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) {
         blend_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg, aa);
@@ -717,6 +810,10 @@ HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInput
         normalmap_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
         return;
     }
+    if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && S.bsdfs[side.index].type == BSDF_BUMPMAP) {
+        bumpmap_eval_pdf<TYPES, CTX>(S, S.bsdfs[side.index], bg, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), u, v, e, ctx, cg);
+        return;
+    }
     bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_RECORD_BITS), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
 }
 /* d value / d {alpha, eta, k} of the record serving this side (see bsdf_eval_extra_one) */
@@ -726,13 +823,55 @@ HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInp
 }
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx = BsdfCtx(),
-                        float u = 0.f, float v = 0.f, const AttrAddr *aa = nullptr) {
+                        float u = 0.f, float v = 0.f, const AttrAddr *aa = nullptr, const BumpGeom *bg = nullptr) {
     if (!side_ok) { bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u; return; }
     if ((TYPES & HAR_SCENE_BLEND) != 0u && S.bsdfs[side.index].type == BSDF_BLEND) blend_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
     else if ((TYPES & HAR_SCENE_MASK) != 0u && S.bsdfs[side.index].type == BSDF_MASK) mask_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx, aa);
     else if ((TYPES & HAR_SCENE_NORMALMAP) != 0u && S.bsdfs[side.index].type == BSDF_NORMALMAP) normalmap_sample<TYPES, CTX>(S, S.bsdfs[side.index], in, side.wi, u, v, s1, s2x, s2y, bs, ctx);
+    else if ((TYPES & HAR_SCENE_BUMPMAP) != 0u && S.bsdfs[side.index].type == BSDF_BUMPMAP) bumpmap_sample<TYPES, CTX>(S, S.bsdfs[side.index], bg, side.wi, u, v, s1, s2x, s2y, bs, ctx);
     else bsdf_sample_one<(TYPES & ~HAR_SCENE_RECORD_BITS), CTX>(S.bsdfs[side.index], in, side.wi, s1, s2x, s2y, bs, ctx);
     bs.wo.z *= side.wo_sign;
+}
+
+/* One lane of the array-valued BSDF::eval_pdf / sample that carry the interaction (har_bsdf_eval_pdf_si / har_bsdf_sample_si, their kernels and host twins): `geom` is
+ * 18 x n -- si.n, sh_frame.n, sh_frame.s, sh_frame.t, dp_du, dp_dv, three rows each --, read for a bumpmap record (an outer `twosided` folds wi in front of the frame);
+ * every other record is evaluated as by har_bsdf_eval_pdf / har_bsdf_sample */
+HAR_HD BumpGeom bump_geom_rows(const DScene &S, const DBsdf &B, uint32_t n, uint32_t i, const float *geom, float u, float v) {
+    Vec3 r[6];
+    for (int k = 0; k < 6; ++k) r[k] = Vec3(geom[(3 * k) * (size_t) n + i], geom[(3 * k + 1) * (size_t) n + i], geom[(3 * k + 2) * (size_t) n + i]);
+    return bump_geom(S, B, r[0], r[1], r[2], r[3], r[4], r[5], u, v);
+}
+HAR_HD void bsdf_eval_pdf_si_lane(const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, uint32_t i, const float *wi, const float *uv, const float *wo, const float *geom,
+                                  bool active, float *value, float *pdf) {
+    BsdfEval e; e.value = Vec3(0.f); e.pdf = 0.f;
+    if (active) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        const DBsdf &B = S.bsdfs[side.index];
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, B, uv[i], uv[n + i], taps);
+        BumpGeom G; const bool bump = B.type == BSDF_BUMPMAP;
+        if (bump) G = bump_geom_rows(S, B, n, i, geom, uv[i], uv[n + i]);
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i],
+                                                                          nullptr, nullptr, bump ? &G : nullptr);
+    }
+    if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
+    if (pdf) pdf[i] = e.pdf;
+}
+HAR_HD void bsdf_sample_si_lane(const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, uint32_t i, const float *wi, const float *uv, const float *s1, const float *s2,
+                                const float *geom, bool active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
+    if (active) {
+        BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
+        const DBsdf &B = S.bsdfs[side.index];
+        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, B, uv[i], uv[n + i], taps);
+        BumpGeom G; const bool bump = B.type == BSDF_BUMPMAP;
+        if (bump) G = bump_geom_rows(S, B, n, i, geom, uv[i], uv[n + i]);
+        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i], nullptr, bump ? &G : nullptr);
+    }
+    wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
+    weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
+    if (eta) eta[i] = b.eta;
+    if (stype) stype[i] = b.type;
+    if (scomp) scomp[i] = b.comp;
 }
 
 /* SmoothDiffuse::eval_pdf / sample (src/bsdfs/diffuse.cpp:159-179, 100-124) */

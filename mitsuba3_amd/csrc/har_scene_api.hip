@@ -40,7 +40,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
             const DBsdf &b = hs.bsdfs[k];
             uint32_t c = std::min<uint32_t>(b.type, BSDF_TYPE_COUNT - 1u);
             if ((b.flags & BF_TWOSIDED) && b.back >= 0 && hs.bsdfs[(size_t) b.back].type != b.type) c = HAR_MAT_GENERIC;
-            if (b.type == BSDF_BLEND || b.type == BSDF_MASK || b.type == BSDF_NORMALMAP) c = HAR_MAT_GENERIC;      /* two models at one vertex / a nested model and a null lobe: the generic bucket of the block-local sort */
+            if (b.type == BSDF_BLEND || b.type == BSDF_MASK || b.type == BSDF_NORMALMAP || b.type == BSDF_BUMPMAP) c = HAR_MAT_GENERIC;      /* two models at one vertex / a nested model and a null lobe: the generic bucket of the block-local sort */
             cls[k] = c;
         }
         for (DMesh &m : hs.meshes) { m.pad1 = m.bsdf < cls.size() ? cls[m.bsdf] : 0u; S->mat_classes |= 1u << m.pad1; }
@@ -83,7 +83,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
     D.n_emitters = (uint32_t) hs.emitters.size(); D.n_meshes = (uint32_t) hs.meshes.size();
     D.n_bsdfs = (uint32_t) hs.bsdfs.size(); D.n_insts = (uint32_t) hs.insts.size(); D.n_textures = (uint32_t) hs.textures.size();
     D.env_emitter = hs.env_emitter;
-    D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+    D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
     if (hs.has_envmap || hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) D.bsdf_types |= HAR_SCENE_ENVMAP;
     for (const DEmitter &e : hs.emitters) if (e.type == 7u) D.bsdf_types |= HAR_SCENE_TEXLIGHT;      /* (has_mesh_emitters is set with it: the generic emitter kernels + the texel-distribution code) */
     for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) D.bsdf_types |= HAR_SCENE_ATTR;      /* a `mesh_attribute` texture: the widest set that also looks attributes up */
@@ -765,10 +765,13 @@ static int lower_ctx(const HarBSDFContext *ctx, BsdfCtx &out) {
     out.mode = ctx->mode; out.type_mask = ctx->type_mask; out.component = ctx->component;
     return 0;
 }
+/* is record `bsdf` a bumpmap (possibly under an outer one-BSDF `twosided`, which is a flag of the same record)?  Such a record needs the entries that carry the interaction */
+static bool bsdf_reaches_bumpmap(HarScene S, uint32_t bsdf) { return S->hs.bsdfs[bsdf].type == BSDF_BUMPMAP; }
 static int bsdf_eval_common(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                             float *value, float *pdf, void *stream) {
     if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
     if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::eval / pdf see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+    if (bsdf_reaches_bumpmap(S, bsdf)) return fail("bumpmap: BSDF::eval / pdf of a `bumpmap` record read si.n, si.sh_frame, si.dp_du and si.dp_dv: use har_bsdf_eval_pdf_si");
     BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
     if (n == 0) return 0;
     if (!wi || !uv || !wo) return fail("null wi / uv / wo");
@@ -793,10 +796,34 @@ int har_bsdf_sample(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32
                     const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component, void *stream) {
     if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
     if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::sample sees a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+    if (bsdf_reaches_bumpmap(S, bsdf)) return fail("bumpmap: BSDF::sample of a `bumpmap` record reads si.n, si.sh_frame, si.dp_du and si.dp_dv: use har_bsdf_sample_si");
     BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
     if (n == 0) return 0;
     if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return fail("null input / output arrays");
     launch_api_bsdf_sample((hipStream_t) stream, S->ds, bsdf, c, n, wi, uv, sample1, sample2, active, wo, pdf, weight, eta, sampled_type, sampled_component);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int har_bsdf_eval_pdf_si(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom,
+                         const uint8_t *active, float *value, float *pdf, void *stream) {
+    if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
+    if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::eval / pdf see a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+    if (!value && !pdf) return fail("null value / pdf");
+    BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
+    if (n == 0) return 0;
+    if (!wi || !uv || !wo || !geom) return fail("null wi / uv / wo / geom");
+    launch_api_bsdf_eval_pdf_si((hipStream_t) stream, S->ds, bsdf, c, n, wi, uv, wo, geom, active, value, pdf);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int har_bsdf_sample_si(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1, const float *sample2, const float *geom,
+                       const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component, void *stream) {
+    if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
+    if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("mesh_attribute: BSDF::sample sees a uv, not the shape that was hit; not available for a scene with a `mesh_attribute` texture");
+    BsdfCtx c; if (lower_ctx(ctx, c)) return 1;
+    if (n == 0) return 0;
+    if (!wi || !uv || !sample2 || !geom || !wo || !pdf || !weight) return fail("null input / output arrays");
+    launch_api_bsdf_sample_si((hipStream_t) stream, S->ds, bsdf, c, n, wi, uv, sample1, sample2, geom, active, wo, pdf, weight, eta, sampled_type, sampled_component);
     HIP_TRY(hipGetLastError());
     return 0;
 }

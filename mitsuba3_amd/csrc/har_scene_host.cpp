@@ -207,6 +207,11 @@ bool scene_set_bsdf_params_host(HostScene &hs, uint32_t index, const HarBSDF &in
     if (b.type == BSDF_BLEND) { err = "blendbsdf: the record has no parameter besides its weight (slot 0)"; return false; }
     if (b.type == BSDF_MASK) { err = "mask: the record has no parameter besides its opacity (slot 0)"; return false; }
     if (b.type == BSDF_NORMALMAP) { err = "normalmap: the record has no parameter besides its normal map (slot 0)"; return false; }
+    if (b.type == BSDF_BUMPMAP) {          /* BumpMap::traverse (bumpmap.cpp:131-135): `scale`, which the record keeps in alpha_u */
+        if (!std::isfinite(in.alpha_u)) { err = "bumpmap: `scale` is not finite"; return false; }
+        b.alpha_u = in.alpha_u;
+        return true;
+    }
     for (float v : { in.alpha_u, in.alpha_v, in.eta, in.eta_c[0], in.eta_c[1], in.eta_c[2], in.k_c[0], in.k_c[1], in.k_c[2], in.reflectance2[0], in.reflectance2[1], in.reflectance2[2] })
         if (!std::isfinite(v)) { err = "BSDF parameter is not finite"; return false; }
     const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
@@ -305,7 +310,7 @@ static bool build_envmap(HostScene &hs, const HarTexture &img, const HarEmitter 
 
 /* the two mesh bits of the public header are the ones the kernels test (har_scene.h) */
 static_assert((uint32_t) MESH_TANGENT_FRAME == HAR_MESH_TANGENT_FRAME && (uint32_t) MESH_FRAME_FLIPPED == HAR_MESH_FRAME_FLIPPED, "HarMesh::flags and DMesh::flags disagree");
-static_assert((uint32_t) BF_NM_FLIP == HAR_BSDF_NM_FLIP && (uint32_t) BF_NM_SHADOW == HAR_BSDF_NM_SHADOW && (uint32_t) BSDF_NORMALMAP == HAR_BSDF_NORMALMAP, "HarBSDF and DBsdf disagree");
+static_assert((uint32_t) BF_NM_FLIP == HAR_BSDF_NM_FLIP && (uint32_t) BF_NM_SHADOW == HAR_BSDF_NM_SHADOW && (uint32_t) BSDF_NORMALMAP == HAR_BSDF_NORMALMAP && (uint32_t) BSDF_BUMPMAP == HAR_BSDF_BUMPMAP, "HarBSDF and DBsdf disagree");
 
 bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     if (d.top_mesh_count > d.mesh_count) { err = "top_mesh_count exceeds mesh_count"; return false; }
@@ -360,13 +365,15 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.bsdf_count; ++i) {
         const HarBSDF &b = d.bsdfs[i];
-        if (b.type > BSDF_NORMALMAP) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask, normalmap and twosided are implemented in hip_ad_rgb)"; return false; }
+        if (b.type > BSDF_BUMPMAP) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask, normalmap, bumpmap and twosided are implemented in hip_ad_rgb)"; return false; }
         if (b.texture >= (int32_t) d.texture_count) { err = "BSDF references a texture that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
         /* ... and BSDFFlags::Null is part of BSDFFlags::Transmission: `twosided` over a `mask`, on either side */
         if ((b.flags & BF_TWOSIDED) && (b.type == BSDF_MASK || (b.back >= 0 && d.bsdfs[b.back].type == BSDF_MASK))) { err = "twosided over `mask`: Only materials without a transmission component can be nested!"; return false; }
         /* `twosided` over a `normalmap`: the one-BSDF form, twosided(normalmap(X)); a pair with a normalmap on either side is not supported */
         if ((b.flags & BF_TWOSIDED) && b.back >= 0 && (b.type == BSDF_NORMALMAP || d.bsdfs[b.back].type == BSDF_NORMALMAP)) { err = "twosided over `normalmap`: the two-BSDF form is not supported (nest ONE normalmap: twosided(normalmap(X)))"; return false; }
+        /* ... and over a `bumpmap`, likewise */
+        if ((b.flags & BF_TWOSIDED) && b.back >= 0 && (b.type == BSDF_BUMPMAP || d.bsdfs[b.back].type == BSDF_BUMPMAP)) { err = "twosided over `bumpmap`: the two-BSDF form is not supported (nest ONE bumpmap: twosided(bumpmap(X)))"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
         if ((b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC) && !(b.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
         if (b.type == BSDF_ROUGHPLASTIC && b.eta == 1.f) { err = "The interior and exterior indices of refraction must be positive and differ!"; return false; }
@@ -384,6 +391,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 const HarBSDF &c = d.bsdfs[b.nested[k]];
                 if (c.type == BSDF_MASK) { err = "blendbsdf: a nested `mask` BSDF is not supported (put the `mask` outside, over plain BSDF models)"; return false; }
                 if (c.type == BSDF_NORMALMAP) { err = "blendbsdf: a nested `normalmap` BSDF is not supported (nested BSDFs are plain BSDF models)"; return false; }
+                if (c.type == BSDF_BUMPMAP) { err = "blendbsdf: a nested `bumpmap` BSDF is not supported (nested BSDFs are plain BSDF models)"; return false; }
                 if (c.type >= BSDF_TYPE_COUNT || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
                 if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
                 if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_BLEND_SMOOTH;
@@ -396,6 +404,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             if (c.type == BSDF_BLEND) { err = "mask: unsupported BSDF type of the nested record: a nested `blendbsdf` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type == BSDF_MASK) { err = "mask: unsupported BSDF type of the nested record: a nested `mask` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type == BSDF_NORMALMAP) { err = "mask: unsupported BSDF type of the nested record: a nested `normalmap` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
+            if (c.type == BSDF_BUMPMAP) { err = "mask: unsupported BSDF type of the nested record: a nested `bumpmap` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type >= BSDF_TYPE_COUNT) { err = "mask: unsupported BSDF type of the nested record"; return false; }
             if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
             if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
@@ -411,8 +420,8 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             db.flags &= BF_TWOSIDED | BF_NM_FLIP | BF_NM_SHADOW;
             if (b.nested[0] < 0 || b.nested[0] >= (int32_t) d.bsdf_count) { err = "normalmap: the nested BSDF index is out of range"; return false; }
             const HarBSDF &c = d.bsdfs[b.nested[0]];
-            if (c.type == BSDF_BLEND || c.type == BSDF_MASK || c.type == BSDF_NORMALMAP) {
-                err = std::string("normalmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
+            if (c.type == BSDF_BLEND || c.type == BSDF_MASK || c.type == BSDF_NORMALMAP || c.type == BSDF_BUMPMAP) {
+                err = std::string("normalmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : c.type == BSDF_BUMPMAP ? "bumpmap" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
                 return false;
             }
             if (c.type >= BSDF_TYPE_COUNT) { err = "normalmap: unsupported BSDF type of the nested record"; return false; }
@@ -422,6 +431,27 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 if (c.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
                 const HarBSDF &k = d.bsdfs[c.back];
                 if (k.type >= BSDF_TYPE_COUNT) { err = "normalmap: the back side of a nested `twosided` must be a plain BSDF model (a `blendbsdf`, `mask` or `normalmap` there is not supported)"; return false; }
+                if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
+            }
+            db.pad = (uint32_t) b.nested[0];
+        } else if (b.type == BSDF_BUMPMAP) {                /* BumpMap (bumpmap.cpp:102-129): the height bitmap, one nested record named by index (it may be a `twosided`), `scale` in alpha_u */
+            if (b.texture < 0) { err = "bumpmap: the nested texture must be a `bitmap` (a constant has no eval_1_grad: Texture::eval_1_grad is not implemented for it)"; return false; }
+            if (d.textures[b.texture].mode & HAR_TEX_MESH_ATTRIBUTE) { err = "bumpmap: a `mesh_attribute` texture as the height map is not supported (eval_1_grad of a bitmap is)"; return false; }
+            if (!std::isfinite(b.alpha_u)) { err = "bumpmap: `scale` is not finite"; return false; }
+            db.flags &= BF_TWOSIDED | BF_MONO | BF_NM_FLIP | BF_NM_SHADOW;
+            if (b.nested[0] < 0 || b.nested[0] >= (int32_t) d.bsdf_count) { err = "bumpmap: the nested BSDF index is out of range"; return false; }
+            const HarBSDF &c = d.bsdfs[b.nested[0]];
+            if (c.type == BSDF_BLEND || c.type == BSDF_MASK || c.type == BSDF_NORMALMAP || c.type == BSDF_BUMPMAP) {
+                err = std::string("bumpmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : c.type == BSDF_BUMPMAP ? "bumpmap" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
+                return false;
+            }
+            if (c.type >= BSDF_TYPE_COUNT) { err = "bumpmap: unsupported BSDF type of the nested record"; return false; }
+            if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
+            if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
+            if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
+                if (c.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
+                const HarBSDF &k = d.bsdfs[c.back];
+                if (k.type >= BSDF_TYPE_COUNT) { err = "bumpmap: the back side of a nested `twosided` must be a plain BSDF model (a `blendbsdf`, `mask`, `normalmap` or `bumpmap` there is not supported)"; return false; }
                 if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
             }
             db.pad = (uint32_t) b.nested[0];
@@ -442,6 +472,9 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     {
         bool any = false; for (const DBsdf &b : hs.bsdfs) any = any || b.type == BSDF_NORMALMAP;
         if (any) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "normalmap: a scene with a `normalmap` BSDF and a `mesh_attribute` texture is not supported"; return false; }
+        /* a `bumpmap` record sets no BSDFFlags::NormalMapped (bumpmap.cpp:124-128): the meshes under it keep the frame they have, with or without normals and texcoords */
+        bool any_bump = false; for (const DBsdf &b : hs.bsdfs) any_bump = any_bump || b.type == BSDF_BUMPMAP;
+        if (any_bump) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "bumpmap: a scene with a `bumpmap` BSDF and a `mesh_attribute` texture is not supported"; return false; }
         for (uint32_t m = 0; m < d.mesh_count; ++m) {
             DMesh &dm = hs.meshes[m];
             const bool under = hs.bsdfs[dm.bsdf].type == BSDF_NORMALMAP;
