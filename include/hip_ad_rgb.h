@@ -660,6 +660,14 @@ int har_integrator_set_grad_bsdf_params(HarIntegrator integrator, float *grad);
  * into the light's bitmap's entry of `grad_textures` (which har_render_backward takes for every texture of the scene).  0 switches it off (default).  Needs the replay cache
  * (default) and max_depth <= 12; not combined with vertex-position gradients; reverse mode only. */
 int har_integrator_set_grad_light_texels(HarIntegrator integrator, int on);
+/* `prb`: gradients w.r.t. the TEXELS of the environment map (src/emitters/envmap.cpp:203-208: `data` and `scale` are differentiable traverse entries) for the following
+ * har_render_backward calls.  With the sampling density, the MIS weights and mis_compensation detached (prb.py:174-175) the derivative has the two terms of a light's bitmap:
+ * beta * mis at a ray that escapes into the map (envmap.cpp:228-236), beta * mis * f / pdf at a visible emitter sample (:284-323, at the uv after the half-texel shift), both
+ * through the transpose of the map's bilinear lookup (envmap_taps, har_scene.h).  The deposit D is ACCUMULATED into the entry of `grad_textures` of the map's image,
+ * height x width x 3 REAL texels (a halo column's share goes to the edge column it copies), WITHOUT the map's `scale`: d / d data = scale * D, d / d scale = <D, data> --
+ * exact at scale = 0.  0 switches it off (default).  Needs the replay cache (default) and max_depth <= 12; not combined with vertex-position gradients; reverse mode only;
+ * an image the emitter pads (smaller than 2 x 3) is refused. */
+int har_integrator_set_grad_envmap(HarIntegrator integrator, int on);
 /* counters of the last har_render / har_render_backward on this integrator (synchronises) */
 int har_render_stats(HarIntegrator integrator, HarStats *out);
 /* HIP-event timing of the render calls ("frames") issued since har_integrator_set_profiling(.., 1): one event per kernel launch, recorded on
@@ -727,6 +735,11 @@ int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFC
  * at the point p (3 x n).  value (3 x n, may be NULL) = the colour looked up; g (3 x n) with grad (rows x 3, ACCUMULATED into; both or neither) = the deposit of the adjoint:
  * grad[row_k] += g * b_k * scale over the lookup's three rows (a face attribute: its one row).  All pointers HOST. */
 int har_attribute_lookup_host(const HarSceneDesc *desc, uint32_t texture, uint32_t n, const uint32_t *prim, const float *p, float *value, const float *g, float *grad);
+/* The lookup of the scene's environment map and its transpose on the HOST (no GPU), by the per-lane code of the kernels (envmap_taps / envmap_eval_uv): n lookups at uv (2 x n).
+ * idx (4 x n) / weight (4 x n) = the four taps as row-major indices into the height x width REAL texels and their weights; value (3 x n) = scale * sum_k w_k image[idx_k];
+ * eval (3 x n) = envmap_eval_uv; g (3 x n) with grad (height x width x 3, ACCUMULATED into; both or neither) = the deposit of the adjoint, grad[idx_k] += g * w_k (no
+ * `scale`, as har_integrator_set_grad_envmap deposits).  Any output may be NULL.  All pointers HOST. */
+int har_envmap_taps_host(const HarSceneDesc *desc, uint32_t n, const float *uv, uint32_t *idx, float *weight, float *value, float *eval, const float *g, float *grad);
 /* PreliminaryIntersection::compute_surface_interaction on the HOST (no GPU) for n given hits: d = the ray directions (3 x n), t / u / v / prim / shape / inst = the fields
  * of har_ray_intersect_preliminary, `out` = the 33 x n rows of har_compute_surface_interaction.  Every lane runs the per-lane code that entry's kernel runs in a scene with
  * a `normalmap` record (the tangent frame of shapes with HAR_MESH_TANGENT_FRAME in sh_frame.s / .t and wi); for every other shape that is the plain interaction.

@@ -107,6 +107,7 @@ SIGNATURES = {
     "har_integrator_set_grad_emitters": (C.c_int, [vp, vp]),
     "har_integrator_set_grad_bsdf_params": (C.c_int, [vp, vp]),
     "har_integrator_set_grad_light_texels": (C.c_int, [vp, C.c_int]),
+    "har_integrator_set_grad_envmap": (C.c_int, [vp, C.c_int]),
     "har_integrator_set_grad_positions": (C.c_int, [vp, vp, vp]),
     "har_integrator_set_grad_instances": (C.c_int, [vp, vp, vp]),
     "har_integrator_set_hide_emitters": (C.c_int, [vp, C.c_int]),
@@ -162,6 +163,7 @@ SIGNATURES = {
     "har_mesh_load_ply_fields": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp, vp]),
     "har_mesh_fields_free": (None, [vp]),
     "har_attribute_lookup_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, vp, f32p, f32p, f32p, f32p]),
+    "har_envmap_taps_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, f32p, vp, f32p, f32p, f32p, f32p, f32p]),
     "har_mesh_load_serialized_fields": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp, vp]),
     "har_mesh_load_obj": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp]),
     "har_mesh_load_serialized": (C.c_int, [C.c_char_p, C.c_int, C.c_int, f32p, C.c_int, vp]),

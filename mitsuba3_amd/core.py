@@ -1899,7 +1899,7 @@ class Integrator:
     def __init__(self, props):
         self.type = props['type']
         # integrator.cpp:26-33,128-147,539-550; block_size only shapes the scalar / LLVM-parallel drivers; the last four are hip_ad_rgb extensions
-        _check_props(self.type, props, ('max_depth', 'rr_depth', 'hide_emitters', 'samples_per_pass', 'block_size', 'chunk_lanes', 'replay_cache', 'material_queues', 'packet_tracing', 'top_seed', 'emitter_gradients', 'shape_gradients', 'bsdf_parameter_gradients', 'light_texel_gradients'),
+        _check_props(self.type, props, ('max_depth', 'rr_depth', 'hide_emitters', 'samples_per_pass', 'block_size', 'chunk_lanes', 'replay_cache', 'material_queues', 'packet_tracing', 'top_seed', 'emitter_gradients', 'shape_gradients', 'bsdf_parameter_gradients', 'light_texel_gradients', 'envmap_gradients'),
                      unsupported=(('timeout', -1.0),), free_children=False, slot_kind=())
         default_depth = -1 if self.type == 'path' else 6        # integrator.cpp:539, common.py:31
         self.max_depth = int(props.get('max_depth', default_depth))
@@ -1924,6 +1924,10 @@ class Integrator:
         self.bsdf_parameter_gradients = bool(props.get('bsdf_parameter_gradients', False))
         # gradients w.r.t. the texels of a bitmap `radiance` of area lights ('<shape>.emitter.radiance.data'; area.cpp:64-70): har_integrator_set_grad_light_texels
         self.light_texel_gradients = bool(props.get('light_texel_gradients', False))
+        # gradients w.r.t. the texels and the `scale` of an environment map ('<emitter>.data', '<emitter>.scale'; envmap.cpp:203-208): har_integrator_set_grad_envmap
+        if 'envmap_gradients' in props and self.type != 'prb':
+            raise RuntimeError("Unreferenced property \"envmap_gradients\" in plugin of type \"%s\"" % self.type)
+        self.envmap_gradients = bool(props.get('envmap_gradients', False))
         # SamplingIntegrator property (integrator.cpp:140-147); the Python AD integrators do not query it, and an
         # unqueried property is an error in the reference's plugin loader
         self.samples_per_pass = props.get('samples_per_pass', None)
@@ -2090,10 +2094,27 @@ class Integrator:
         check(lib().har_render_weights(C.byref(sensor.har), (sensor.sampler().m_base_seed + int(seed)) & 0xffffffff, spp, lb, le, _ptr(film), _stream()))
         return film
 
+    def _check_envmap_routes(self, scene, envmap_keys):
+        """what har_render_backward refuses for the texel terms of an environment map (they are committed in place by the re-shading replay), said before anything is allocated"""
+        if self.shape_gradients:
+            raise RuntimeError("envmap gradients cannot be combined with vertex-position gradients (`envmap_gradients` with `shape_gradients`)")
+        if not self.replay_cache:
+            raise RuntimeError("envmap gradients need the replay cache (`replay_cache` is off)")
+        if self.max_depth < 0 or self.max_depth > 12:
+            raise RuntimeError("envmap gradients: max_depth must not exceed 12 (the cached bounces)")
+        img = scene.textures[scene.emitters[envmap_keys["env_data"][1]]["mesh"]]
+        if img.shape[0] < 3 or img.shape[1] < 2:
+            raise RuntimeError("envmap gradients: an environment map smaller than 2 x 3 texels (padded by the emitter) is not differentiated")
+
     def render_backward(self, scene, params, grad_in, sensor=0, seed=0, spp=0, lanes=None, weight_film=None):
         """RBIntegrator.render_backward (common.py:625-783): returns {key: gradient tensor}."""
         if self.type != 'prb':
             raise RuntimeError("render_backward(): only the `prb` integrator implements the adjoint pass in hip_ad_rgb")
+        # `envmap_gradients`: the environment map's keys of this scene, {kind: (key, emitter)} -- none: the switch stays off in the library.  What the library would refuse
+        # (har_render_backward: the routes of the texel terms) is said here, before anything is allocated
+        envmap_keys = {kind: (k, i) for k, (kind, i) in scene._pose_keys().items() if kind in ("env_data", "env_scale")} if getattr(self, 'envmap_gradients', False) else {}
+        if envmap_keys:
+            self._check_envmap_routes(scene, envmap_keys)
         torch = _torch(); dev = _device()
         sensor = self._sensor(scene, sensor)
         if spp:
@@ -2165,6 +2186,7 @@ class Integrator:
             check(lib().har_integrator_set_grad_emitters(self._handle(), _ptr(g_emit) if self.emitter_gradients else None))
             check(lib().har_integrator_set_grad_bsdf_params(self._handle(), _ptr(g_extra) if g_extra is not None else None))
             check(lib().har_integrator_set_grad_light_texels(self._handle(), 1 if self.light_texel_gradients else 0))
+            check(lib().har_integrator_set_grad_envmap(self._handle(), 1 if envmap_keys else 0))
             check(lib().har_render_backward(scene._handle(), self._handle(), C.byref(sensor.har), _ptr(grad_in), _ptr(weight_film), sd, spp,
                                             lb, le, _ptr(g_refl), ptrs, _stream()))
         finally:
@@ -2173,6 +2195,7 @@ class Integrator:
             check(lib().har_integrator_set_grad_emitters(self._handle(), None))
             check(lib().har_integrator_set_grad_bsdf_params(self._handle(), None))
             check(lib().har_integrator_set_grad_light_texels(self._handle(), 0))
+            check(lib().har_integrator_set_grad_envmap(self._handle(), 0))
         out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None)
         if g_extra is not None:
             for k, (what, b) in scene._bsdf_param_keys().items():
@@ -2185,6 +2208,8 @@ class Integrator:
             for k, (kind, i) in scene._pose_keys().items():
                 if kind == "emitter_tex":
                     out[k] = g_tex[scene.emitters[i]["light"].tex_index]
+        if envmap_keys:
+            out.update(scene._envmap_gradients(g_tex[scene.emitters[envmap_keys["env_data"][1]]["mesh"]], envmap_keys))
         out.update(g_pos)
         for k, (mi_, pk, keep) in rect_wanted.items():         # d loss / d to_world[r, :] = sum over the vertices of  d loss / d p_v[r] * (local corner of v, 1);  fourth row constant
             rect = scene.meshes[mi_]["rect"]
@@ -3303,7 +3328,8 @@ class Scene:
             elif t in (5, 6):
                 keys[key + ".to_world"] = ("emitter_to_world", i)
             elif t == 2:        # EnvironmentMapEmitter::traverse (envmap.cpp:204-208): `scale`, `to_world` -- updatable here (the record is rebuilt with the next scene handle);
-                                # and so is `data` (differentiable there, without a gradient here)
+                                # and so is `data`; `data` and `scale` are Differentiable: the `prb` integrator's `envmap_gradients` (switched on by mi.render for a key with
+                                # requires_grad) produces their gradients
                 keys[key + ".scale"] = ("env_scale", i); keys[key + ".to_world"] = ("emitter_to_world", i)
                 keys[key + ".data"] = ("env_data", i)          # the texel tensor in the reference's layout: H x (W + 2) x 3, real column x at x + 1 (envmap.cpp:146-188)
             if t == 5:          # SpotLight::traverse (spot.cpp:115-116): the cone, in degrees -- updatable here; their gradient (the reference marks them Differentiable) is refused
@@ -3531,6 +3557,18 @@ class Scene:
             self._drop_handle()
             raise RuntimeError(msg or "emitter update failed")
 
+    def _envmap_gradients(self, D, envmap_keys):
+        """the gradients of an environment map's `data` and `scale` from what the library deposits with har_integrator_set_grad_envmap: D, the adjoint of the map's bilinear
+        lookup over the REAL texels (H x W x 3), without `scale`.  d / d data = scale * D in the parameter's layout H x (W + 2) x 3 with ZERO halo columns (the halo is a copy
+        the emitter refreshes from the real edge columns, envmap.cpp:229-246: what reaches it is folded onto its source column, as the reference's AD-tracked scatter does);
+        d / d scale = <D, data> -- exact at scale = 0.  envmap_keys: {"env_data": (key, emitter), "env_scale": (key, emitter)}"""
+        torch = _torch()
+        key_d, i = envmap_keys["env_data"]; key_s, _ = envmap_keys["env_scale"]
+        data = torch.as_tensor(np.asarray(self.textures[self.emitters[i]["mesh"]], np.float32), device=D.device)
+        g_data = torch.zeros((D.shape[0], D.shape[1] + 2, 3), dtype=torch.float32, device=D.device)
+        g_data[:, 1:-1, :] = D * float(self.emitters[i]["radiance"][0])
+        return {key_d: g_data, key_s: (D.double() * data.double()).sum().to(torch.float32).reshape(1)}
+
     def _gradients(self, g_refl, g_tex, g_emit=None):
         out = {}
         for k, (kind, b) in self._param_keys().items():
@@ -3619,6 +3657,8 @@ class SceneParameters(dict):
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
         if sc._pose_keys().get(key, (None,))[0] == "emitter_tex":
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
+        if sc._pose_keys().get(key, (None,))[0] in ("env_data", "env_scale"):          # envmap.cpp:203-208; `prb` with `envmap_gradients`
+            return ParamFlags.Differentiable
         return ParamFlags.NonDifferentiable
 
     def set_dirty(self, key):
@@ -4038,6 +4078,8 @@ class DeviceGroup:
         integrator's `emitter_gradients` -- emitter-radiance parameters"""
         if self.integrator.type != 'prb':
             raise RuntimeError("render_backward(): only the `prb` integrator implements the adjoint pass in hip_ad_rgb")
+        if getattr(self.integrator, 'envmap_gradients', False):
+            raise RuntimeError("envmap gradients are not produced by DeviceGroup.render_backward() (har_multi_render_backward has no switch for them); use one device")
         torch = _torch()
         s = self.scene.sensors()[sensor] if isinstance(sensor, int) else sensor
         _refuse_batch(s, "DeviceGroup (har_multi_render_backward)")
@@ -4290,7 +4332,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
             raise RuntimeError("scalar_rgb renders are not differentiable (the reference's scalar variants have no AD either); use hip_ad_rgb")
         return _render_scalar(scene, integrator, sensor, seed, spp)
     keys = [k for k, v in (params or {}).items() if getattr(v, 'requires_grad', False)]
-    fixed = [k for k in keys if k in scene._pose_keys() and scene._pose_keys()[k][0] != "emitter_tex"]      # (a light's radiance bitmap IS differentiable: area.cpp:64-70)
+    fixed = [k for k in keys if k in scene._pose_keys() and scene._pose_keys()[k][0] not in ("emitter_tex", "env_data", "env_scale")]      # (a light's radiance bitmap IS differentiable: area.cpp:64-70; an environment map's `data` and `scale`: envmap.cpp:203-208)
     if fixed:       # ParamFlags::NonDifferentiable in the reference's traverse(): dr.enable_grad on them has no effect there; here it is said
         raise RuntimeError("%s are not differentiable parameters in hip_ad_rgb (placement of sensors and delta emitters: ParamFlags::NonDifferentiable in the reference; "
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
@@ -4317,6 +4359,8 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
             overrides['bsdf_parameter_gradients'] = True
         if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator_ad.light_texel_gradients:
             overrides['light_texel_gradients'] = True
+        if any(scene._pose_keys().get(k, (None,))[0] in ("env_data", "env_scale") for k in keys) and not integrator_ad.envmap_gradients:
+            overrides['envmap_gradients'] = True
         if any(v[0] == "emit" for k, v in scene._param_keys().items() if k in keys) and not integrator_ad.emitter_gradients:
             overrides['emitter_gradients'] = True
 
@@ -4342,7 +4386,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
             missing = [k for k in keys if k not in grads]
             if missing:       # e.g. emitter radiance with emitter_gradients=False, vertex positions without shape_gradients
                 raise RuntimeError("mi.render(): the `prb` integrator cannot differentiate %s (integrator properties `emitter_gradients`, "
-                                   "`shape_gradients`, `bsdf_parameter_gradients`, `light_texel_gradients`); differentiable keys of this render: %s" % (missing, sorted(grads)))
+                                   "`shape_gradients`, `bsdf_parameter_gradients`, `light_texel_gradients`, `envmap_gradients`); differentiable keys of this render: %s" % (missing, sorted(grads)))
             return tuple(grads[k].reshape(params[k].shape) for k in keys)
 
     return _RenderOp.apply(*[params[k] for k in keys])

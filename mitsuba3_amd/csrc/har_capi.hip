@@ -682,7 +682,9 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     const bool nmap = (S->ds.bsdf_types & HAR_SCENE_NORMALMAP) != 0u;
     const bool bump = (S->ds.bsdf_types & HAR_SCENE_BUMPMAP) != 0u;          /* ... and a `bumpmap` record: the height map's gradient and the nested colours' likewise */
     const char *const comp = bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
-    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
+    /* ... and the texels of the environment map (har_integrator_set_grad_envmap): the same two terms, the same route */
+    const bool env_texels = I->set.grad_envmap && S->hs.has_envmap;
+    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !env_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
     tape = std::min(tape, I->bw_tape_max);
     /* The tapes are the large workspaces (record tape 69 B, state tape 115 B per lane and bounce against 25 B for the lane-indexed cache: 28 - 90 GB for a 2^26-lane chunk
      * at max_depth 6 - 12).  When the device -- or the host's allocator pool, shared with the caller's tensors -- cannot hold one, step down instead of failing: record
@@ -720,6 +722,14 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
         if (!I->set.use_cache || I->shape_on) return fail("gradients of a light's texels need the replay cache and cannot be combined with vertex-position gradients");
         if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail("gradients of a light's texels: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
         if (!W.adjoint_inline) return fail("gradients of a light's texels need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
+    }
+    if (env_texels) {
+        if (!I->set.use_cache || I->shape_on) return fail("envmap gradients need the replay cache and cannot be combined with vertex-position gradients");
+        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail("envmap gradients: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
+        if (!W.adjoint_inline) return fail("envmap gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
+        /* the deposit addresses the REAL texels of the map, H x W: an image the constructor padded (to at least 2 x 3, envmap.cpp:125-131) has a smaller gradient buffer */
+        const HostTexture &T = S->hs.textures[S->hs.envmap.tex_index];
+        if (T.w != S->hs.envmap.w || T.h != S->hs.envmap.h) return fail("envmap gradients: an environment map smaller than 2 x 3 texels (padded by the emitter) is not differentiated");
     }
     if (blend) {
         if (I->set.grad_bsdf_params && attr_only) return fail("mesh_attribute: gradients of alpha / eta / k / specular colours are not produced for scenes with a `mesh_attribute` texture (the attributes' are)");
@@ -923,6 +933,13 @@ int har_integrator_set_grad_light_texels(HarIntegrator I, int on) {
     if (!I) return fail("null integrator");
     if (I->set.type != HAR_INTEGRATOR_PRB) return fail("gradients of a light's texels are computed by the `prb` integrator");
     I->set.grad_light_texels = on != 0;
+    return 0;
+}
+
+int har_integrator_set_grad_envmap(HarIntegrator I, int on) {
+    if (!I) return fail("null integrator");
+    if (I->set.type != HAR_INTEGRATOR_PRB) return fail("envmap gradients are computed by the `prb` integrator");
+    I->set.grad_envmap = on != 0;
     return 0;
 }
 

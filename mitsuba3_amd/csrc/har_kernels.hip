@@ -997,17 +997,26 @@ __device__ __forceinline__ void adjoint_commit_regs(const DScene &S, bool pred, 
     }
 }
 /* g * d radiance(u, v) / d texels into the gradient buffer of emitter `index`'s bitmap (type 7): the transpose of the lookup (nearest: four coincident taps of weight 1, 0, 0, 0);
- * called by whole waves */
+ * the environment map (type 2, HAR_SHADE_ENV_TEXELS): the transpose of envmap_eval_uv WITHOUT its `scale`, into the REAL texels of the map's image (envmap_taps folds the
+ * halo columns onto the edge they copy).  Called by whole waves */
+template <uint32_t TYPES>
 __device__ __forceinline__ void light_texel_commit(const DScene &S, float *const *grad_tex, bool pred, int32_t index, float u, float v, Vec3 g) {
     pred = pred && (g.x != 0.f || g.y != 0.f || g.z != 0.f);
     if (!__ballot(pred)) return;
-    TexTaps taps; float *dst = nullptr;
-    taps.idx[0] = taps.idx[1] = taps.idx[2] = taps.idx[3] = 0u; taps.w0x = taps.w1x = taps.w0y = taps.w1y = 0.f;
-    if (pred) { const uint32_t t = as_u32(S.emitters[index].radiance[0]); tex_taps(S.textures[t], u, v, taps); dst = grad_tex[t]; }
-    const float w[4] = { taps.w0x * taps.w0y, taps.w1x * taps.w0y, taps.w0x * taps.w1y, taps.w1x * taps.w1y };
+    uint32_t idx[4] = { 0u, 0u, 0u, 0u }; float w[4] = { 0.f, 0.f, 0.f, 0.f }; float *dst = nullptr;
+    if (pred) {
+        if ((TYPES & HAR_SCENE_TEXLIGHT) == 0u || S.emitters[index].type == 2u) {
+            EnvTaps T; envmap_taps(*S.envmap, u, v, T); dst = grad_tex[S.envmap->tex_index];
+            for (int k = 0; k < 4; ++k) { idx[k] = T.idx[k]; w[k] = T.w[k]; }
+        } else {
+            TexTaps taps; const uint32_t t = as_u32(S.emitters[index].radiance[0]); tex_taps(S.textures[t], u, v, taps); dst = grad_tex[t];
+            for (int k = 0; k < 4; ++k) idx[k] = taps.idx[k];
+            w[0] = taps.w0x * taps.w0y; w[1] = taps.w1x * taps.w0y; w[2] = taps.w0x * taps.w1y; w[3] = taps.w1x * taps.w1y;
+        }
+    }
     for (int k = 0; k < 4; ++k) {
         const bool on = pred && w[k] != 0.f;
-        wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
+        wave_aggregated_add3(on ? dst + 3 * (size_t) idx[k] : nullptr, on ? g * w[k] : Vec3(0.f), on);
     }
 }
 /* g = d L / d (slot 0 of BSDF record `rec`, evaluated at (u, v)) deposited where that record's gradient lives: its row of `grad_slots`, or -- a bitmap -- its entry of
@@ -1354,7 +1363,7 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
             }
             if (R.add_emission && MODE == MODE_PRB_ADJOINT && INLINE) {
                 Lr = Vec3(Lr.x - R.em_b.x, Lr.y - R.em_b.y, Lr.z - R.em_b.z); L_dirty = true;
-                if ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && R.lt_hit_emitter >= 0) { lt_hit = true; lt_hit_g = R.em_unit * dlr; }
+                if ((TYPES & (HAR_SCENE_TEXLIGHT | HAR_SCENE_ENVMAP)) != 0u && R.lt_hit_emitter >= 0) { lt_hit = true; lt_hit_g = R.em_unit * dlr; }
                 if (emitter_grads && R.em_index >= 0) {
                     const Vec3 g = R.em_unit * dlr;
                     if ((uint32_t) R.em_index < HAR_LDS_GRAD_EMITTERS) { eg_lds = true; eg_slot = (uint32_t) R.em_index; eg = g; }      /* committed below by the whole wave */
@@ -1392,12 +1401,13 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
             adjoint_commit_regs(S, item_pred, visible, make_float4(c.x, c.y, c.z, __uint_as_float(tag)), make_float4(R.dLr_drho.x, R.dLr_drho.y, R.dLr_drho.z, R.uv_x),
                                 make_float4(R.rel_grad.x, R.rel_grad.y, R.rel_grad.z, R.uv_y), Lr, L_dirty, dlr, grad_slots, grad_tex, gacc,      /* forward mode never commits in place (host) */
                                 tq.nq ? &tq : nullptr, &rec, (TYPES & HAR_SCENE_ATTR) != 0u ? &R.attr : nullptr);
-            if ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && (P.flags & HAR_SHADE_LIGHT_TEXELS)) {
+            if ((TYPES & (HAR_SCENE_TEXLIGHT | HAR_SCENE_ENVMAP)) != 0u && (P.flags & (((TYPES & HAR_SCENE_TEXLIGHT) != 0u ? HAR_SHADE_LIGHT_TEXELS : 0u) | HAR_SHADE_ENV_TEXELS))) {
                 /* the texels of a bitmap `radiance` (area.cpp:64-70): d Le / d radiance(si.uv) = beta mis at an emitter hit, d Lr_dir / d radiance(ds.uv) = beta mis f / pdf at a
-                 * VISIBLE emitter sample -- scattered through the transpose of the bilinear lookup, pre-reduced over the wave (all lanes of a block sample the same few texels) */
-                light_texel_commit(S, grad_tex, in_range && lt_hit, R.lt_hit_emitter, R.lt_hit_uv[0], R.lt_hit_uv[1], lt_hit_g);
+                 * VISIBLE emitter sample -- scattered through the transpose of the bilinear lookup, pre-reduced over the wave (all lanes of a block sample the same few texels).
+                 * The texels of the environment map (envmap.cpp:203-208, HAR_SHADE_ENV_TEXELS): the same two terms at an escaping ray and a visible sample of the map */
+                light_texel_commit<TYPES>(S, grad_tex, in_range && lt_hit, R.lt_hit_emitter, R.lt_hit_uv[0], R.lt_hit_uv[1], lt_hit_g);
                 const bool lt_nee = visible && R.lt_nee_emitter >= 0;
-                light_texel_commit(S, grad_tex, lt_nee, R.lt_nee_emitter, R.lt_nee_uv[0], R.lt_nee_uv[1], R.contrib_unit * dlr);
+                light_texel_commit<TYPES>(S, grad_tex, lt_nee, R.lt_nee_emitter, R.lt_nee_uv[0], R.lt_nee_uv[1], R.contrib_unit * dlr);
             }
             if (EXTRA && item_pred) {
                 /* the same two terms as for slot 0 (adjoint_commit_regs), for the five other parameter groups: g = dL * ([visible] d Lr_dir / d theta

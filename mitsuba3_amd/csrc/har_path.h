@@ -47,7 +47,9 @@ struct ShadeParams {
 #define HAR_SHADE_EXTRA_GRADS 16u    /* adjoint: also differentiate w.r.t. alpha / eta / k / colour slot 1 of the rough BSDF models (ShadeResult::x_dir / x_rel) */
 #define HAR_SHADE_SCALAR_DRAWS 8u    /* scalar variants: the two emitter samples are only drawn where the BSDF has a smooth lobe (path.cpp:244-249); JIT variants draw them on every lane */
 #define HAR_SHADE_LIGHT_TEXELS 64u    /* adjoint: also differentiate w.r.t. the texels of bitmap `radiance` textures of area lights (ShadeResult::lt_*; committed in place by the re-shading replay) */
-#define HAR_SHADE_HIDE_EMITTERS 2u   /* Integrator property `hide_emitters`: the environment is not seen by camera rays (path.cpp:114-115, prb.py:146-148) */
+#define HAR_SHADE_ENV_TEXELS 256u     /* adjoint: also differentiate w.r.t. the texels of the environment map (ShadeResult::lt_* with the map's emitter; committed in place by the re-shading replay,
+                                      * WITHOUT the map's `scale`: har_integrator_set_grad_envmap) */
+#define HAR_SHADE_HIDE_EMITTERS 2u  /* Integrator property `hide_emitters`: the environment is not seen by camera rays (path.cpp:114-115, prb.py:146-148) */
 #define HAR_SHADE_FUSED_NEE 128u     /* `path` on caller-supplied rays (Integrator::sample): the shadow-ray item carries ShadeResult::contrib_b and k_resolve adds it as path.cpp:279 does, result = fmadd(throughput, contrib_b, result),
                                       * with the throughput it reads back from the bounce's input wavefront (run_chunk) */
 #define HAR_ITEM_NO_EMITTER 0x7ffu   /* emitter field of an adjoint item's tag: contribution stored as is (no emitter gradient) */
@@ -79,7 +81,10 @@ struct ShadeResult {
     Vec3 x_dir[5], x_rel[5]; bool x_ind;
     /* ... with HAR_SHADE_LIGHT_TEXELS (kernels of scenes with a bitmap-radiance area light only): the emitter met at the vertex / sampled from it when its radiance is a bitmap
      * (-1: none), and the uv its bitmap is looked up at -- si.uv of the hit (area.cpp:83-90), ds.uv of the sample (:139-146).  d em_b / d radiance(uv) = em_unit, d contrib / d
-     * radiance(uv) = contrib_unit, as for the colour of a uniform light */
+     * radiance(uv) = contrib_unit, as for the colour of a uniform light.
+     * With HAR_SHADE_ENV_TEXELS (kernels that carry the environment-map code) the same fields serve the environment map: the map's emitter, the uv of the escaping ray's
+     * direction (envmap.cpp:228-236) / of the sampled direction after the half-texel shift (:284-323); em_unit / contrib_unit are then d / d (the bilinear lookup), the
+     * map's `scale` left out */
     int32_t lt_hit_emitter, lt_nee_emitter; float lt_hit_uv[2], lt_nee_uv[2];
     /* ... kernels of scenes with a `blendbsdf` record (HAR_SCENE_BLEND), at a blend vertex: the two nested records (0xffffffff at any other vertex), d Lr_dir / d slot 0 of
      * each and (d f / d slot 0) / f at the sampled direction -- the factors (1 - w) / w are in them and f is the BLENDED value; bl_ind: the second term exists.  The weight's
@@ -222,6 +227,9 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 R.em_index = (E.type != 2u && E.type != 7u && facing) ? emitter : -1;      /* (no colour parameter behind an environment map or a bitmap radiance) */
                 R.em_unit = st.throughput * mis;
                 if (textured && facing && (P.flags & HAR_SHADE_LIGHT_TEXELS)) { R.lt_hit_emitter = emitter; R.lt_hit_uv[0] = si.uv_x; R.lt_hit_uv[1] = si.uv_y; }
+                if (envmap && (P.flags & HAR_SHADE_ENV_TEXELS)) {          /* the escape term: d Le / d lookup(u, v) = beta * mis at the uv envmap_eval looks up */
+                    R.lt_hit_emitter = emitter; envmap_direction_to_uv(xf_vector(S.envmap->to_local, st.d), R.lt_hit_uv[0], R.lt_hit_uv[1]);
+                }
             }
         }
     }
@@ -277,7 +285,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
     DirSample ds; ds.pdf = 0.f; ds.d = Vec3(0.f); ds.p = Vec3(0.f); ds.n = Vec3(0.f); ds.dist = 0.f;
     Vec3 em_weight(0.f); float em_unit = 0.f; uint32_t em_sampled = 0;
-    bool lt_sampled = false;                                     /* HAR_SHADE_LIGHT_TEXELS: the sample lies on a bitmap-radiance light */
+    bool lt_sampled = false;                                     /* HAR_SHADE_LIGHT_TEXELS / _ENV_TEXELS: the sample lies on a bitmap-radiance light / the environment map */
     bool em_delta = false;                                       /* DirectionSample::delta: a point light's sample carries MIS weight 1 (path.cpp:274, prb.py:211) */
     bool active_em = active_next && S.n_emitters > 0 && smooth;
     if (active_em) {
@@ -296,8 +304,14 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
          * variants sample their only emitter directly (:351-354) and never multiply by its pmf */
         if (distr && (S.n_emitters > 1 || !(P.flags & HAR_SHADE_SCALAR_DRAWS))) sel_pmf = S.emitter_distr[index] * S.emitter_norm;
         else if (distr) sel_pmf = 1.f;
-        if ((TYPES & HAR_SCENE_ENVMAP) != 0u && S.emitters[index].type == 2u) envmap_sample_direction(*S.envmap, si.p, ex, ey, ds, em_weight);
-        else if ((TYPES & HAR_SCENE_ENVMAP) != 0u && S.emitters[index].type == 3u)
+        if ((TYPES & HAR_SCENE_ENVMAP) != 0u && S.emitters[index].type == 2u) {
+            /* (both passes of a texel-gradient step ask for the unit weight: a sample over texels that are all ZERO still has a derivative -- lt_sampled, as for a bitmap light) */
+            const bool et = MODE != MODE_PATH && (P.flags & HAR_SHADE_ENV_TEXELS) != 0u;
+            float et_uv[2] = { 0.f, 0.f };
+            envmap_sample_direction(*S.envmap, si.p, ex, ey, ds, em_weight, et ? &em_unit : nullptr, et ? et_uv : nullptr);
+            if (et) lt_sampled = true;
+            if (et && MODE == MODE_PRB_ADJOINT) { R.lt_nee_emitter = (int32_t) index; R.lt_nee_uv[0] = et_uv[0]; R.lt_nee_uv[1] = et_uv[1]; }
+        } else if ((TYPES & HAR_SCENE_ENVMAP) != 0u && S.emitters[index].type == 3u)
             mesh_emitter_sample_direction(S, S.emitters[index], si.p, ex, ey, ds, em_weight, MODE != MODE_PATH ? &em_unit : nullptr);
         else if ((TYPES & HAR_SCENE_ENVMAP) != 0u && S.emitters[index].type == 4u) {
             point_sample_direction(S.emitters[index], si.p, ds, em_weight, MODE != MODE_PATH ? &em_unit : nullptr); em_delta = true;
@@ -394,7 +408,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                     const Vec3 dk = ((st.throughput * mis_em) * cg.d[k]) * em_weight;
                     grad_item = grad_item || dk.x != 0.f || dk.y != 0.f || dk.z != 0.f;
                 }
-            if ((P.flags & HAR_SHADE_EMITTER_GRADS) || ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && lt_sampled)) {
+            if ((P.flags & HAR_SHADE_EMITTER_GRADS) || ((TYPES & (HAR_SCENE_TEXLIGHT | HAR_SCENE_ENVMAP)) != 0u && lt_sampled)) {
                 const Vec3 cu = ((st.throughput * mis_em) * ev.value) * em_unit;
                 grad_item = grad_item || cu.x != 0.f || cu.y != 0.f || cu.z != 0.f;
             }

@@ -45,7 +45,8 @@ struct Settings {
     float *grad_emitters = nullptr;       /* user buffer (DEVICE, emitter_count x 3) of har_integrator_set_grad_emitters, or null */
     float *grad_bsdf_params = nullptr;    /* user buffer (DEVICE, bsdf_count x 15) of har_integrator_set_grad_bsdf_params, or null */
     bool grad_light_texels = false;       /* har_integrator_set_grad_light_texels: the texels of bitmap `radiance` textures of area lights are differentiated (into their entries of grad_textures) */
-    float *alpha_film = nullptr;          /* user buffer (DEVICE, H x W x 4: channel 3 accumulates w * alpha) of har_integrator_set_alpha_film, or null */
+    bool grad_envmap = false;             /* har_integrator_set_grad_envmap: the texels of the environment map are differentiated (into the image's entry of grad_textures, without the map's `scale`) */
+    float *alpha_film = nullptr;         /* user buffer (DEVICE, H x W x 4: channel 3 accumulates w * alpha) of har_integrator_set_alpha_film, or null */
     /* har_integrator_set_batch_sensors: the child cameras of a batch sensor (DEVICE table, a block of its own) -- batch.n != 0: the `sensor` of the render calls is the
      * batch sensor's wide film and the camera rays come from the table (k_raygen_batch) */
     DBatch batch{ nullptr, 0u, 0u };
@@ -116,7 +117,9 @@ inline ChunkPlan plan_chunk(const Switches &W, const Settings &I, const SceneFac
     P.shade_flags = ((mode != MODE_PATH && I.grad_emitters) ? HAR_SHADE_EMITTER_GRADS : 0u)      /* (the primal pass of a backward step too: it traces the shadow rays of samples that only carry a radiance gradient, shade_lane) */ | (I.hide_emitters ? HAR_SHADE_HIDE_EMITTERS : 0u) |
                     (P.fwd ? HAR_SHADE_FORWARD_MODE : 0u) | ((mode == MODE_PRB_ADJOINT && I.grad_bsdf_params && !P.fwd) ? HAR_SHADE_EXTRA_GRADS : 0u) |
                     /* both passes of a backward step: the primal pass traces the shadow rays whose visibility the adjoint pass reads (shade_lane: lt_item) */
-                    ((mode != MODE_PATH && I.grad_light_texels && !J.forward_mode && (F.bsdf_types & HAR_SCENE_TEXLIGHT)) ? HAR_SHADE_LIGHT_TEXELS : 0u);
+                    ((mode != MODE_PATH && I.grad_light_texels && !J.forward_mode && (F.bsdf_types & HAR_SCENE_TEXLIGHT)) ? HAR_SHADE_LIGHT_TEXELS : 0u) |
+                    /* ... likewise for the texels of the environment map (the kernels that carry its code: HAR_SCENE_ENVMAP; env_emitter: the scene has an environment) */
+                    ((mode != MODE_PATH && I.grad_envmap && !J.forward_mode && (F.bsdf_types & HAR_SCENE_ENVMAP) && F.env_emitter >= 0) ? HAR_SHADE_ENV_TEXELS : 0u);
     /* grid: a multiple of 8 so that block b serves shard b % 8; enough blocks to cover the chunk once */
     P.grid = std::max<uint32_t>(SWITCH_SHARDS, std::min<uint32_t>(((J.n + 255) / 256 + SWITCH_SHARDS - 1) / SWITCH_SHARDS * SWITCH_SHARDS, 4096u));
     /* persistent traversal kernels: enough blocks to fill the chip (<= 8 blocks/CU), never more than the work; HAR_TRACE_GRID (A/B): blocks of a persistent launch */

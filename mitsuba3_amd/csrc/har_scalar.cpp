@@ -495,6 +495,41 @@ extern "C" int har_attribute_lookup_host(const HarSceneDesc *desc, uint32_t text
     catch (const std::exception &ex) { return har_set_error(std::string("har_attribute_lookup_host: ") + ex.what()); }
 }
 
+/* The lookup of the environment map and its transpose on the host, by the functions the kernels run (envmap_taps, envmap_eval_uv): n lookups at uv (2 x n).  idx / weight
+ * (4 x n): the taps in the REAL image; value (3 x n) = scale * sum_k w_k image[idx_k]; eval (3 x n) = envmap_eval_uv; with g (3 x n) and grad (h x w x 3, ACCUMULATED into)
+ * the deposit of the in-place commit under HAR_SHADE_ENV_TEXELS: grad[idx_k] += g * w_k */
+extern "C" int har_envmap_taps_host(const HarSceneDesc *desc, uint32_t n, const float *uv, uint32_t *idx, float *weight, float *value, float *eval, const float *g, float *grad) {
+    try {
+        if (!desc || (n && !uv) || (!g != !grad)) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (!B.hs.has_envmap || !B.ds.envmap) return har_set_error("har_envmap_taps_host: the scene has no environment map");
+        const DEnvmap &E = *B.ds.envmap;
+        const HostTexture &T = B.hs.textures[E.tex_index];
+        if (T.w != E.w || T.h != E.h) return har_set_error("envmap gradients: an environment map smaller than 2 x 3 texels (padded by the emitter) is not differentiated");
+        const size_t texels = (size_t) E.w * E.h;
+        for (uint32_t i = 0; i < n; ++i) {
+            const size_t i1 = n + (size_t) i, i2 = 2 * (size_t) n + i;
+            EnvTaps t; envmap_taps(E, uv[i], uv[i1], t);
+            for (int k = 0; k < 4; ++k) {
+                if (t.idx[k] >= texels) return har_set_error("har_envmap_taps_host: tap out of bounds");
+                if (idx) idx[k * (size_t) n + i] = t.idx[k];
+                if (weight) weight[k * (size_t) n + i] = t.w[k];
+            }
+            if (value) {
+                float acc[3] = { 0.f, 0.f, 0.f };
+                for (int k = 0; k < 4; ++k) for (int c = 0; c < 3; ++c) acc[c] += t.w[k] * T.data[3 * (size_t) t.idx[k] + c];
+                value[i] = acc[0] * E.scale; value[i1] = acc[1] * E.scale; value[i2] = acc[2] * E.scale;
+            }
+            if (eval) { const Vec3 v = envmap_eval_uv(E, uv[i], uv[i1]); eval[i] = v.x; eval[i1] = v.y; eval[i2] = v.z; }
+            if (grad) for (int k = 0; k < 4; ++k) for (int c = 0; c < 3; ++c) grad[3 * (size_t) t.idx[k] + c] += g[c * (size_t) n + i] * t.w[k];
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_envmap_taps_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_envmap_taps_host: ") + ex.what()); }
+}
+
 /* BSDF::eval_pdf / BSDF::sample of record `bsdf` of a scene on the host: the functions k_api_bsdf_eval_pdf / k_api_bsdf_sample run per lane (bsdf_side, bsdf_inputs,
  * bsdf_eval_pdf / bsdf_sample with the caller's context, the blend-carrying instantiation).  The twins of har_bsdf_eval_pdf / har_bsdf_sample: `value` / `pdf` may be
  * NULL, a masked lane returns zeros.  wi, wo, value, weight: 3 x n; uv, sample2: 2 x n. */

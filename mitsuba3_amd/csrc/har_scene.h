@@ -47,6 +47,7 @@ struct DEnvmap {
     float to_world[12], to_local[12];       /* column-major 3 x 4 */
     float center[3], radius;                /* scene bounding sphere (set_scene, :214-226) */
     uint32_t lvl_offset[HAR_ENV_MAX_LEVELS], lvl_width[HAR_ENV_MAX_LEVELS];
+    uint32_t tex_index;                     /* the image's entry of the scene's texture table (where its gradient lives: grad_textures, envmap_taps) */
 };
 
 struct DScene {
@@ -969,6 +970,25 @@ HAR_HD Vec3 envmap_eval_uv(const DEnvmap &E, float u_, float v_) {
     }
     return Vec3(out[0], out[1], out[2]);
 }
+/* The transpose of envmap_eval_uv: the four taps of that lookup as indices into the REAL image (H x W texels, row-major) and their weights, with the same arithmetic --
+ * envmap_eval_uv(u, v) = scale * sum_k w[k] * image[idx[k]].  The halo columns of the storage are copies of the opposite edge (refresh_halo, envmap.cpp:229-246): storage
+ * column 0 is real column W - 1, storage column W + 1 is real column 0, storage column x is real column x - 1 otherwise; rows clamp as the lookup clamps them. */
+struct EnvTaps { uint32_t idx[4]; float w[4]; };
+HAR_HD void envmap_taps(const DEnvmap &E, float u_, float v_, EnvTaps &T) {
+    const float rx = (float) E.w, ry = (float) E.h;
+    const float u = u_ - floorf(u_), v = clip01_(v_);
+    const float pos_x = fma_(u, rx, 1.f) / (rx + 2.f), pos_y = fma_(v, ry - 1.f, 0.5f) / ry;
+    const int32_t sw = (int32_t) E.w + 2, H = (int32_t) E.h, W = (int32_t) E.w;
+    const float px = fma_(pos_x, (float) sw, -0.5f), py = fma_(pos_y, ry, -0.5f);
+    const float fx = floorf(px), fy = floorf(py);
+    const int32_t ix = (int32_t) fx, iy = (int32_t) fy;
+    const float w1x = px - fx, w1y = py - fy, w0x = 1.f - w1x, w0y = 1.f - w1y;
+    const int32_t x0 = ix < 0 ? 0 : (ix > sw - 1 ? sw - 1 : ix), x1 = ix + 1 < 0 ? 0 : (ix + 1 > sw - 1 ? sw - 1 : ix + 1),
+                  y0 = iy < 0 ? 0 : (iy > H - 1 ? H - 1 : iy), y1 = iy + 1 < 0 ? 0 : (iy + 1 > H - 1 ? H - 1 : iy + 1);
+    const int32_t r0 = x0 == 0 ? W - 1 : (x0 == W + 1 ? 0 : x0 - 1), r1 = x1 == 0 ? W - 1 : (x1 == W + 1 ? 0 : x1 - 1);
+    T.idx[0] = (uint32_t) (y0 * W + r0); T.idx[1] = (uint32_t) (y0 * W + r1); T.idx[2] = (uint32_t) (y1 * W + r0); T.idx[3] = (uint32_t) (y1 * W + r1);
+    T.w[0] = w0x * w0y; T.w[1] = w1x * w0y; T.w[2] = w0x * w1y; T.w[3] = w1x * w1y;
+}
 HAR_HD void envmap_direction_to_uv(Vec3 d, float &u, float &v) {                                   /* envmap.cpp:454-459 */
     u = atan2_(d.x, -d.z) * (0.5f * HAR_INV_PI);
     v = acos_(fminf(fmaxf(d.y, -1.f), 1.f)) * HAR_INV_PI;
@@ -988,7 +1008,9 @@ HAR_HD float envmap_pdf_direction(const DEnvmap &E, Vec3 d_world) {
     return hier2d_eval(E, u, v) * inv_sin_theta * (1.f / (2.f * (HAR_PI * HAR_PI)));
 }
 /* EnvironmentMapEmitter::sample_direction (envmap.cpp:284-323) */
-HAR_HD void envmap_sample_direction(const DEnvmap &E, Vec3 ref_p, float sx, float sy, struct DirSample &ds, Vec3 &spec);
+/* `unit` (optional): the weight the sample would carry for a unit radiance LOOKUP, 1 / pdf (the map's `scale` is part of the lookup); `uv_out`: where the map is looked up,
+ * i.e. after the half-texel shift */
+HAR_HD void envmap_sample_direction(const DEnvmap &E, Vec3 ref_p, float sx, float sy, struct DirSample &ds, Vec3 &spec, float *unit = nullptr, float *uv_out = nullptr);
 
 /* PointLight::sample_direction (src/emitters/point.cpp:119-148): emitter type 4, position in to_world[9..11], `radiance` = radiant intensity; pdf 1, delta */
 HAR_HD void point_sample_direction(const DEmitter &E, Vec3 ref_p, DirSample &ds, Vec3 &spec, float *unit = nullptr) {
@@ -1053,9 +1075,10 @@ HAR_HD void emitter_sample_direction(const DEmitter &E, Vec3 ref_p, float sx, fl
     spec = active ? div3(Vec3(E.radiance[0], E.radiance[1], E.radiance[2]), ds.pdf) : Vec3(0.f);
     if (unit) *unit = active ? rcp_(ds.pdf) : 0.f;
 }
-HAR_HD void envmap_sample_direction(const DEnvmap &E, Vec3 ref_p, float sx, float sy, DirSample &ds, Vec3 &spec) {
+HAR_HD void envmap_sample_direction(const DEnvmap &E, Vec3 ref_p, float sx, float sy, DirSample &ds, Vec3 &spec, float *unit, float *uv_out) {
     float u, v, pdf; hier2d_sample(E, sx, sy, u, v, pdf);
     u += .5f / (float) E.w;
+    if (uv_out) { uv_out[0] = u; uv_out[1] = v; }
     const bool active = pdf > 0.f;
     float st, ct, sp, cp; sincos_(v * HAR_PI, st, ct); sincos_(u * (2.f * HAR_PI), sp, cp);
     const float inv_sin_theta = rcp_(fmaxf(st, 0x1p-24f));
@@ -1066,6 +1089,7 @@ HAR_HD void envmap_sample_direction(const DEnvmap &E, Vec3 ref_p, float sx, floa
     ds.p = fma3(d, dist, ref_p); ds.n = -d; ds.d = d; ds.dist = dist;
     ds.pdf = active ? pdf * inv_sin_theta * (1.f / (2.f * (HAR_PI * HAR_PI))) : 0.f;
     spec = active ? div3(envmap_eval_uv(E, u, v), ds.pdf) : Vec3(0.f);
+    if (unit) *unit = active ? rcp_(ds.pdf) : 0.f;
 }
 /* DiscreteDistribution::sample / sample_reuse_pmf (include/mitsuba/core/distr_1d.h:117-140,205-219): value *= sum; dr::binary_search over [lo, hi] (m_valid) with the
  * predicate of the variant -- JIT: (cdf[i] < value || cdf[i] == 0) && cdf[i] != sum, scalar: cdf[i] < value -- then the index, the re-used sample

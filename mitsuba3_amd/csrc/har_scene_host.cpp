@@ -246,7 +246,7 @@ static bool build_envmap(HostScene &hs, const HarTexture &img, const HarEmitter 
     if (!img.data || img.width == 0 || img.height == 0) { err = "envmap: empty bitmap"; return false; }
     DEnvmap &E = hs.envmap;
     const uint32_t W = std::max(img.width, 2u), H = std::max(img.height, 3u), sw = W + 2;
-    E.w = W; E.h = H; E.scale = e.radiance[0];
+    E.w = W; E.h = H; E.scale = e.radiance[0]; E.tex_index = e.mesh;
     std::memcpy(E.to_world, e.to_world, 48); std::memcpy(E.to_local, e.to_local, 48);
     E.center[0] = E.center[1] = E.center[2] = 0.f; E.radius = 1.f;
     std::vector<float> &T = hs.env_tex; T.assign((size_t) H * sw * 3, 0.f);
