@@ -114,6 +114,18 @@ typedef struct HarInstance {
 #define HAR_BSDF_MONO           16u     /* blend / mask: the weight / opacity bitmap has one channel; bumpmap: the height bitmap has */
 #define HAR_BSDF_NM_FLIP        64u     /* normalmap / bumpmap: flip_invalid_normals */
 #define HAR_BSDF_NM_SHADOW      128u    /* normalmap / bumpmap: use_shadowing_function */
+/* roughconductor: the roughness is a bitmap (roughconductor.cpp:195-198, m_alpha_u / m_alpha_v ->eval_1(si)).  Behind HAR_BSDF_ALPHA_TEX -- and only behind it -- `nested[0]`
+ * / `nested[1]` name the textures of alpha_u / alpha_v: -1 = that axis keeps the constant `alpha_u` / `alpha_v`, the same index twice = one isotropic `alpha` map.  A map
+ * with ONE channel (stored three times, channel 0 is read) sets HAR_BSDF_ALPHA_MONO_U / _V; a three-channel map is read as its luminance (Texture::eval_1).  Any filter, wrap
+ * mode and to_uv of the texture record apply.  Refused: the flag on another model (the alpha of `roughplastic` is a float), an index out of range, a `mesh_attribute`
+ * texture there, and a scene that also holds a `mesh_attribute` texture.  The record may be nested in a twosided / blendbsdf / mask / normalmap / bumpmap record (forward
+ * renders).  Gradients (`prb`, har_integrator_set_grad_bsdf_params): groups 0 / 1 (alpha_u / alpha_v) of such a record are scattered through the transpose of the lookup
+ * into the map's entry of `grad_textures` instead of the record's row (an isotropic map receives both; a lookup <= 1e-4, where Microfacet clamps, deposits nothing); eta / k /
+ * slot 1 go where they went.  Not produced: in a scene that also holds a blendbsdf / mask / normalmap / bumpmap record, with vertex-position / instance gradients, and in
+ * har_render_forward. */
+#define HAR_BSDF_ALPHA_TEX      256u
+#define HAR_BSDF_ALPHA_MONO_U   512u
+#define HAR_BSDF_ALPHA_MONO_V   1024u
 #define HAR_MESH_TANGENT_FRAME  4u      /* HarMesh::flags: under a `normalmap` the frame's s follows the face's dp_du (a rectangle) */
 #define HAR_MESH_FRAME_FLIPPED  8u      /* HarMesh::flags: SurfaceInteraction::frame_flipped of the shape (to_world mirrors, flip_normals included) */
 typedef struct HarBSDF {
@@ -126,7 +138,8 @@ typedef struct HarBSDF {
     float    eta;                     /* int_ior / ext_ior */
     float    eta_c[3], k_c[3];        /* conductor: real and imaginary part of the relative IOR */
     int32_t  back;
-    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask / normalmap / bumpmap: nested[0] (read for types 6 - 9 only) */
+    int32_t  nested[2];               /* blend: indices of the two nested records in HarSceneDesc::bsdfs; mask / normalmap / bumpmap: nested[0] (read for types 6 - 9 only);
+                                       * roughconductor with HAR_BSDF_ALPHA_TEX: the TEXTURE indices of alpha_u / alpha_v (-1: constant), read behind that flag only */
 } HarBSDF;
 
 /* BitmapTexture, raw H x W x 3 f32 (src/textures/bitmap.cpp:175-206). HOST pointer.  mode = filter_type | wrap_mode (bitmap.cpp:182-206):
@@ -417,6 +430,9 @@ int har_bsdf_sample(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, ui
                     float *pdf, float *weight /*[3][n]*/, float *eta, uint32_t *sampled_type, uint32_t *sampled_component, void *stream);
 /* BSDF::eval_pdf / sample with more of the interaction: geom (DEVICE, 18 x n) = si.n, si.sh_frame.n, .s, .t, si.dp_du, si.dp_dv, three rows each -- what a `bumpmap`
  * record's frame reads besides wi and uv (bumpmap.cpp:224-253).  Any record may be evaluated through them (only a bumpmap record reads geom); value OR pdf may be NULL. */
+/* The looked-up roughness of record `bsdf` at n uv points (uv 2 x n, device): alpha_u, alpha_v (n each, device) after the lookup of its roughness map(s) and BEFORE the
+ * max(., 1e-4) of the microfacet distribution; a record without HAR_BSDF_ALPHA_TEX returns its constants.  The record itself is read: no `twosided` side is chosen. */
+int har_bsdf_alpha(HarScene scene, uint32_t bsdf, uint32_t n, const float *uv /*[2][n]*/, float *alpha_u, float *alpha_v, void *stream);
 int har_bsdf_eval_pdf_si(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom /*[18][n]*/,
                          const uint8_t *active, float *value /*[3][n]*/, float *pdf, void *stream);
 int har_bsdf_sample_si(HarScene scene, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1, const float *sample2 /*[2][n]*/,
@@ -731,6 +747,12 @@ int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSD
                            const uint8_t *active, float *value, float *pdf);
 int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
                          const float *sample2, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component);
+/* d value / d {alpha_u, alpha_v, eta, k} of record `bsdf` (a plain model, possibly twosided) at n tuples on the HOST, by the per-lane code of the shading kernels that
+ * carry those terms: 3 x n each, default context; a roughness map is looked up at uv. */
+int har_bsdf_eval_extra_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi /*[3][n]*/, const float *uv /*[2][n]*/, const float *wo /*[3][n]*/,
+                             float *d_alpha_u, float *d_alpha_v, float *d_eta, float *d_k);
+/* ... and of har_bsdf_alpha (host arrays; the same per-lane code) */
+int har_bsdf_alpha_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *uv /*[2][n]*/, float *alpha_u, float *alpha_v);
 /* The lookup of HAR_TEX_MESH_ATTRIBUTE record `texture` and its transpose on the HOST (no GPU), by the per-lane code of the kernels: n hits on the record's mesh, face prim[i]
  * at the point p (3 x n).  value (3 x n, may be NULL) = the colour looked up; g (3 x n) with grad (rows x 3, ACCUMULATED into; both or neither) = the deposit of the adjoint:
  * grad[row_k] += g * b_k * scale over the lookup's three rows (a face attribute: its one row).  All pointers HOST. */

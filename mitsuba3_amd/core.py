@@ -1153,7 +1153,7 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
 BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8, 'bumpmap': 9}
 _NESTING_BSDFS = ('blendbsdf', 'mask', 'normalmap', 'bumpmap')          # records that name nested records: built by the plugin factory
-_MONO_TEX_BSDFS = ('blendbsdf', 'mask', 'bumpmap')          # records whose bitmap may have ONE channel (stored three times; `weight_channels`)
+_MONO_TEX_BSDFS = ('blendbsdf', 'mask', 'bumpmap', 'alphamap')          # records whose bitmap may have ONE channel (stored three times; `weight_channels`); 'alphamap': a roughconductor's roughness map (_AlphaMap)
 _NOGRAD_PARAMS = ('ior', 'scale')          # non-colour parameters that are updatable and carry no gradient (ParamFlags::NonDifferentiable)
 _WEIGHTED_BSDFS = ('blendbsdf', 'mask')          # records whose slot 0 is a scalar texture (Texture::eval_1): the blend weight, the mask opacity
 _LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
@@ -1232,9 +1232,44 @@ class _RecordFlags(int):
         return self._owner._lobe_flags(index)
 
 
+class _AlphaMap:
+    """`alpha` / `alpha_u` / `alpha_v` of a `roughconductor` given as a `bitmap` (get_unbounded_texture, roughconductor.cpp:195-198; read by Texture::eval_1): a texture of
+    the scene that no colour slot names.  It carries what the parameter tables read of a textured slot (`texture`, `tex_mode`, `tex_to_uv`, `tex_index`, `slot0_name`,
+    `weight_channels`), so '<bsdf>.<name>.data' / '.to_uv' are shown, updated and differentiated like any other bitmap's"""
+    kind = 'alphamap'; attr = None
+
+    def __init__(self, name, props):
+        src = props['data'] if 'data' in props else (props['bitmap'].data if isinstance(props.get('bitmap'), Bitmap) else Bitmap(props['filename']).data if 'filename' in props else None)
+        ch = None if src is None else (1 if len(tuple(src.shape)) == 2 else int(src.shape[2]))
+        if ch is not None and ch not in (1, 3):
+            raise RuntimeError("roughconductor: the `%s` bitmap has %d channels, expected 1 or 3" % (name, ch))
+        self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(props)
+        self.slot0_name = name; self.weight_channels = ch; self.tex_index = None; self.owner = None
+
+    def mean(self):
+        """the mean of Texture::eval_1 over the texels: the constant the record carries next to the map (nothing shades with it)"""
+        t = np.asarray(self.texture, np.float64)
+        return float(t[:, :, 0].mean() if self.weight_channels == 1 else (t * np.asarray(_LUMINANCE)).sum(axis=2).mean())
+
+
 class BSDF:
     """diffuse / dielectric / conductor / plastic / roughconductor / roughplastic (src/bsdfs/*.cpp), optionally wrapped by `twosided`.
-    Colour parameters live in two slots (include/hip_ad_rgb.h HarBSDF); slot 0 may be a raw `bitmap`."""
+    Colour parameters live in two slots (include/hip_ad_rgb.h HarBSDF); slot 0 may be a raw `bitmap`, and so may the roughness of a `roughconductor`."""
+
+    def _alpha_prop(self, props, name):
+        """`alpha` / `alpha_u` / `alpha_v` of a rough model: a float, or -- `roughconductor` only -- a `bitmap` of 1 or 3 channels, kept in self.alpha_maps[name]"""
+        v = props.get(name, 0.1)
+        if not isinstance(v, dict):
+            return float(v)
+        if self.kind != 'roughconductor':
+            raise RuntimeError("roughplastic: `%s` is a float (roughplastic.cpp:210: a Float member); an alpha bitmap is supported on `roughconductor`" % name)
+        if v.get('type') == 'mesh_attribute':
+            raise RuntimeError("roughconductor: a `mesh_attribute` texture as `%s` is not supported in hip_ad_rgb (a float or a `bitmap` is)" % name)
+        if v.get('type') != 'bitmap':
+            raise RuntimeError("roughconductor: `%s` is a float or a `bitmap` texture in hip_ad_rgb (got \"%s\")" % (name, v.get('type')))
+        am = _AlphaMap(name, v); am.owner = self
+        self.alpha_maps[name] = am
+        return am.mean()
 
     def __init__(self, props=None, id=None):
         props = props or {}
@@ -1264,6 +1299,7 @@ class BSDF:
             raise RuntimeError("Plugin \"%s\" not found for variant hip_ad_rgb (textures: rgb, bitmap, mesh_attribute)" % refl['type'])
         self.value2 = _rgb_value(props.get(slot1[0]), slot1[1]) if slot1 else _f32([0, 0, 0])
         self.flags = 0; self.alpha_u = self.alpha_v = 0.1; self.eta = 1.0; self.anisotropic = False
+        self.alpha_maps = {}          # roughconductor: 'alpha', or 'alpha_u' / 'alpha_v', -> _AlphaMap where that roughness is a bitmap
         self.eta_c = _f32([0, 0, 0]); self.k_c = _f32([1, 1, 1]); self.back = None
         if self.kind in ('roughconductor', 'roughplastic'):          # MicrofacetDistribution(props), microfacet.h:103-144
             distr = str(props.get('distribution', 'beckmann')).lower()
@@ -1278,9 +1314,12 @@ class BSDF:
                     raise RuntimeError("Microfacet model: both 'alpha_u' and 'alpha_v' must be specified.")
                 if 'alpha' in props:
                     raise RuntimeError("Microfacet model: please specifyeither 'alpha' or 'alpha_u'/'alpha_v'.")
-                self.alpha_u = float(props['alpha_u']); self.alpha_v = float(props['alpha_v']); self.anisotropic = True
+                self.alpha_u = self._alpha_prop(props, 'alpha_u'); self.alpha_v = self._alpha_prop(props, 'alpha_v'); self.anisotropic = True
             else:
-                self.alpha_u = self.alpha_v = float(props.get('alpha', 0.1))
+                self.alpha_u = self.alpha_v = self._alpha_prop(props, 'alpha')
+            if self.alpha_maps:          # HAR_BSDF_ALPHA_TEX, and HAR_BSDF_ALPHA_MONO_U / _V for a one-channel map on that axis
+                mu = self.alpha_maps.get('alpha', self.alpha_maps.get('alpha_u')); mv = self.alpha_maps.get('alpha', self.alpha_maps.get('alpha_v'))
+                self.flags |= 256 | (512 if mu is not None and mu.weight_channels == 1 else 0) | (1024 if mv is not None and mv.weight_channels == 1 else 0)
         if self.kind in ('roughconductor', 'conductor'):             # roughconductor.cpp:163-172, conductor.cpp:228-237
             if props.get('material', 'none') != 'none':
                 if 'eta' in props:
@@ -1380,7 +1419,8 @@ class BSDF:
         """BSDFFlags of the components of this plugin without a `twosided` wrapper (the constructors of src/bsdfs/*.cpp)"""
         F = BSDFFlags; fs = F.FrontSide
         return {'diffuse': [F.DiffuseReflection | fs], 'dielectric': [F.DeltaReflection | fs | F.BackSide, F.DeltaTransmission | fs | F.BackSide | F.NonSymmetric],
-                'roughconductor': [F.GlossyReflection | fs | (F.Anisotropic if self.alpha_u != self.alpha_v else 0)],
+                # (Anisotropic: m_alpha_u != m_alpha_v compares the texture OBJECTS, roughconductor.cpp:205 -- with a roughness map, whether the two were given separately)
+                'roughconductor': [F.GlossyReflection | fs | (F.Anisotropic if (self.anisotropic if getattr(self, 'alpha_maps', None) else self.alpha_u != self.alpha_v) else 0)],
                 'roughplastic': [F.GlossyReflection | fs, F.DiffuseReflection | fs], 'conductor': [F.DeltaReflection | fs], 'plastic': [F.DeltaReflection | fs, F.DiffuseReflection | fs]}[self.kind]
 
     def _lobe_flags(self, index=None):
@@ -2175,6 +2215,12 @@ class Integrator:
         else:
             check(lib().har_integrator_set_grad_positions(self._handle(), None, None))
             check(lib().har_integrator_set_grad_instances(self._handle(), None, None))
+        amap_keys = sorted(k for k, (kind, b) in scene._param_keys().items() if getattr(b, 'kind', None) == 'alphamap')
+        if self.bsdf_parameter_gradients and amap_keys and any(b.kind in _NESTING_BSDFS for b in scene.bsdfs):
+            raise RuntimeError("%s: the alpha texel gradients of a roughness map are not produced for a scene that also holds a `%s` in hip_ad_rgb (a roughconductor nested in a "
+                               "`blendbsdf` / `mask` / `normalmap` / `bumpmap` renders; its alpha texels have no gradient)" % (amap_keys, next(b.kind for b in scene.bsdfs if b.kind in _NESTING_BSDFS)))
+        if self.bsdf_parameter_gradients and amap_keys and self.shape_gradients:
+            raise RuntimeError("%s: the alpha texel gradients of a roughness map cannot be combined with vertex-position / instance gradients (`shape_gradients`) in hip_ad_rgb" % amap_keys)
         if self.bsdf_parameter_gradients and any(b.kind == 'mask' for b in scene.bsdfs):
             raise RuntimeError("%s: `bsdf_parameter_gradients` is not implemented for a scene with a `mask` in hip_ad_rgb (its `opacity` and the nested BSDF's colour slot 0 have gradients)"
                                % sorted(k for k, (what, b) in scene._bsdf_param_keys().items() if what not in _NOGRAD_PARAMS))
@@ -2196,7 +2242,7 @@ class Integrator:
             check(lib().har_integrator_set_grad_bsdf_params(self._handle(), None))
             check(lib().har_integrator_set_grad_light_texels(self._handle(), 0))
             check(lib().har_integrator_set_grad_envmap(self._handle(), 0))
-        out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None)
+        out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None, alpha_maps=g_extra is not None)
         if g_extra is not None:
             for k, (what, b) in scene._bsdf_param_keys().items():
                 if what in _NOGRAD_PARAMS:
@@ -2621,6 +2667,8 @@ class Scene:
         b.scene = self; b.index = len(self.bsdf_objs)
         if b.texture is not None:
             b.tex_index = len(self.textures); self.textures.append(b.texture); self.texture_modes.append(b.tex_mode); self.texture_to_uv.append(b.tex_to_uv)
+        for am in (getattr(b, 'alpha_maps', None) or {}).values():          # a roughness map is a texture of the scene that no colour slot names
+            am.tex_index = len(self.textures); self.textures.append(am.texture); self.texture_modes.append(am.tex_mode); self.texture_to_uv.append(am.tex_to_uv)
         self.bsdf_objs.append(b)
         for c in getattr(b, 'nested', ()):           # blendbsdf: the nested BSDFs are records of their own (an object referenced from several places is lowered once)
             self._add_bsdf(c)
@@ -2811,6 +2859,9 @@ class Scene:
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, b.nested[1].index)
             elif b.kind in ('mask', 'normalmap', 'bumpmap'):
                 bsdfs[i].nested = (C.c_int32 * 2)(b.nested[0].index, -1)
+            elif getattr(b, 'alpha_maps', None):          # HAR_BSDF_ALPHA_TEX: the texture indices of alpha_u / alpha_v (-1: that axis is a float)
+                mu = b.alpha_maps.get('alpha', b.alpha_maps.get('alpha_u')); mv = b.alpha_maps.get('alpha', b.alpha_maps.get('alpha_v'))
+                bsdfs[i].nested = (C.c_int32 * 2)(mu.tex_index if mu is not None else -1, mv.tex_index if mv is not None else -1)
         texs = (M.HarTexture * max(1, len(self.textures)))()
         for i, t in enumerate(self.textures):
             texs[i].data = _fp(t); texs[i].height = t.shape[0]; texs[i].width = t.shape[1]; texs[i].mode = self.texture_modes[i] if i < len(self.texture_modes) else 0
@@ -2951,6 +3002,8 @@ class Scene:
                 keys[base + "." + b.slot0_name + ".data"] = ("tex", b)
             else:
                 keys[base + "." + b.slot0_name + ".value"] = ("rgb", b)
+            for name, am in (getattr(b, 'alpha_maps', None) or {}).items():          # '<bsdf>.alpha.data' (BitmapTexture::traverse under roughconductor.cpp:216-220)
+                keys[base + "." + name + ".data"] = ("tex", am)
         # emitter radiances: `<shape>.emitter.radiance.value` for area lights, `<emitter>.radiance.value` for `constant` (type 2 = envmap: none)
         for i, key in enumerate(self._emitter_order):
             e = self.emitters[i]
@@ -3027,10 +3080,9 @@ class Scene:
             if b.kind == 'roughplastic':
                 keys[base + ".alpha"] = ("alpha", b)                  # a Float member, not a texture: no '.value' (roughplastic.cpp:210, :534)
             elif b.kind == 'roughconductor':
-                if b.anisotropic:
-                    keys[base + ".alpha_u.value"] = ("alpha_u", b); keys[base + ".alpha_v.value"] = ("alpha_v", b)
-                else:
-                    keys[base + ".alpha.value"] = ("alpha", b)
+                for name in (("alpha_u", "alpha_v") if b.anisotropic else ("alpha",)):          # (a roughness map shows '.data' / '.to_uv' instead: _param_keys, _pose_keys)
+                    if name not in (getattr(b, 'alpha_maps', None) or {}):
+                        keys[base + "." + name + ".value"] = (name, b)
             if b.kind == 'roughconductor':
                 keys[base + ".eta.value"] = ("eta", b); keys[base + ".k.value"] = ("k", b)
             if b.kind == 'roughplastic' and b.slot1_name:
@@ -3342,6 +3394,8 @@ class Scene:
         for b in self.bsdf_objs:            # BitmapTexture::traverse: `to_uv` (src/textures/bitmap.cpp), NonDifferentiable
             if b.texture is not None and getattr(b, 'attr', None) is None:          # (a `mesh_attribute` has no to_uv: its only own parameter is `scale`)
                 keys[self._bsdf_key_base(b) + "." + b.slot0_name + ".to_uv"] = ("to_uv", b)
+            for name, am in (getattr(b, 'alpha_maps', None) or {}).items():
+                keys[self._bsdf_key_base(b) + "." + name + ".to_uv"] = ("to_uv", am)
         return keys
 
     def _pose_value(self, kind, b):
@@ -3569,12 +3623,17 @@ class Scene:
         g_data[:, 1:-1, :] = D * float(self.emitters[i]["radiance"][0])
         return {key_d: g_data, key_s: (D.double() * data.double()).sum().to(torch.float32).reshape(1)}
 
-    def _gradients(self, g_refl, g_tex, g_emit=None):
+    def _gradients(self, g_refl, g_tex, g_emit=None, alpha_maps=False):
         out = {}
         for k, (kind, b) in self._param_keys().items():
             if kind == "emit":
                 if g_emit is not None:
                     out[k] = g_emit[b]
+            elif b.kind == 'alphamap':
+                # a roughness map: filled by the alpha terms of the adjoint (`bsdf_parameter_gradients`) alone, through the transpose of eval_1 -- the luminance coefficients
+                # are in it; a one-channel map received channel 0.  Without those terms the key has no gradient (not a zero one)
+                if alpha_maps:
+                    out[k] = g_tex[b.tex_index] if b.weight_channels == 3 else g_tex[b.tex_index][:, :, :1].contiguous()
             elif b.kind in _WEIGHTED_BSDFS:
                 # the weight of a blend (the opacity of a mask): the buffers hold d L / d w per colour channel of the radiance; the parameter is a scalar (sum of the row, as `alpha` is summed), a
                 # one-channel bitmap (channel sum) or a three-channel one whose luminance is the weight (d w / d texel_k = lum_k)
@@ -4080,6 +4139,9 @@ class DeviceGroup:
             raise RuntimeError("render_backward(): only the `prb` integrator implements the adjoint pass in hip_ad_rgb")
         if getattr(self.integrator, 'envmap_gradients', False):
             raise RuntimeError("envmap gradients are not produced by DeviceGroup.render_backward() (har_multi_render_backward has no switch for them); use one device")
+        if getattr(self.integrator, 'bsdf_parameter_gradients', False) and any(getattr(b, 'alpha_maps', None) for b in self.scene.bsdfs):
+            raise RuntimeError("roughness map: the alpha texel gradients %s are not produced by DeviceGroup.render_backward() (har_multi_render_backward routes no BSDF-parameter gradients); use one device"
+                               % sorted(k for k, (kind, b) in self.scene._param_keys().items() if getattr(b, 'kind', None) == 'alphamap'))
         torch = _torch()
         s = self.scene.sensors()[sensor] if isinstance(sensor, int) else sensor
         _refuse_batch(s, "DeviceGroup (har_multi_render_backward)")
@@ -4342,6 +4404,10 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
     nested = [k for k in keys if k in scene._bsdf_param_keys() and id(scene._bsdf_param_keys()[k][1]) in scene._blend_nested()]
     if nested:
         raise RuntimeError("%s: the non-colour parameters of a BSDF nested in a `blendbsdf` / `mask` / `normalmap` / `bumpmap` have no gradient in hip_ad_rgb (a blend's `weight`, a mask's `opacity` and the colour slot 0 of the BSDFs nested in them do)" % nested)
+    amap_nested = [k for k in keys if getattr(scene._param_keys().get(k, (None, None))[1], 'kind', None) == 'alphamap' and id(scene._param_keys()[k][1].owner) in scene._blend_nested()]
+    if amap_nested:
+        raise RuntimeError("%s: the alpha texels of a roughness map on a BSDF nested in a `blendbsdf` / `mask` / `normalmap` / `bumpmap` have no gradient in hip_ad_rgb (the map renders there; "
+                           "under a plain or `twosided` roughconductor its texels are differentiated)" % amap_nested)
     if not keys:
         return integrator.render(scene, sensor, seed, spp)
     params.update()
@@ -4355,7 +4421,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
         shape_keys = [k for k in keys if k in scene._position_keys() or k in scene._instance_keys() or k in scene._rect_keys()]
         if shape_keys and integrator_ad.shape_gradients is not True:
             overrides['shape_gradients'] = sorted(set(list(integrator_ad.shape_gradients or [])) | set(shape_keys))
-        if any(k in scene._bsdf_param_keys() for k in keys) and not integrator_ad.bsdf_parameter_gradients:
+        if any(k in scene._bsdf_param_keys() or getattr(scene._param_keys().get(k, (None, None))[1], 'kind', None) == 'alphamap' for k in keys) and not integrator_ad.bsdf_parameter_gradients:
             overrides['bsdf_parameter_gradients'] = True
         if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator_ad.light_texel_gradients:
             overrides['light_texel_gradients'] = True

@@ -37,6 +37,11 @@ enum { BF_TWOSIDED = 1u, BF_GGX = 2u, BF_SAMPLE_VISIBLE = 4u, BF_NONLINEAR = 8u,
 /* a normalmap record: BF_NM_SMOOTH (the same derived bit again: the nested BSDF has a smooth lobe), BF_NM_FLIP = flip_invalid_normals, BF_NM_SHADOW = use_shadowing_function
  * (normalmap.cpp:114-115) */
 enum { BF_NM_SMOOTH = 32u, BF_NM_FLIP = 64u, BF_NM_SHADOW = 128u };          /* (a bumpmap record reads the same three bits, and BF_MONO for a one-channel height map) */
+/* a roughconductor record whose roughness is a bitmap (roughconductor.cpp:195-198, m_alpha_u / m_alpha_v ->eval_1(si)): BF_ALPHA_TEX = DBsdf::table / ::pad name the
+ * texture records of alpha_u / alpha_v (-1: that axis keeps the constant DBsdf::alpha_u / ::alpha_v; the same index twice for an isotropic map), BF_ALPHA_MONO_U / _V =
+ * that map has ONE channel (stored three times, channel 0 is read); a three-channel map is read as its luminance, as Texture::eval_1 does.  Only the kernels of scenes
+ * that hold such a record (HAR_SCENE_ALPHAMAP) test these bits */
+enum { BF_ALPHA_TEX = 256u, BF_ALPHA_MONO_U = 512u, BF_ALPHA_MONO_V = 1024u };
 enum { LOBE_NULL = 0x1u };                    /* BSDFFlags::Null (bsdf.h:37): the only lobe of that kind is the mask record's */
 #define HAR_ROUGH_TRANSMITTANCE_RES 64          /* MI_ROUGH_TRANSMITTANCE_RES, include/mitsuba/render/microfacet.h */
 
@@ -282,7 +287,9 @@ HAR_HD float lerp_gather(const float *data, float x, uint32_t size) {
     return lerp_(v0, v1, x - (float) index);
 }
 
-struct BsdfInputs { Vec3 slot0, slot1; const float *table; };       /* evaluated colour parameters + roughplastic table */
+/* evaluated colour parameters + roughplastic table; alpha_u / alpha_v: the roughness of a roughconductor record at the vertex, before Microfacet's max(., 1e-4) --
+ * filled and read by the kernels of scenes with a roughness map only (HAR_SCENE_ALPHAMAP; every other kernel reads DBsdf::alpha_u / ::alpha_v as it did) */
+struct BsdfInputs { Vec3 slot0, slot1; const float *table; float alpha_u, alpha_v; };
 
 HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC && B.type != BSDF_CONDUCTOR; }          /* BSDFFlags::Smooth */
 /* material class of a BSDF record for the per-material shading queues: its model when both sides of the surface evaluate the same model (plain records,
@@ -342,9 +349,17 @@ static_assert((HAR_SCENE_ATTR & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1
 #define HAR_SCENE_BUMPMAP_TYPES (HAR_SCENE_NORMALMAP_TYPES | HAR_SCENE_BUMPMAP)
 #define HAR_SCENE_NMAP_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP)
 #define HAR_SCENE_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP)
-#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
+#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP | HAR_SCENE_ALPHAMAP /* below */)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
 static_assert((HAR_SCENE_NORMALMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x8000u | 0x80000000u)) == 0u, "HAR_SCENE_NORMALMAP collides with another scene bit");
 static_assert((HAR_SCENE_BUMPMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x4000u | 0x80000000u)) == 0u, "HAR_SCENE_BUMPMAP collides with another scene bit");
+/* ... and a roughconductor record whose `alpha` is a bitmap (BF_ALPHA_TEX): the roughness is looked up at every vertex on such a record and rides in BsdfInputs.  A scene
+ * with such a record sets this bit and runs a widest set of its own, TYPES = HAR_SCENE_ALPHAMAP_TYPES = the bumpmap set | HAR_SCENE_ALPHAMAP (the record may sit under a
+ * blend / mask / normalmap / bumpmap record, or next to them); every line of roughness-map code sits behind a test of this bit.  Unlike the record bits it reaches the leaf
+ * models: THEY read the looked-up roughness */
+#define HAR_SCENE_ALPHAMAP 0x10000u
+#define HAR_SCENE_ALPHAMAP_TYPES (HAR_SCENE_BUMPMAP_TYPES | HAR_SCENE_ALPHAMAP)
+#define HAR_SCENE_ALPHAMAP_LEAN_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_ALPHAMAP)      /* ... without a blend / mask / normalmap / bumpmap record in the scene: no composite code */
+static_assert((HAR_SCENE_ALPHAMAP & (0xffffu | 0x80000000u)) == 0u, "HAR_SCENE_ALPHAMAP collides with another scene bit");
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */
@@ -374,7 +389,7 @@ HAR_HD void bsdf_eval_pdf_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec
         if (CTX && !ctx.is_enabled(LOBE_GLOSSY_REFLECTION)) return;
         Vec3 H = normalize3(wo + wi);
         if (!(cos_theta_i > 0.f && cos_theta_o > 0.f && dot3(wi, H) > 0.f && dot3(wo, H) > 0.f)) return;
-        Microfacet distr((B.flags & BF_GGX) != 0, B.alpha_u, B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
+        Microfacet distr((B.flags & BF_GGX) != 0, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_u : B.alpha_u, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_v : B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
         float D = distr.eval(H);
         bool active = D != 0.f;
         float smith_g1_wi = distr.smith_g1(wi, H), G = smith_g1_wi * distr.smith_g1(wo, H);
@@ -445,6 +460,7 @@ HAR_HD void bsdf_eval_pdf_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec
  *   d_eta / d_k           : roughconductor's complex IOR, channel-diagonal through the conductor Fresnel term
  * (roughplastic's `eta` and its transmittance tables are not differentiable in the reference either: ScalarFloat members.) */
 struct BsdfEvalExtra { Vec3 d_alpha_u, d_alpha_v, d_eta, d_k; };
+template <uint32_t TYPES = HAR_BSDF_ALL_TYPES>          /* (only the HAR_SCENE_ALPHAMAP bit is read: the roughness comes from `in`) */
 HAR_HD void bsdf_eval_extra_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, Vec3 wo, BsdfEvalExtra &x) {
     x.d_alpha_u = Vec3(0.f); x.d_alpha_v = Vec3(0.f); x.d_eta = Vec3(0.f); x.d_k = Vec3(0.f);
     const float cos_theta_i = wi.z, cos_theta_o = wo.z;
@@ -452,7 +468,7 @@ HAR_HD void bsdf_eval_extra_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, V
     if (B.type == BSDF_ROUGHCONDUCTOR) {
         const Vec3 H = normalize3(wo + wi);
         if (!(dot3(wi, H) > 0.f && dot3(wo, H) > 0.f)) return;
-        Microfacet distr((B.flags & BF_GGX) != 0, B.alpha_u, B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
+        Microfacet distr((B.flags & BF_GGX) != 0, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_u : B.alpha_u, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_v : B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
         const float D = distr.eval(H);
         if (D == 0.f) return;
         const float V = D * distr.G(wi, wo, H) / (4.f * cos_theta_i), c = dot3(wi, H);
@@ -509,7 +525,7 @@ HAR_HD void bsdf_sample_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, float
         if (!HAR_BSDF_HAS(TYPES, BSDF_ROUGHCONDUCTOR)) return;
         if (CTX && !ctx.is_enabled(LOBE_GLOSSY_REFLECTION)) return;
         if (!(cos_theta_i > 0.f)) return;
-        Microfacet distr((B.flags & BF_GGX) != 0, B.alpha_u, B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
+        Microfacet distr((B.flags & BF_GGX) != 0, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_u : B.alpha_u, (TYPES & HAR_SCENE_ALPHAMAP) != 0u ? in.alpha_v : B.alpha_v, (B.flags & BF_SAMPLE_VISIBLE) != 0);
         float pdf; Vec3 m = distr.sample(wi, s2x, s2y, pdf);
         bs.wo = reflect_m(wi, m); bs.eta = 1.f; bs.pdf = pdf; bs.type = LOBE_GLOSSY_REFLECTION;
         bool active = pdf != 0.f && bs.wo.z > 0.f;

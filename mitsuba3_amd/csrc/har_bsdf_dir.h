@@ -99,6 +99,7 @@ HAR_HD D6 d6_lerp_gather(const float *data, const D6 &x, uint32_t size) {
 
 /* F = sum_c A_c value_c(wi, wo) of ONE (not twosided) record and its partials: g[0..2] = dF / d wi, g[3..5] = dF / d wo.  `wi`, `wo` are the directions the
  * record is evaluated with (the caller has mirrored them for the back side of a twosided BSDF and mirrors g[2], g[5] back).  Returns the value. */
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_ALPHAMAP bit is read: a roughconductor's roughness comes from `in`) */
 HAR_HD float bsdf_weighted_value_dir(const DBsdf &B, const BsdfInputs &in, Vec3 wi_v, Vec3 wo_v, Vec3 A, float g[6]) {
     for (int i = 0; i < 6; ++i) g[i] = 0.f;
     if (!(wi_v.z > 0.f && wo_v.z > 0.f)) return 0.f;
@@ -115,7 +116,8 @@ HAR_HD float bsdf_weighted_value_dir(const DBsdf &B, const BsdfInputs &in, Vec3 
         break;
     case BSDF_ROUGHCONDUCTOR: case BSDF_ROUGHPLASTIC: {
         const bool rc = B.type == BSDF_ROUGHCONDUCTOR, ggx = (B.flags & BF_GGX) != 0;
-        const float au = fmaxf(B.alpha_u, 1e-4f), av = rc ? fmaxf(B.alpha_v, 1e-4f) : au;
+        const bool amap = (TYPES & HAR_SCENE_ALPHAMAP) != 0u && rc;
+        const float au = fmaxf(amap ? in.alpha_u : B.alpha_u, 1e-4f), av = rc ? fmaxf(amap ? in.alpha_v : B.alpha_v, 1e-4f) : au;
         D6Vec H{ wi.x + wo.x, wi.y + wo.y, wi.z + wo.z };
         const D6 il = d6_rcp(d6_safe_sqrt(d6_dot(H, H)));
         H.x = H.x * il; H.y = H.y * il; H.z = H.z * il;

@@ -20,6 +20,7 @@ namespace har {
 /* F = sum_c A_c value_c(wi, wo) of bumpmap record B at the scaled height gradient (gx, gy), and dg[0] = dF / d gx, dg[1] = dF / d gy.  wi, wo: local directions of the
  * vertex as the record sees them (an outer `twosided` has folded them already: the fold does not depend on the texels).  (u, v): the vertex's texture coordinates,
  * for the nested record's own colours. */
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_ALPHAMAP bit is read: the nested record may carry a roughness map) */
 HAR_HD float bumpmap_weighted_value_grad(const DScene &S, const DBsdf &B, const BumpGeom &G, float gx, float gy, Vec3 wi, Vec3 wo, float u, float v, Vec3 A, float dg[2]) {
     dg[0] = dg[1] = 0.f;
     /* forward, as bumpmap_frame_grad (har_scene.h) */
@@ -41,9 +42,9 @@ HAR_HD float bumpmap_weighted_value_grad(const DScene &S, const DBsdf &B, const 
     BsdfSide ns;
     if (!bsdf_side(S, B.pad, pwi, ns)) return 0.f;
     const DBsdf &N = S.bsdfs[ns.index];
-    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps);
     float g[6];
-    const float fn = bsdf_weighted_value_dir(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), A, g);
+    const float fn = bsdf_weighted_value_dir<TYPES>(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), A, g);
     g[2] *= ns.wo_sign; g[5] *= ns.wo_sign;          /* a nested `twosided` mirrored wi'.z and wo'.z by the same sign */
     /* the shadow term 2 / (1 + sqrt(1 + alpha2 tan^2(wo))), alpha2 = min(tan^2(n) / 8, 1): it depends on the height map through n.z alone */
     float sh = 1.f, dsh_dnz = 0.f;

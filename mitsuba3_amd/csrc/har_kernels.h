@@ -207,6 +207,7 @@ void launch_api_bsdf_eval_pdf_si(hipStream_t s, const DScene &S, uint32_t bsdf, 
                                  const uint8_t *active, float *value, float *pdf);
 void launch_api_bsdf_sample_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom,
                                const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp);
+void launch_api_bsdf_alpha(hipStream_t s, const DScene &S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v);
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf);
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,

@@ -1059,6 +1059,29 @@ __device__ __forceinline__ void bump_texel_commit(const DScene &S, float *const 
         wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? ch * w[k] : Vec3(0.f), on);
     }
 }
+/* s = d L / d alpha_u (`axis` 0) or d alpha_v (1) of a vertex on roughconductor record `rec`, whose roughness on that axis is the bitmap DBsdf::table / ::pad names,
+ * deposited in that bitmap's gradient buffer through the transpose of Texture::eval_1: the four bilinear tap weights (a nearest map: one tap of weight 1) times the
+ * luminance coefficient of the channel, or channel 0 of a one-channel map.  A lookup at or below Microfacet's clamp deposits nothing: d max(alpha, 1e-4) / d alpha = 0
+ * there (the derivative AT the clamp is unpinned, docs/parity.md).  Called by whole waves; lanes aimed at the same texel are pre-reduced -- a roughness map is small
+ * and a wave's vertices share its texels --, as in blend_child_commit. */
+__device__ __forceinline__ void alpha_texel_commit(const DScene &S, float *const *grad_tex, bool pred, uint32_t rec, int axis, float u, float v, float s) {
+    pred = pred && s != 0.f;
+    if (!__ballot(pred)) return;
+    TexTaps taps; float *dst = nullptr; float w[4] = { 0.f, 0.f, 0.f, 0.f }; Vec3 ch(0.f);
+    taps.idx[0] = taps.idx[1] = taps.idx[2] = taps.idx[3] = 0u; taps.w0x = taps.w1x = taps.w0y = taps.w1y = 0.f;
+    if (pred) {
+        const DBsdf &B = S.bsdfs[rec];
+        const int32_t t = axis == 0 ? B.table : (int32_t) B.pad;
+        const bool mono = (B.flags & (axis == 0 ? BF_ALPHA_MONO_U : BF_ALPHA_MONO_V)) != 0u;
+        if (tex_eval_1(S, t, mono, u, v, taps) > 1e-4f) tap_weights(taps, false, w);
+        ch = tex_eval_1_grad_channels(mono);
+        dst = grad_tex[t];
+    }
+    for (int k = 0; k < 4; ++k) {
+        const bool on = pred && w[k] != 0.f;
+        wave_aggregated_add3(on ? dst + 3 * (size_t) taps.idx[k] : nullptr, on ? ch * (w[k] * s) : Vec3(0.f), on);
+    }
+}
 /* ATTR (forward mode of a scene with a `mesh_attribute` texture, k_resolve_forward_attr): the item of a vertex whose record reads an attribute carries the barycentrics
  * (b1, b2) in its uv words (shade_lane), and the face comes from the bounce's replay-cache hit record of the item's lane, `hits` */
 template <bool FWD = false, bool ATTR = false>
@@ -1409,6 +1432,9 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                 const bool lt_nee = visible && R.lt_nee_emitter >= 0;
                 light_texel_commit<TYPES>(S, grad_tex, lt_nee, R.lt_nee_emitter, R.lt_nee_uv[0], R.lt_nee_uv[1], R.contrib_unit * dlr);
             }
+            /* kernels of scenes with a roughness map: groups 0 / 1 (d alpha_u, d alpha_v) of a vertex on a record whose roughness on that axis is a bitmap carry the scalar
+             * sum_c v_c, which goes through the transpose of the lookup into the map's texels (alpha_texel_commit, by whole waves) instead of into grad_extra */
+            float amap_su = 0.f, amap_sv = 0.f;
             if (EXTRA && item_pred) {
                 /* the same two terms as for slot 0 (adjoint_commit_regs), for the five other parameter groups: g = dL * ([visible] d Lr_dir / d theta
                  * + [path continues] L * (d f / d theta) / f), with L already reduced by this vertex's Lr_dir */
@@ -1418,9 +1444,22 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
                     if (R.x_ind) v = v + Vec3(L.x * R.x_rel[g].x, L.y * R.x_rel[g].y, L.z * R.x_rel[g].z);
                     v = v * Vec3(dl.x, dl.y, dl.z);
                     if (v.x == 0.f && v.y == 0.f && v.z == 0.f) continue;
+                    if ((TYPES & HAR_SCENE_ALPHAMAP) != 0u && g < 2) {
+                        const DBsdf &XB = S.bsdfs[R.bsdf];
+                        if (XB.type == BSDF_ROUGHCONDUCTOR && (XB.flags & BF_ALPHA_TEX) && (g == 0 ? XB.table : (int32_t) XB.pad) >= 0) {
+                            if (g == 0) amap_su = (v.x + v.y) + v.z; else amap_sv = (v.x + v.y) + v.z;
+                            continue;
+                        }
+                    }
                     if (R.bsdf < HAR_LDS_EXTRA_BSDFS) { float *a = xacc + 15 * R.bsdf + 3 * g; atomicAdd(a, v.x); atomicAdd(a + 1, v.y); atomicAdd(a + 2, v.z); }
                     else { float *a = grad_extra + 15 * (size_t) R.bsdf + 3 * g; atomicAdd(a, v.x); atomicAdd(a + 1, v.y); atomicAdd(a + 2, v.z); }
                 }
+            }
+            if (EXTRA && (TYPES & HAR_SCENE_ALPHAMAP) != 0u) {
+                /* an isotropic map (the same texture on both axes) receives the sum of the two groups in one deposit */
+                const bool iso = (amap_su != 0.f || amap_sv != 0.f) && S.bsdfs[R.bsdf].table == (int32_t) S.bsdfs[R.bsdf].pad;
+                alpha_texel_commit(S, grad_tex, amap_su != 0.f || (iso && amap_sv != 0.f), R.bsdf, 0, R.uv_x, R.uv_y, iso ? amap_su + amap_sv : amap_su);
+                alpha_texel_commit(S, grad_tex, amap_sv != 0.f && !iso, R.bsdf, 1, R.uv_x, R.uv_y, amap_sv);
             }
             if ((TYPES & HAR_SCENE_BLEND) != 0u) {
                 /* a blend vertex: the same two terms for slot 0 of its two nested records, g = dL * ([visible] d Lr_dir / d slot0 + L * (d f / d slot0) / f) with f the
@@ -2388,6 +2427,25 @@ __global__ void k_api_bsdf_sample_bump(DScene S, uint32_t bsdf, BsdfCtx ctx, uin
     if (i >= n) return;
     bsdf_sample_si_lane(S, bsdf, ctx, n, i, wi, uv, s1, s2, geom, !(active && !active[i]), wo, pdf, weight, eta, stype, scomp);
 }
+/* ... of a scene that holds a roughness map (HAR_SCENE_ALPHAMAP): both families of entries over the set that also looks the roughness up (`geom` is read for a bumpmap
+ * record only, which har_bsdf_eval_pdf / har_bsdf_sample refuse: they pass null).  Kernels of their own once more */
+__global__ void k_api_bsdf_eval_pdf_amap(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom, const uint8_t *active, float *value, float *pdf) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_eval_pdf_si_lane<HAR_SCENE_ALPHAMAP>(S, bsdf, ctx, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+}
+__global__ void k_api_bsdf_sample_amap(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom, const uint8_t *active,
+                                       float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP>(S, bsdf, ctx, n, i, wi, uv, s1, s2, geom, !(active && !active[i]), wo, pdf, weight, eta, stype, scomp);
+}
+/* har_bsdf_alpha: the roughness record `bsdf` evaluates at n uv points (bsdf_alpha_lane) */
+__global__ void k_api_bsdf_alpha(DScene S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_alpha_lane(S, bsdf, n, i, uv, alpha_u, alpha_v);
+}
 /* `path` in a scene with a mask record: the radiance of a camera sample that stayed invalid is dropped, dr::select(valid_ray, result, 0) (path.cpp:341-345) */
 __global__ void k_drop_invalid(uint32_t n, const float *valid, float4 *result) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2498,6 +2556,30 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) {
+        /* a scene with a roughconductor record whose roughness is a bitmap: the bumpmap set (the record may sit under or next to blend / mask / normalmap / bumpmap records)
+         * plus the lookup of the roughness at every vertex.  Four shading kernels: forward, prb primal, the in-place adjoint commit, and that commit with the alpha / eta /
+         * k / slot-1 terms (EXTRA), which scatters groups 0 / 1 of a textured record into the map's texels.  No item-writing adjoint: run_chunk refuses those modes.
+         * Two sets, as for a `mesh_attribute` scene: a plain roughconductor over a roughness map -- the feature's main use -- runs the generic set plus the lookup
+         * (HAR_SCENE_ALPHAMAP_LEAN_TYPES) and does not carry the composite code; the EXTRA flavour exists in that set only (backward_range refuses alpha / eta / k gradients
+         * in a scene that also holds a blend / mask / normalmap / bumpmap record) */
+#define HAR_LAUNCH_SHADE_AMAP(T, X) do { \
+        if (X && mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4) && grad_extra) \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true, X>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, grad_extra, no_mq, 0u, tape); \
+        else if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4) && !grad_extra) \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape); \
+        else if (mode == MODE_PATH) \
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags of a scene that also holds a mask record, or null (run_chunk) */, no_mq, 0u, tape); \
+        else if (mode == MODE_PRB_PRIMAL) \
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape); \
+        else { \
+            fprintf(stderr, "hip_ad_rgb: launch_shade: a scene with a roughness map has no shading kernel for mode %d without the in-place commit\n", mode); \
+            abort(); \
+        } } while (0)
+        if (S.bsdf_types & HAR_SCENE_RECORD_BITS) HAR_LAUNCH_SHADE_AMAP(HAR_SCENE_ALPHAMAP_TYPES, false); else HAR_LAUNCH_SHADE_AMAP(HAR_SCENE_ALPHAMAP_LEAN_TYPES, true);
+#undef HAR_LAUNCH_SHADE_AMAP
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_BUMPMAP) {
         /* a scene with a `bumpmap` record: the normalmap set (normalmap, mask and blend records may sit on other meshes) plus the bump frame.  The same three shading
          * kernels as a normalmap scene (below): forward, prb primal and the in-place adjoint commit, which deposits the height map's gradient through the transpose of
@@ -2797,25 +2879,32 @@ void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const u
 }
 void launch_api_bsdf_eval_pdf_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom,
                                  const uint8_t *active, float *value, float *pdf) {
+    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) { hipLaunchKernelGGL(k_api_bsdf_eval_pdf_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf); return; }
     hipLaunchKernelGGL(k_api_bsdf_eval_pdf_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf);
 }
 void launch_api_bsdf_sample_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom,
                                const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) { hipLaunchKernelGGL(k_api_bsdf_sample_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp); return; }
     hipLaunchKernelGGL(k_api_bsdf_sample_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp);
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {
-    if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
+    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, nullptr, active, value, pdf);
+    else if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else hipLaunchKernelGGL(k_api_bsdf_eval_pdf<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
 }
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
-    if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_sample_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_sample_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, nullptr, active, wo, pdf, weight, eta, stype, scomp);
+    else if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_sample_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_sample_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else hipLaunchKernelGGL(k_api_bsdf_sample<false>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
+}
+void launch_api_bsdf_alpha(hipStream_t s, const DScene &S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v) {
+    hipLaunchKernelGGL(k_api_bsdf_alpha, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, n, uv, alpha_u, alpha_v);
 }
 void launch_api_sensor_ray(hipStream_t s, const DSensor &C, uint32_t n, const float *px, const float *py, const float *ax, const float *ay, float *o, float *d, float *maxt) {
     hipLaunchKernelGGL(k_api_sensor_ray, dim3(blocks_for(n)), dim3(kBlock), 0, s, C, n, px, py, ax, ay, o, d, maxt);

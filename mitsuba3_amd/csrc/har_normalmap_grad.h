@@ -19,6 +19,7 @@ namespace har {
 
 /* F = sum_c A_c value_c(wi, wo) of normalmap record B for the looked-up colour c, and dc[k] = dF / d c_k.  wi, wo: local directions of the vertex as the record sees
  * them (an outer `twosided` has folded them already: the fold does not depend on c).  (u, v): the vertex's texture coordinates, for the nested record's own colours. */
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_ALPHAMAP bit is read: the nested record may carry a roughness map) */
 HAR_HD float normalmap_weighted_value_grad(const DScene &S, const DBsdf &B, Vec3 c, Vec3 wi, Vec3 wo, float u, float v, Vec3 A, float dc[3]) {
     dc[0] = dc[1] = dc[2] = 0.f;
     /* forward, as normalmap_frame (har_scene.h) */
@@ -35,9 +36,9 @@ HAR_HD float normalmap_weighted_value_grad(const DScene &S, const DBsdf &B, Vec3
     BsdfSide ns;
     if (!bsdf_side(S, B.pad, pwi, ns)) return 0.f;
     const DBsdf &N = S.bsdfs[ns.index];
-    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps);
     float g[6];
-    const float fn = bsdf_weighted_value_dir(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), A, g);
+    const float fn = bsdf_weighted_value_dir<TYPES>(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), A, g);
     g[2] *= ns.wo_sign; g[5] *= ns.wo_sign;          /* a nested `twosided` mirrored wi'.z and wo'.z by the same sign */
     /* the shadow term 2 / (1 + sqrt(1 + alpha2 tan^2(wo))), alpha2 = min(tan^2(n) / 8, 1), tan^2(v) = max(1 - v.z^2, 0) / v.z^2: it depends on c through n.z alone */
     float sh = 1.f, dsh_dnz = 0.f;

@@ -259,7 +259,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     else side_ok = bsdf_side(S, M.bsdf, si.wi, side);
     const DBsdf B = S.bsdfs[side.index];
     TexTaps taps;
-    const BsdfInputs bin = bsdf_inputs(S, B, si.uv_x, si.uv_y, taps, aa);
+    const BsdfInputs bin = bsdf_inputs<TYPES>(S, B, si.uv_x, si.uv_y, taps, aa);          /* (kernels of scenes with a roughness map: the record's looked-up alpha as well) */
 
     /* ---- emitter sampling (path.cpp:238-258, prb.py:163-175; scene.cpp:316-366).  The two samples are drawn by
      * every active lane; only BSDFs with a Smooth lobe use them (path.cpp:237, prb.py:169) */
@@ -374,7 +374,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                     const float wk[3] = { w.x, w.y, w.z };
                     for (int k = 0; k < 3; ++k) {
                         float dc[3];
-                        normalmap_weighted_value_grad(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dc);
+                        normalmap_weighted_value_grad<TYPES>(S, B, bin.slot0, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dc);
                         R.nm_dir[k] = Vec3(dc[0], dc[1], dc[2]);
                     }
                 }
@@ -384,12 +384,12 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                     const float wk[3] = { w.x, w.y, w.z };
                     for (int k = 0; k < 3; ++k) {
                         float dg[2];
-                        bumpmap_weighted_value_grad(S, B, bgeom, bgeom.gx, bgeom.gy, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dg);
+                        bumpmap_weighted_value_grad<TYPES>(S, B, bgeom, bgeom.gx, bgeom.gy, side.wi, wo_f, si.uv_x, si.uv_y, Vec3(k == 0 ? wk[0] : 0.f, k == 1 ? wk[1] : 0.f, k == 2 ? wk[2] : 0.f), dg);
                         R.nm_dir[k] = Vec3(dg[0], dg[1], 0.f);
                     }
                 }
                 if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
-                    BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok, wo_em, x);
+                    BsdfEvalExtra x; bsdf_eval_extra<TYPES>(S, side, bin, side_ok, wo_em, x);
                     const Vec3 w = (st.throughput * mis_em) * em_weight;
                     R.x_dir[0] = w * x.d_alpha_u; R.x_dir[1] = w * x.d_alpha_v; R.x_dir[2] = w * x.d_eta; R.x_dir[3] = w * x.d_k; R.x_dir[4] = w * ev.d_slot1;
                 }
@@ -471,7 +471,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
          * (the face comes from the replay cache, k_resolve_forward_attr) */
         if ((TYPES & HAR_SCENE_ATTR) != 0u && (P.flags & HAR_SHADE_FORWARD_MODE) && B.texture >= 0 && (S.textures[B.texture].mode & HAR_TEX_ATTRIBUTE)) { R.uv_x = addr.b1; R.uv_y = addr.b2; }
         if (EXTRA && TYPES != HAR_BSDF_ONLY_DIFFUSE) {
-            BsdfEvalExtra x; bsdf_eval_extra(S, side, bin, side_ok && alive, wo, x);
+            BsdfEvalExtra x; bsdf_eval_extra<TYPES>(S, side, bin, side_ok && alive, wo, x);
             const Vec3 dv[5] = { x.d_alpha_u, x.d_alpha_v, x.d_eta, x.d_k, e2.d_slot1 };
             R.x_ind = false;
             for (int g = 0; g < 5; ++g) {

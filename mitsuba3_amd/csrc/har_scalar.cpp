@@ -67,6 +67,7 @@ struct BoundScene {
         S.env_emitter = hs.env_emitter;
         S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
         for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) S.bsdf_types |= HAR_SCENE_ATTR;
+        for (const DBsdf &b : hs.bsdfs) if (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX)) S.bsdf_types |= HAR_SCENE_ALPHAMAP;
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
         hs.bind_tables(S, hs.emitter_distr.data());
         if (hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) S.bsdf_types |= HAR_SCENE_ENVMAP;
@@ -119,7 +120,8 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         if (stats) { stats->vertices++; stats->closest_rays++; }   /* one loop iteration of PathIntegrator::sample: what the wavefront's bounce counters add up to */
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
-        if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
+        if (S.bsdf_types & HAR_SCENE_ALPHAMAP) shade_lane<MODE_PATH, HAR_SCENE_ALPHAMAP_TYPES>(S, P, st, hit, R);      /* a roughness map: the bumpmap set plus the lookup (no `mesh_attribute` texture next to it) */
+        else if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
         else if (S.bsdf_types & HAR_SCENE_BUMPMAP) shade_lane<MODE_PATH, HAR_SCENE_BUMPMAP_TYPES>(S, P, st, hit, R);      /* ... with a `bumpmap` record the bump frame as well */
         else if (S.bsdf_types & HAR_SCENE_NORMALMAP) shade_lane<MODE_PATH, HAR_SCENE_NORMALMAP_TYPES>(S, P, st, hit, R);      /* ... with a `normalmap` record the perturbed and the tangent frames */
         else shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
@@ -355,7 +357,7 @@ extern "C" int har_normalmap_grad_host(const HarSceneDesc *desc, uint32_t bsdf, 
             BsdfSide side;
             if (bsdf_side(S, bsdf, Vec3(wi[i], wi[i1], wi[i2]), side)) {
                 TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[i1], taps);
-                f = normalmap_weighted_value_grad(S, S.bsdfs[side.index], in.slot0, side.wi, Vec3(wo[i], wo[i1], wo[i2] * side.wo_sign), uv[i], uv[i1], Vec3(A[i], A[i1], A[i2]), dc);
+                f = normalmap_weighted_value_grad<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], in.slot0, side.wi, Vec3(wo[i], wo[i1], wo[i2] * side.wo_sign), uv[i], uv[i1], Vec3(A[i], A[i1], A[i2]), dc);
             }
             if (value) value[i] = f;
             grad[i] = dc[0]; grad[i1] = dc[1]; grad[i2] = dc[2];
@@ -380,7 +382,7 @@ extern "C" int har_bsdf_eval_pdf_si_host(const HarSceneDesc *desc, uint32_t bsdf
         if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
         if (n == 0) return 0;
         if (!wi || !uv || !wo || !geom) return har_set_error("null input arrays");
-        for (uint32_t i = 0; i < n; ++i) bsdf_eval_pdf_si_lane(B.ds, bsdf, c, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+        for (uint32_t i = 0; i < n; ++i) bsdf_eval_pdf_si_lane<HAR_SCENE_ALPHAMAP>(B.ds, bsdf, c, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_eval_pdf_si_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_eval_pdf_si_host: ") + ex.what()); }
@@ -399,7 +401,7 @@ extern "C" int har_bsdf_sample_si_host(const HarSceneDesc *desc, uint32_t bsdf, 
         if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
         if (n == 0) return 0;
         if (!wi || !uv || !sample2 || !geom || !wo || !pdf || !weight) return har_set_error("null input / output arrays");
-        for (uint32_t i = 0; i < n; ++i) bsdf_sample_si_lane(B.ds, bsdf, c, n, i, wi, uv, sample1, sample2, geom, !(active && !active[i]), wo, pdf, weight, eta, sampled_type, sampled_component);
+        for (uint32_t i = 0; i < n; ++i) bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP>(B.ds, bsdf, c, n, i, wi, uv, sample1, sample2, geom, !(active && !active[i]), wo, pdf, weight, eta, sampled_type, sampled_component);
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_sample_si_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_si_host: ") + ex.what()); }
@@ -558,8 +560,8 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
             BsdfEval ev; ev.value = Vec3(0.f); ev.pdf = 0.f;
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
-                TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                TexTaps taps; const BsdfInputs in = bsdf_inputs<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);          /* (the host entries always carry the roughness lookup) */
+                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             if (value) { value[i] = ev.value.x; value[n + i] = ev.value.y; value[2 * (size_t) n + i] = ev.value.z; }
             if (pdf) pdf[i] = ev.pdf;
@@ -586,8 +588,8 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
             BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
-                TexTaps taps; const BsdfInputs in = bsdf_inputs(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                TexTaps taps; const BsdfInputs in = bsdf_inputs<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
+                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
             weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
@@ -598,6 +600,50 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_sample_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_host: ") + ex.what()); }
+}
+
+/* The looked-up roughness of record `bsdf` at n uv points (uv 2 x n) on the host: bsdf_alpha_lane (har_scene.h), the function k_api_bsdf_alpha runs per lane -- alpha_u,
+ * alpha_v after the lookup and before Microfacet's max(., 1e-4); the constants of a record without a roughness map.  The twin of har_bsdf_alpha. */
+extern "C" int har_bsdf_alpha_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (n == 0) return 0;
+        if (!uv || !alpha_u || !alpha_v) return har_set_error("null uv / alpha_u / alpha_v");
+        for (uint32_t i = 0; i < n; ++i) bsdf_alpha_lane(B.ds, bsdf, n, i, uv, alpha_u, alpha_v);
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_alpha_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_alpha_host: ") + ex.what()); }
+}
+
+/* d value / d {alpha_u, alpha_v, eta, k} of record `bsdf` on the host (bsdf_eval_extra, har_scene.h: what the EXTRA shading kernels form at a vertex), n tuples (wi 3 x n,
+ * uv 2 x n, wo 3 x n) under the default context; a `twosided` record is resolved, a roughness map is looked up at uv.  d_alpha_u, d_alpha_v, d_eta, d_k: 3 x n each. */
+extern "C" int har_bsdf_eval_extra_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi, const float *uv, const float *wo,
+                                        float *d_alpha_u, float *d_alpha_v, float *d_eta, float *d_k) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (bsdf >= B.hs.bsdfs.size()) return har_set_error("invalid bsdf index");
+        if (B.hs.bsdfs[bsdf].type >= BSDF_TYPE_COUNT) return har_set_error("har_bsdf_eval_extra_host: a plain BSDF model (possibly twosided) is expected");
+        if (n == 0) return 0;
+        if (!wi || !uv || !wo || !d_alpha_u || !d_alpha_v || !d_eta || !d_k) return har_set_error("null input / output arrays");
+        const DScene &S = B.ds;
+        for (uint32_t i = 0; i < n; ++i) {
+            const size_t i1 = n + (size_t) i, i2 = 2 * (size_t) n + i;
+            BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[i1], wi[i2]), side);
+            TexTaps taps; const BsdfInputs in = bsdf_inputs<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], uv[i], uv[i1], taps);
+            BsdfEvalExtra x; bsdf_eval_extra<HAR_BSDF_ALL_TYPES | HAR_SCENE_ALPHAMAP>(S, side, in, ok, Vec3(wo[i], wo[i1], wo[i2]), x);
+            const Vec3 v[4] = { x.d_alpha_u, x.d_alpha_v, x.d_eta, x.d_k }; float *const out[4] = { d_alpha_u, d_alpha_v, d_eta, d_k };
+            for (int k = 0; k < 4; ++k) { out[k][i] = v[k].x; out[k][i1] = v[k].y; out[k][i2] = v[k].z; }
+        }
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_eval_extra_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_eval_extra_host: ") + ex.what()); }
 }
 
 /* BatchSensor::sample_ray (src/sensors/batch.cpp:132-159) on the host: batch_sample_ray (har_scene.h) -- the function k_raygen_batch runs per lane -- over the children

@@ -490,12 +490,36 @@ HAR_HD Vec3 bsdf_reflectance(const DScene &S, const DBsdf &B, float u, float v, 
     if (tex_taps_at(S, T, u, v, aa, taps)) return attr_fetch(T, taps);
     return tex_fetch(T, taps);
 }
-/* evaluated colour parameters of a BSDF record at (u, v) */
+/* Texture::eval_1 of bitmap `tex` at (u, v) (bitmap.cpp:523-541): the channel of a one-channel bitmap (`mono`: stored three times, channel 0 is read), luminance() of the
+ * interpolated texel of a three-channel one -- the arithmetic of blend_weight below, without its clip.  `l`: the taps of the lookup (the adjoint scatters through them) */
+HAR_HD float tex_eval_1(const DScene &S, int32_t tex, bool mono, float u, float v, TexTaps &l) {
+    const DTexture T = S.textures[tex];
+    tex_taps(T, u, v, l);
+    const Vec3 c = tex_fetch(T, l);
+    return mono ? c.x : c.x * 0.212671f + c.y * 0.715160f + c.z * 0.072169f;
+}
+/* the roughness of a record at (u, v), before Microfacet's max(., 1e-4) (roughconductor.cpp:244-245: m_alpha_u->eval_1(si), m_alpha_v->eval_1(si)): the constants of the
+ * record, or -- a roughconductor with BF_ALPHA_TEX -- the lookup of the map(s) DBsdf::table / ::pad name; ONE lookup for an isotropic map (the same index twice) */
+HAR_HD void bsdf_alpha(const DScene &S, const DBsdf &B, float u, float v, float &au, float &av) {
+    au = B.alpha_u; av = B.alpha_v;
+    if (B.type != BSDF_ROUGHCONDUCTOR || !(B.flags & BF_ALPHA_TEX)) return;
+    const int32_t tu = B.table, tv = (int32_t) B.pad;
+    TexTaps l;
+    if (tu >= 0) au = tex_eval_1(S, tu, (B.flags & BF_ALPHA_MONO_U) != 0u, u, v, l);
+    if (tv >= 0) av = tv == tu ? au : tex_eval_1(S, tv, (B.flags & BF_ALPHA_MONO_V) != 0u, u, v, l);
+}
+/* evaluated colour parameters of a BSDF record at (u, v); TYPES: only the HAR_SCENE_ALPHAMAP bit is read -- the kernels of scenes with a roughness map look the roughness up
+ * here, once per vertex, for sample / eval / pdf alike */
+template <uint32_t TYPES = 0u>
 HAR_HD BsdfInputs bsdf_inputs(const DScene &S, const DBsdf &B, float u, float v, TexTaps &taps, const AttrAddr *aa = nullptr) {
     BsdfInputs in;
     in.slot0 = bsdf_reflectance(S, B, u, v, taps, aa);
     in.slot1 = Vec3(B.r2, B.g2, B.b2);
     in.table = B.table >= 0 ? S.bsdf_tables + B.table : nullptr;      /* (a blend record keeps a record index there: its `table` is never read) */
+    if ((TYPES & HAR_SCENE_ALPHAMAP) != 0u) {
+        if (B.type == BSDF_ROUGHCONDUCTOR) in.table = nullptr;         /* (... and a roughconductor with a roughness map a texture index) */
+        bsdf_alpha(S, B, u, v, in.alpha_u, in.alpha_v);
+    }
     return in;
 }
 
@@ -554,7 +578,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const float k = first ? 1.f - w : w;
         const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps, aa);
         bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, e, ctx2);
         const Vec3 nv = e.value;
         if (cg) cg->d[first ? 0 : 1] = e.d_slot0 * k;
@@ -568,7 +592,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
 #endif
     for (int k = 0; k < 2; ++k) {
         const DBsdf &N = S.bsdfs[child[k]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps, aa);
         BsdfEval ne; bsdf_eval_pdf_one<LEAF, CTX>(N, nin, wi, wo, ne, ctx);
         val[k] = ne.value; pdf[k] = ne.pdf;
         if (cg) cg->d[k] = ne.d_slot0 * (k == 0 ? 1.f - w : w);
@@ -589,7 +613,7 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
         const bool first = ctx.component < n0;
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps, aa);
         bsdf_sample_one<LEAF, CTX>(N, nin, wi, s1, s2x, s2y, bs, ctx2);
         bs.weight = bs.weight * (first ? 1.f - w : w);
         return;
@@ -599,9 +623,9 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
     if (!m0 && !m1) return;
     const DBsdf &Ns = S.bsdfs[child[m0 ? 0 : 1]], &No = S.bsdfs[child[m0 ? 1 : 0]];
     TexTaps taps;
-    const BsdfInputs sin = bsdf_inputs(S, Ns, u, v, taps, aa);
+    const BsdfInputs sin = bsdf_inputs<TYPES>(S, Ns, u, v, taps, aa);
     bsdf_sample_one<LEAF, CTX>(Ns, sin, wi, m0 ? (s1 - w) / (1.f - w) : s1 / w, s2x, s2y, bs, ctx);
-    const BsdfInputs oin = bsdf_inputs(S, No, u, v, taps, aa);
+    const BsdfInputs oin = bsdf_inputs<TYPES>(S, No, u, v, taps, aa);
     BsdfEval eo; bsdf_eval_pdf_one<LEAF, CTX>(No, oin, wi, bs.wo, eo, ctx);
     /* :138-141 / :150-153: weight is nested BSDF 1's share in both branches */
     const float pdf_weighted = m0 ? w * eo.pdf + (1.f - w) * bs.pdf : w * bs.pdf + (1.f - w) * eo.pdf;
@@ -637,7 +661,7 @@ HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in,
     BsdfSide ns;
     if (bsdf_side(S, B.pad, wi, ns)) {
         const DBsdf &N = S.bsdfs[ns.index];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps, aa);
         bsdf_eval_pdf_one<LEAF, CTX>(N, nin, ns.wi, Vec3(wo.x, wo.y, wo.z * ns.wo_sign), ne, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
     }
     e.value = ne.value * o;
@@ -662,7 +686,7 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
         BsdfSide ns;
         if (!bsdf_side(S, B.pad, wi, ns)) return;
         const DBsdf &N = S.bsdfs[ns.index];
-        TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps, aa);
+        TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps, aa);
         bsdf_sample_one<LEAF, CTX>(N, nin, ns.wi, s1 / o, s2x, s2y, bs, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
         bs.wo.z *= ns.wo_sign; bs.pdf *= o;
         return;
@@ -707,7 +731,7 @@ HAR_HD void perturbed_eval_pdf(const DScene &S, const DBsdf &B, const NormalFram
     BsdfSide ns;
     if (!bsdf_side(S, B.pad, pwi, ns)) return;
     const DBsdf &N = S.bsdfs[ns.index];
-    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps);
     BsdfEval ne; bsdf_eval_pdf_one<LEAF, CTX>(N, nin, ns.wi, Vec3(pwo.x, pwo.y, pwo.z * ns.wo_sign), ne, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
     const float shadow = (B.flags & BF_NM_SHADOW) ? normalmap_shadow_terminator(F.n, wo) : 1.f;
     e.value = (B.flags & BF_NM_SHADOW) ? ne.value * shadow : ne.value;
@@ -729,7 +753,7 @@ HAR_HD void perturbed_sample(const DScene &S, const DBsdf &B, const NormalFrame 
     BsdfSide ns;
     if (!bsdf_side(S, B.pad, pwi, ns)) return;
     const DBsdf &N = S.bsdfs[ns.index];
-    TexTaps taps; const BsdfInputs nin = bsdf_inputs(S, N, u, v, taps);
+    TexTaps taps; const BsdfInputs nin = bsdf_inputs<TYPES>(S, N, u, v, taps);
     bsdf_sample_one<LEAF, CTX>(N, nin, ns.wi, s1, s2x, s2y, bs, CTX ? bsdf_side_ctx(S, B.pad, ns, ctx) : ctx);
     bs.wo.z *= ns.wo_sign;
     const bool nonzero = bs.weight.x != 0.f || bs.weight.y != 0.f || bs.weight.z != 0.f;                             /* :146 (a lane of a wavefront: the rest still runs, masked) */
@@ -818,9 +842,10 @@ HAR_HD void bsdf_eval_pdf(const DScene &S, const BsdfSide &side, const BsdfInput
     bsdf_eval_pdf_one<(TYPES & ~HAR_SCENE_RECORD_BITS), CTX>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), e, ctx);
 }
 /* d value / d {alpha, eta, k} of the record serving this side (see bsdf_eval_extra_one) */
+template <uint32_t TYPES = HAR_BSDF_ALL_TYPES>
 HAR_HD void bsdf_eval_extra(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, Vec3 wo, BsdfEvalExtra &x) {
     if (!side_ok) { x.d_alpha_u = Vec3(0.f); x.d_alpha_v = Vec3(0.f); x.d_eta = Vec3(0.f); x.d_k = Vec3(0.f); return; }
-    bsdf_eval_extra_one(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), x);
+    bsdf_eval_extra_one<TYPES>(S.bsdfs[side.index], in, side.wi, Vec3(wo.x, wo.y, wo.z * side.wo_sign), x);
 }
 template <uint32_t TYPES = HAR_BSDF_ALL_TYPES, bool CTX = false>
 HAR_HD void bsdf_sample(const DScene &S, const BsdfSide &side, const BsdfInputs &in, bool side_ok, float s1, float s2x, float s2y, BsdfSample &bs, const BsdfCtx &ctx = BsdfCtx(),
@@ -842,37 +867,45 @@ HAR_HD BumpGeom bump_geom_rows(const DScene &S, const DBsdf &B, uint32_t n, uint
     for (int k = 0; k < 6; ++k) r[k] = Vec3(geom[(3 * k) * (size_t) n + i], geom[(3 * k + 1) * (size_t) n + i], geom[(3 * k + 2) * (size_t) n + i]);
     return bump_geom(S, B, r[0], r[1], r[2], r[3], r[4], r[5], u, v);
 }
+template <uint32_t AMAP = 0u>          /* AMAP = HAR_SCENE_ALPHAMAP: the entries of a scene with a roughness map (kernels of their own; the host twins always) */
 HAR_HD void bsdf_eval_pdf_si_lane(const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, uint32_t i, const float *wi, const float *uv, const float *wo, const float *geom,
                                   bool active, float *value, float *pdf) {
     BsdfEval e; e.value = Vec3(0.f); e.pdf = 0.f;
     if (active) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         const DBsdf &B = S.bsdfs[side.index];
-        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, B, uv[i], uv[n + i], taps);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs<AMAP>(S, B, uv[i], uv[n + i], taps);
         BumpGeom G; const bool bump = B.type == BSDF_BUMPMAP;
         if (bump) G = bump_geom_rows(S, B, n, i, geom, uv[i], uv[n + i]);
-        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i],
+        bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS | AMAP, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), e, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i],
                                                                           nullptr, nullptr, bump ? &G : nullptr);
     }
     if (value) { value[i] = e.value.x; value[n + i] = e.value.y; value[2 * (size_t) n + i] = e.value.z; }
     if (pdf) pdf[i] = e.pdf;
 }
+template <uint32_t AMAP = 0u>
 HAR_HD void bsdf_sample_si_lane(const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, uint32_t i, const float *wi, const float *uv, const float *s1, const float *s2,
                                 const float *geom, bool active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
     BsdfSample b; b.wo = Vec3(0.f); b.pdf = 0.f; b.weight = Vec3(0.f); b.eta = 0.f; b.delta = false; b.type = 0u; b.comp = 0u;
     if (active) {
         BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
         const DBsdf &B = S.bsdfs[side.index];
-        TexTaps taps; const BsdfInputs in = bsdf_inputs(S, B, uv[i], uv[n + i], taps);
+        TexTaps taps; const BsdfInputs in = bsdf_inputs<AMAP>(S, B, uv[i], uv[n + i], taps);
         BumpGeom G; const bool bump = B.type == BSDF_BUMPMAP;
         if (bump) G = bump_geom_rows(S, B, n, i, geom, uv[i], uv[n + i]);
-        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i], nullptr, bump ? &G : nullptr);
+        bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_RECORD_BITS | AMAP, true>(S, side, in, ok, s1 ? s1[i] : 0.f, s2[i], s2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, ctx), uv[i], uv[n + i], nullptr, bump ? &G : nullptr);
     }
     wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
     weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;
     if (eta) eta[i] = b.eta;
     if (stype) stype[i] = b.type;
     if (scomp) scomp[i] = b.comp;
+}
+
+/* One lane of har_bsdf_alpha / har_bsdf_alpha_host: the roughness record `bsdf` itself (no `twosided` side is chosen) evaluates at uv point i, before max(., 1e-4) */
+HAR_HD void bsdf_alpha_lane(const DScene &S, uint32_t bsdf, uint32_t n, uint32_t i, const float *uv, float *alpha_u, float *alpha_v) {
+    float au, av; bsdf_alpha(S, S.bsdfs[bsdf], uv[i], uv[n + i], au, av);
+    alpha_u[i] = au; alpha_v[i] = av;
 }
 
 /* SmoothDiffuse::eval_pdf / sample (src/bsdfs/diffuse.cpp:159-179, 100-124) */

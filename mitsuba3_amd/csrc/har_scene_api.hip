@@ -84,6 +84,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
     D.n_bsdfs = (uint32_t) hs.bsdfs.size(); D.n_insts = (uint32_t) hs.insts.size(); D.n_textures = (uint32_t) hs.textures.size();
     D.env_emitter = hs.env_emitter;
     D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+    for (const DBsdf &b : hs.bsdfs) if (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX)) D.bsdf_types |= HAR_SCENE_ALPHAMAP;      /* a roughness map: the set that also looks the roughness up */
     if (hs.has_envmap || hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) D.bsdf_types |= HAR_SCENE_ENVMAP;
     for (const DEmitter &e : hs.emitters) if (e.type == 7u) D.bsdf_types |= HAR_SCENE_TEXLIGHT;      /* (has_mesh_emitters is set with it: the generic emitter kernels + the texel-distribution code) */
     for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) D.bsdf_types |= HAR_SCENE_ATTR;      /* a `mesh_attribute` texture: the widest set that also looks attributes up */
@@ -824,6 +825,14 @@ int har_bsdf_sample_si(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uin
     if (n == 0) return 0;
     if (!wi || !uv || !sample2 || !geom || !wo || !pdf || !weight) return fail("null input / output arrays");
     launch_api_bsdf_sample_si((hipStream_t) stream, S->ds, bsdf, c, n, wi, uv, sample1, sample2, geom, active, wo, pdf, weight, eta, sampled_type, sampled_component);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int har_bsdf_alpha(HarScene S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v, void *stream) {
+    if (!S || bsdf >= S->hs.bsdfs.size()) return fail("invalid bsdf index");
+    if (n == 0) return 0;
+    if (!uv || !alpha_u || !alpha_v) return fail("null uv / alpha_u / alpha_v");
+    launch_api_bsdf_alpha((hipStream_t) stream, S->ds, bsdf, n, uv, alpha_u, alpha_v);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -456,6 +456,19 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             }
             db.pad = (uint32_t) b.nested[0];
         } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH | BF_NM_FLIP | BF_NM_SHADOW);
+        /* a roughness map (roughconductor.cpp:195-198): behind HAR_BSDF_ALPHA_TEX -- and only there -- nested[0] / nested[1] name the bitmaps of alpha_u / alpha_v
+         * (-1: that axis keeps its constant); `table` / `pad` are free in a roughconductor record */
+        if (b.flags & BF_ALPHA_TEX) {
+            if (b.type != BSDF_ROUGHCONDUCTOR) { err = "roughness map: HAR_BSDF_ALPHA_TEX on a record that is not a `roughconductor` (the alpha of every other model, `roughplastic` included, is a float)"; return false; }
+            if (b.nested[0] < 0 && b.nested[1] < 0) { err = "roughness map: HAR_BSDF_ALPHA_TEX is set but neither alpha_u nor alpha_v names a texture"; return false; }
+            for (int k = 0; k < 2; ++k) {
+                if (b.nested[k] < 0) continue;
+                if (b.nested[k] >= (int32_t) d.texture_count) { err = std::string("roughness map: the texture index of ") + (k ? "alpha_v" : "alpha_u") + " is out of range"; return false; }
+                if (d.textures[b.nested[k]].mode & HAR_TEX_MESH_ATTRIBUTE) { err = "roughness map: a `mesh_attribute` texture as alpha is not supported (a `bitmap` is)"; return false; }
+            }
+            if (b.nested[0] == b.nested[1] && ((b.flags & BF_ALPHA_MONO_U) != 0u) != ((b.flags & BF_ALPHA_MONO_V) != 0u)) { err = "roughness map: one bitmap on both axes needs HAR_BSDF_ALPHA_MONO_U and _V set alike"; return false; }
+            db.table = b.nested[0] < 0 ? -1 : b.nested[0]; db.pad = (uint32_t) (b.nested[1] < 0 ? -1 : b.nested[1]);
+        } else db.flags &= ~(uint32_t) (BF_ALPHA_MONO_U | BF_ALPHA_MONO_V);
         hs.bsdfs.push_back(db);
         if (b.type == BSDF_ROUGHPLASTIC) { build_roughplastic_tables(hs, i); update_roughplastic_sampling_weight(hs, i); }
         if (b.type == BSDF_PLASTIC) {                       /* SmoothPlastic::parameters_changed (plastic.cpp:188-205) */
@@ -475,6 +488,9 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
         /* a `bumpmap` record sets no BSDFFlags::NormalMapped (bumpmap.cpp:124-128): the meshes under it keep the frame they have, with or without normals and texcoords */
         bool any_bump = false; for (const DBsdf &b : hs.bsdfs) any_bump = any_bump || b.type == BSDF_BUMPMAP;
         if (any_bump) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "bumpmap: a scene with a `bumpmap` BSDF and a `mesh_attribute` texture is not supported"; return false; }
+        /* ... and a roughness map: its kernels are the bumpmap set plus the lookup, which does not look attributes up */
+        bool any_amap = false; for (const DBsdf &b : hs.bsdfs) any_amap = any_amap || (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX) != 0u);
+        if (any_amap) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "roughness map: a scene with a bitmap `alpha` and a `mesh_attribute` texture is not supported"; return false; }
         for (uint32_t m = 0; m < d.mesh_count; ++m) {
             DMesh &dm = hs.meshes[m];
             const bool under = hs.bsdfs[dm.bsdf].type == BSDF_NORMALMAP;
