@@ -95,6 +95,21 @@ typedef struct HarInstance {
  * holds a `mesh_attribute` texture are refused.  Gradients (`prb`): the height map's texels -- d / d grad_uv by a reverse sweep through the frame, the nested model's
  * directional partials and the shadow term, scattered through the transpose of eval_1_grad --, the nested leaf record's colour slot 0 in its own; the refusals of a
  * normalmap scene hold.  har_bsdf_eval_pdf / har_bsdf_sample refuse such a record: its frame reads the interaction (har_bsdf_eval_pdf_si / har_bsdf_sample_si).
+ *   type 10 thindielectric (src/bsdfs/thindielectric.cpp)  slot0 = specular_transmittance: a constant rgb or a bitmap (any filter, wrap mode and to_uv); slot1 =
+ *                          specular_reflectance: a constant; eta as for `dielectric`.  A colour that was not given is stored as (1, 1, 1)
+ * A thindielectric record is a LEAF model with two components: 0 = delta reflection (wo = reflect(wi)), 1 = a NULL lobe (wo = -wi, sampled_type 0x1, eta 1: nothing
+ * refracts).  r' = r * (2 / (1 + r)) with r = fresnel(|cos theta_i|, eta) accounts for the internal reflections; sample1 <= r' reflects with weight slot1 and pdf r',
+ * otherwise the ray passes with weight slot0 and pdf 1 - r' (a context that enables one of the two takes it with pdf 1 and r' / 1 - r' in the weight).  eval and pdf are
+ * zero for every direction, so `prb` produces no gradient for the record's own parameters (the gradient rows of the record stay zero); parameters of the surfaces
+ * behind and in front of the pane are differentiated through it.  `path` counts a camera sample as valid when a non-null lobe was sampled at one of its vertices,
+ * as in a scene with a mask record.  Shadow rays are occluded by the pane (Scene::ray_test).  The record may be nested[0] of a mask record (the null lobe of the
+ * mask is then component 2) and either child of a blendbsdf record.  Refused: HAR_BSDF_TWOSIDED on it, or the record as the `back` of a twosided one ("Only materials
+ * without a transmission component can be nested"), also through a twosided blend record; the record as nested[0] of a normalmap / bumpmap record; a `mesh_attribute`
+ * texture in slot 0; HAR_BSDF_ALPHA_TEX on it; a scene that also holds a `mesh_attribute` texture.  A scene with such a record runs shading kernels of its own and takes
+ * the replay-cache route with the in-place commit for every backward pass (max_depth <= 12).  A pane among plain BSDF models (no blendbsdf / mask / normalmap / bumpmap
+ * record, no roughness map) keeps har_render_forward and the alpha / eta / k / slot-1 gradients of the rough models on the other surfaces
+ * (har_integrator_set_grad_bsdf_params); next to one of those records both are refused, as they are without the pane.  Vertex-position and instance gradients and
+ * har_integrator_set_material_queues are refused for every scene that holds a pane.
  * flags: bit0 twosided (src/bsdfs/twosided.cpp; `back` = record used for the back side, -1 = the same one),
  *        bit1 GGX distribution (else Beckmann), bit2 sample_visible, bit3 plastic / roughplastic `nonlinear`. */
 #define HAR_BSDF_DIFFUSE        0
@@ -107,6 +122,7 @@ typedef struct HarInstance {
 #define HAR_BSDF_MASK           7
 #define HAR_BSDF_NORMALMAP      8
 #define HAR_BSDF_BUMPMAP        9
+#define HAR_BSDF_THINDIELECTRIC 10
 #define HAR_BSDF_TWOSIDED       1u
 #define HAR_BSDF_GGX            2u
 #define HAR_BSDF_SAMPLE_VISIBLE 4u

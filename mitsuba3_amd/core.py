@@ -596,7 +596,7 @@ def _cube(props):
 # `rgb` is the dict form of a colour property, which the reference's loader turns into an `srgb` texture object (src/core/python/parser.cpp) -- a texture here.
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
-    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf', 'bumpmap': 'bsdf',
+    'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'thindielectric': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf', 'bumpmap': 'bsdf',
     'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
@@ -1144,6 +1144,7 @@ def _rgb_value(v, default, bounded=True, uniform=None):
 # the properties each BSDF plugin queries (src/bsdfs/*.cpp constructors; MicrofacetDistribution(props), microfacet.h:103-144)
 _BSDF_PROPS = {'diffuse': ('reflectance',),
                'dielectric': ('int_ior', 'ext_ior', 'specular_reflectance', 'specular_transmittance'),
+               'thindielectric': ('int_ior', 'ext_ior', 'specular_reflectance', 'specular_transmittance'),
                'conductor': ('material', 'eta', 'k', 'specular_reflectance'),
                'plastic': ('int_ior', 'ext_ior', 'diffuse_reflectance', 'specular_reflectance', 'nonlinear'),
                'roughconductor': ('material', 'eta', 'k', 'distribution', 'sample_visible', 'alpha', 'alpha_u', 'alpha_v', 'specular_reflectance'),
@@ -1151,16 +1152,19 @@ _BSDF_PROPS = {'diffuse': ('reflectance',),
 # BitmapTexture(props) (src/textures/bitmap.cpp:175-260); `raw` only silences a range warning for float data in RGB variants, `accel` picks Dr.Jit's texture
 # hardware path on CUDA (no effect on values), `format` = the storage type of the texels ("auto" / "variant" / "fp16": this path keeps float32)
 _BITMAP_PROPS = ('filename', 'bitmap', 'data', 'to_uv', 'raw', 'accel', 'filter_type', 'wrap_mode', 'format')
-BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8, 'bumpmap': 9}
+BSDF_TYPES = {'diffuse': 0, 'dielectric': 1, 'roughconductor': 2, 'roughplastic': 3, 'conductor': 4, 'plastic': 5, 'blendbsdf': 6, 'mask': 7, 'normalmap': 8, 'bumpmap': 9, 'thindielectric': 10}
 _NESTING_BSDFS = ('blendbsdf', 'mask', 'normalmap', 'bumpmap')          # records that name nested records: built by the plugin factory
 _MONO_TEX_BSDFS = ('blendbsdf', 'mask', 'bumpmap', 'alphamap')          # records whose bitmap may have ONE channel (stored three times; `weight_channels`); 'alphamap': a roughconductor's roughness map (_AlphaMap)
+_THIN_PARAMS = ('thin_ior', 'thin_r')          # `eta` and `specular_reflectance` of a `thindielectric`: differentiable in the reference's traverse(), and `prb` gives zero for them (the model's eval() is zero: prb.py:288-297)
 _NOGRAD_PARAMS = ('ior', 'scale')          # non-colour parameters that are updatable and carry no gradient (ParamFlags::NonDifferentiable)
 _WEIGHTED_BSDFS = ('blendbsdf', 'mask')          # records whose slot 0 is a scalar texture (Texture::eval_1): the blend weight, the mask opacity
 _LUMINANCE = (0.212671, 0.715160, 0.072169)          # luminance() of an RGB colour (include/mitsuba/core/spectrum.h:439-442)
 # (parameter name of slot 0, default), (parameter name of slot 1, default)
 _BSDF_SLOTS = {'diffuse': (('reflectance', 0.5), None), 'dielectric': (('specular_reflectance', 1.0), ('specular_transmittance', 1.0)),
                'roughconductor': (('specular_reflectance', 1.0), None), 'roughplastic': (('diffuse_reflectance', 0.5), ('specular_reflectance', 1.0)),
-               'conductor': (('specular_reflectance', 1.0), None), 'plastic': (('diffuse_reflectance', 0.5), ('specular_reflectance', 1.0))}
+               'conductor': (('specular_reflectance', 1.0), None), 'plastic': (('diffuse_reflectance', 0.5), ('specular_reflectance', 1.0)),
+               # HAR_BSDF_THINDIELECTRIC: slot 0 is the TRANSMITTANCE (it may be a bitmap: stained glass), slot 1 the reflectance (a constant)
+               'thindielectric': (('specular_transmittance', 1.0), ('specular_reflectance', 1.0))}
 
 
 def _bitmap_from_props(refl):
@@ -1283,6 +1287,14 @@ class BSDF:
         (name0, def0), slot1 = _BSDF_SLOTS[self.kind]
         self.slot0_name = name0; self.slot1_name = slot1[0] if slot1 else None
         refl = props.get(name0, {'type': 'rgb', 'value': [def0] * 3})
+        # thindielectric.cpp:119-122: the two colours are null members when the property is absent -- traverse() shows them only when they were given
+        self.given = tuple(n for n in (name0, self.slot1_name) if n is not None and n in props) if self.kind == 'thindielectric' else None
+        if self.kind == 'thindielectric':
+            if isinstance(refl, dict) and refl.get('type') == 'mesh_attribute':
+                raise RuntimeError("thindielectric: a `mesh_attribute` texture as `specular_transmittance` is not supported in hip_ad_rgb (an rgb value or a `bitmap` is)")
+            r1 = props.get(self.slot1_name)
+            if isinstance(r1, dict) and r1.get('type') != 'rgb':
+                raise RuntimeError("thindielectric: `specular_reflectance` is a `%s`: slot 1 is constant in this variant (an rgb value; `specular_transmittance` may be a `bitmap`)" % r1.get('type'))
         if isinstance(refl, (int, float)):
             refl = {'type': 'rgb', 'value': [refl] * 3}
         self.texture = None; self.tex_mode = 0; self.tex_to_uv = None
@@ -1326,8 +1338,8 @@ class BSDF:
                     raise RuntimeError("Should specify either (eta, k) or material, not both.")
                 raise RuntimeError("%s: `material` presets need the spectral IOR data files, give (eta, k) instead" % self.kind)
             self.eta_c = _rgb_value(props.get('eta'), 0.0, bounded=False); self.k_c = _rgb_value(props.get('k'), 1.0, bounded=False)
-        if self.kind in ('dielectric', 'roughplastic', 'plastic'):
-            int_ior = _lookup_ior(props, 'int_ior', 'bk7' if self.kind == 'dielectric' else 'polypropylene')
+        if self.kind in ('dielectric', 'thindielectric', 'roughplastic', 'plastic'):
+            int_ior = _lookup_ior(props, 'int_ior', 'bk7' if self.kind in ('dielectric', 'thindielectric') else 'polypropylene')
             ext_ior = _lookup_ior(props, 'ext_ior', 'air')
             if int_ior < 0 or ext_ior < 0 or (self.kind == 'roughplastic' and int_ior == ext_ior):
                 raise RuntimeError("The interior and exterior indices of refraction must be positive" + (" and differ!" if self.kind == 'roughplastic' else "!"))
@@ -1419,6 +1431,7 @@ class BSDF:
         """BSDFFlags of the components of this plugin without a `twosided` wrapper (the constructors of src/bsdfs/*.cpp)"""
         F = BSDFFlags; fs = F.FrontSide
         return {'diffuse': [F.DiffuseReflection | fs], 'dielectric': [F.DeltaReflection | fs | F.BackSide, F.DeltaTransmission | fs | F.BackSide | F.NonSymmetric],
+                'thindielectric': [F.DeltaReflection | fs | F.BackSide, F.Null | fs | F.BackSide],          # thindielectric.cpp:124-127
                 # (Anisotropic: m_alpha_u != m_alpha_v compares the texture OBJECTS, roughconductor.cpp:205 -- with a roughness map, whether the two were given separately)
                 'roughconductor': [F.GlossyReflection | fs | (F.Anisotropic if (self.anisotropic if getattr(self, 'alpha_maps', None) else self.alpha_u != self.alpha_v) else 0)],
                 'roughplastic': [F.GlossyReflection | fs, F.DiffuseReflection | fs], 'conductor': [F.DeltaReflection | fs], 'plastic': [F.DeltaReflection | fs, F.DiffuseReflection | fs]}[self.kind]
@@ -1739,7 +1752,7 @@ def _mk_blendbsdf(props, named, key):
 
 def _transmits(b):
     """does the BSDF have a transmission lobe (what `twosided` refuses, twosided.cpp:79-83)"""
-    return b.kind == 'dielectric' or (b.kind == 'blendbsdf' and any(c.kind == 'dielectric' for c in b.nested)) or b.kind == 'mask' or (b.kind in ('normalmap', 'bumpmap') and _transmits(b.nested[0]))      # (BSDFFlags::Null is part of BSDFFlags::Transmission; a normalmap has its nested BSDF's lobes)
+    return b.kind in ('dielectric', 'thindielectric') or (b.kind == 'blendbsdf' and any(c.kind in ('dielectric', 'thindielectric') for c in b.nested)) or b.kind == 'mask' or (b.kind in ('normalmap', 'bumpmap') and _transmits(b.nested[0]))      # (BSDFFlags::Null is part of BSDFFlags::Transmission; a normalmap has its nested BSDF's lobes)
 
 
 def _mk_twosided(props, named, key):
@@ -2245,11 +2258,16 @@ class Integrator:
         out = scene._gradients(g_refl, g_tex, g_emit if self.emitter_gradients else None, alpha_maps=g_extra is not None)
         if g_extra is not None:
             for k, (what, b) in scene._bsdf_param_keys().items():
-                if what in _NOGRAD_PARAMS:
-                    continue                  # (no gradient w.r.t. the scalar index of refraction or a bump map's `scale`)
+                if what in _NOGRAD_PARAMS or what in _THIN_PARAMS:
+                    continue                  # (no gradient w.r.t. the scalar index of refraction or a bump map's `scale`; a pane's own entries: below)
                 rec = g_extra[b.index]
                 out[k] = {"alpha": rec[0:6].sum().reshape(1), "alpha_u": rec[0:3].sum().reshape(1), "alpha_v": rec[3:6].sum().reshape(1),
                           "eta": rec[6:9], "k": rec[9:12], "slot1": rec[12:15]}[what]
+        # a `thindielectric`'s own entries: eval() is zero for every direction, so prb.py:288-297 forms relative_grad(0) -- zeros of the parameter's shape, as the reference
+        # returns for every delta model (its colour in slot 0 comes back as the untouched row / bitmap of the gradient buffers)
+        for k, (what, b) in scene._bsdf_param_keys().items():
+            if what in _THIN_PARAMS:
+                out[k] = torch.zeros(1 if what == "thin_ior" else 3, dtype=torch.float32, device=dev)
         if self.light_texel_gradients:            # the light's bitmap is a texture of the scene like any other: its gradient sits in its entry of grad_textures
             for k, (kind, i) in scene._pose_keys().items():
                 if kind == "emitter_tex":
@@ -2998,7 +3016,9 @@ class Scene:
             base = self._bsdf_key_base(b)
             if getattr(b, 'attr', None) is not None:
                 continue                   # a `mesh_attribute`: its values are the SHAPE's parameter '<shape>.<name>' (_attr_keys), its own is the `scale` (_attr_scale_keys)
-            if b.texture is not None:
+            if getattr(b, 'given', None) is not None and b.slot0_name not in b.given:
+                pass                       # a `thindielectric` without `specular_transmittance`: a null member, no entry (thindielectric.cpp:132-133)
+            elif b.texture is not None:
                 keys[base + "." + b.slot0_name + ".data"] = ("tex", b)
             else:
                 keys[base + "." + b.slot0_name + ".value"] = ("rgb", b)
@@ -3089,6 +3109,11 @@ class Scene:
                 keys[base + "." + b.slot1_name + ".value"] = ("slot1", b)
             if b.kind == 'bumpmap':
                 keys[base + ".scale"] = ("scale", b)                  # BumpMap::traverse (bumpmap.cpp:134): a ScalarFloat, NonDifferentiable
+            if b.kind == 'thindielectric':
+                # ThinDielectric::traverse (thindielectric.cpp:130-136): `eta`, and `specular_reflectance` when it was given (slot 1 here)
+                keys[base + ".eta"] = ("thin_ior", b)
+                if b.slot1_name in b.given:
+                    keys[base + "." + b.slot1_name + ".value"] = ("thin_r", b)
             if b.kind in ('dielectric', 'plastic', 'roughplastic'):
                 # the relative index of refraction int_ior / ext_ior, a plain float: dielectric.cpp:238, plastic.cpp:185 (NonDifferentiable), roughplastic.cpp:211 (Differentiable
                 # there; updatable without a gradient here)
@@ -3096,13 +3121,15 @@ class Scene:
         return keys
 
     def _bsdf_param_value(self, what, b):
-        return {"alpha": [b.alpha_u], "alpha_u": [b.alpha_u], "alpha_v": [b.alpha_v], "eta": b.eta_c, "k": b.k_c, "slot1": b.value2, "ior": [b.eta], "scale": [b.alpha_u]}[what]
+        return {"alpha": [b.alpha_u], "alpha_u": [b.alpha_u], "alpha_v": [b.alpha_v], "eta": b.eta_c, "k": b.k_c, "slot1": b.value2, "ior": [b.eta], "scale": [b.alpha_u], "thin_ior": [b.eta], "thin_r": b.value2}[what]
 
     def _set_bsdf_param(self, what, b, v):
         """params.update() of a non-slot-0 BSDF parameter: the record is re-lowered IN PLACE when a scene handle exists (har_scene_set_bsdf_params), else with the first handle (roughplastic's sampling weights and
         transmittance tables depend on alpha / the colours: RoughPlastic::parameters_changed, roughplastic.cpp:204-242)"""
         v = np.asarray(v, np.float32).reshape(-1)
-        if what == "ior":              # Dielectric / SmoothPlastic / RoughPlastic::parameters_changed: Fresnel terms, plastic's internal reflectance and tables follow eta --
+        if what == "thin_r" and (np.any(v[:3] < 0) or np.any(v[:3] > 1) or not np.isfinite(v[:3]).all()):
+            raise RuntimeError("Invalid RGB reflectance value %s, must be in the range [0, 1]!" % v[:3])
+        if what in ("ior", "thin_ior"):              # Dielectric / SmoothPlastic / RoughPlastic::parameters_changed: Fresnel terms, plastic's internal reflectance and tables follow eta --
             if not (float(v[0]) > 0.0) or not math.isfinite(float(v[0])) or (b.kind == 'roughplastic' and float(v[0]) == 1.0):      # all re-derived when the next scene handle lowers the record
                 raise RuntimeError("The interior and exterior indices of refraction must be positive" + (" and differ!" if b.kind == 'roughplastic' else "!"))
             b.eta = float(v[0])
@@ -3149,7 +3176,7 @@ class Scene:
         """BSDFFlags::Smooth on every side: models made of delta lobes only (`dielectric`, `conductor`) cannot sit on MOVING geometry -- their eval() is zero,
         so prb.py:288 would form relative_grad(0) (har_integrator_set_grad_positions)"""
         b = self.bsdf_objs[index]
-        delta = ("dielectric", "conductor")
+        delta = ("dielectric", "conductor", "thindielectric")
         return b.kind not in delta and (b.back is None or b.back.kind not in delta)
 
     def _differentiable_position_keys(self):
@@ -3711,7 +3738,7 @@ class SceneParameters(dict):
         if key in sc._param_keys() or key in sc._attr_keys():
             return ParamFlags.Differentiable
         if key in sc._bsdf_param_keys():
-            return ParamFlags.NonDifferentiable if sc._bsdf_param_keys()[key][0] in _NOGRAD_PARAMS else (ParamFlags.Differentiable if sc._bsdf_param_keys()[key][0] == "slot1" else ParamFlags.Differentiable | ParamFlags.Discontinuous)
+            return ParamFlags.NonDifferentiable if sc._bsdf_param_keys()[key][0] in _NOGRAD_PARAMS else (ParamFlags.Differentiable if sc._bsdf_param_keys()[key][0] in ("slot1", "thin_r") else ParamFlags.Differentiable | ParamFlags.Discontinuous)
         if key in sc._position_keys() or key in sc._instance_keys() or key in sc._rect_keys():
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
         if sc._pose_keys().get(key, (None,))[0] == "emitter_tex":
@@ -4193,7 +4220,7 @@ class DeviceGroup:
 # ---------------------------------------------------------------------------
 
 _REGISTRY = {}
-_BSDF_PLUGINS = ('diffuse', 'dielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask', 'normalmap', 'bumpmap')
+_BSDF_PLUGINS = ('diffuse', 'dielectric', 'thindielectric', 'conductor', 'plastic', 'roughconductor', 'roughplastic', 'twosided', 'blendbsdf', 'mask', 'normalmap', 'bumpmap')
 
 
 def register_plugin(name, variant_name, instantiate):
@@ -4337,7 +4364,7 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'bumpmap': _mk_bumpmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'thindielectric': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'bumpmap': _mk_bumpmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
@@ -4421,7 +4448,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
         shape_keys = [k for k in keys if k in scene._position_keys() or k in scene._instance_keys() or k in scene._rect_keys()]
         if shape_keys and integrator_ad.shape_gradients is not True:
             overrides['shape_gradients'] = sorted(set(list(integrator_ad.shape_gradients or [])) | set(shape_keys))
-        if any(k in scene._bsdf_param_keys() or getattr(scene._param_keys().get(k, (None, None))[1], 'kind', None) == 'alphamap' for k in keys) and not integrator_ad.bsdf_parameter_gradients:
+        if any((k in scene._bsdf_param_keys() and scene._bsdf_param_keys()[k][0] not in _THIN_PARAMS) or getattr(scene._param_keys().get(k, (None, None))[1], 'kind', None) == 'alphamap' for k in keys) and not integrator_ad.bsdf_parameter_gradients:
             overrides['bsdf_parameter_gradients'] = True
         if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator_ad.light_texel_gradients:
             overrides['light_texel_gradients'] = True

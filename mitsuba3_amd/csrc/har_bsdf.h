@@ -11,6 +11,7 @@
  *   type 7  mask             src/bsdfs/mask.cpp:93-232                  (one nested record scaled by an opacity, and a null lobe; resolved in har_scene.h)
  *   type 8  normalmap        src/bsdfs/normalmap.cpp:100-253            (one nested record evaluated in a shading frame perturbed by a texel; resolved in har_scene.h)
  *   type 9  bumpmap          src/bsdfs/bumpmap.cpp:102-253              (one nested record evaluated in a shading frame tilted by the uv-gradient of a height bitmap; resolved in har_scene.h)
+ *   type 10 thindielectric   src/bsdfs/thindielectric.cpp:100-217       (a leaf model: delta reflection and a NULL transmission lobe; only the kernels of scenes with such a record carry it, HAR_SCENE_THIN)
  *
  * plus include/mitsuba/render/fresnel.h:35-91 (fresnel), :93-116 (fresnel_conductor), :276-313 (reflect / refract)
  * and  include/mitsuba/render/microfacet.h:185-421 (MicrofacetDistribution eval / pdf / sample / smith_g1).
@@ -29,7 +30,11 @@ enum { BSDF_DIFFUSE = 0, BSDF_DIELECTRIC = 1, BSDF_ROUGHCONDUCTOR = 2, BSDF_ROUG
        BSDF_BLEND = 6 /* a record that names two leaf records (DBsdf::table, ::pad) and mixes them by the weight in slot 0 */,
        BSDF_MASK = 7 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and scales it by the opacity in slot 0, with a null lobe for the rest */,
        BSDF_NORMALMAP = 8 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame perturbed by the normal-map colour in slot 0 */,
-       BSDF_BUMPMAP = 9 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame tilted by `scale` (DBsdf::alpha_u) times the uv-gradient of its height bitmap (DBsdf::texture) */ };
+       BSDF_BUMPMAP = 9 /* a record that names one leaf record (DBsdf::pad; it may be twosided) and evaluates it in the frame tilted by `scale` (DBsdf::alpha_u) times the uv-gradient of its height bitmap (DBsdf::texture) */,
+       BSDF_THINDIELECTRIC = 10 /* a LEAF model outside the six above: slot 0 = specular_transmittance (a constant or a bitmap), slot 1 = specular_reflectance (a constant), DBsdf::eta.  It sets
+                                 * HAR_SCENE_THIN in DScene::bsdf_types, not a model bit: the model bits are compiled into every kernel (see HAR_SCENE_THIN below) */ };
+/* a leaf model: one of the six, or the thin dielectric (what a blend / mask record may name) */
+HAR_HD bool bsdf_is_leaf(uint32_t type) { return type < (uint32_t) BSDF_TYPE_COUNT || type == (uint32_t) BSDF_THINDIELECTRIC; }
 /* BF_MONO: the bitmap in slot 0 of a blend record has ONE channel (stored three times): Texture::eval_1 reads it instead of taking the luminance (bitmap.cpp:537-540).
  * BF_BLEND_SMOOTH: derived when a blend record is lowered -- one of its nested BSDFs has a smooth lobe (BSDFFlags::Smooth of the union, blendbsdf.cpp:99)
  * BF_MASK_SMOOTH (the same bit, in a mask record): the nested BSDF -- either side of a nested `twosided` pair -- has a smooth lobe (mask.cpp:113) */
@@ -42,7 +47,7 @@ enum { BF_NM_SMOOTH = 32u, BF_NM_FLIP = 64u, BF_NM_SHADOW = 128u };          /* 
  * that map has ONE channel (stored three times, channel 0 is read); a three-channel map is read as its luminance, as Texture::eval_1 does.  Only the kernels of scenes
  * that hold such a record (HAR_SCENE_ALPHAMAP) test these bits */
 enum { BF_ALPHA_TEX = 256u, BF_ALPHA_MONO_U = 512u, BF_ALPHA_MONO_V = 1024u };
-enum { LOBE_NULL = 0x1u };                    /* BSDFFlags::Null (bsdf.h:37): the only lobe of that kind is the mask record's */
+enum { LOBE_NULL = 0x1u };                    /* BSDFFlags::Null (bsdf.h:37): the mask record's pass-through lobe and the thin dielectric's transmission lobe */
 #define HAR_ROUGH_TRANSMITTANCE_RES 64          /* MI_ROUGH_TRANSMITTANCE_RES, include/mitsuba/render/microfacet.h */
 
 /* colour parameter slots: slot 0 = diffuse.reflectance | roughconductor.specular_reflectance |
@@ -75,9 +80,8 @@ struct BsdfCtx {
         return (type_mask == 0xffffffffu || (type_mask & type) == type) && (component == 0xffffffffu || component == comp);
     }
 };
-/* BSDF::component_count() of a (not twosided) record: diffuse 1, dielectric 2 (reflection, transmission), roughconductor 1, roughplastic 2 (glossy, diffuse),
+/* BSDF::component_count() of a (not twosided) record (bsdf_component_count, behind the scene bits below): diffuse 1, dielectric 2 (reflection, transmission), roughconductor 1, roughplastic 2 (glossy, diffuse),
  * conductor 1, plastic 2 (delta reflection, diffuse) */
-HAR_HD uint32_t bsdf_component_count(uint32_t type) { return (type == 1u || type == 3u || type == 5u) ? 2u : 1u; }
 
 HAR_HD float safe_sqrt_(float x) { return sqrtf(fmaxf(x, 0.f)); }
 HAR_HD float lerp_(float a, float b, float t) { return fma_(b, t, fnma_(a, t, a)); }        /* dr::lerp */
@@ -96,6 +100,13 @@ HAR_HD void fresnel_dielectric(float cos_theta_i, float eta, float &r, float &co
     r = 0.5f * (sqr_(a_s) + sqr_(a_p));
     if (special_case) r = r_sc;
     cos_theta_t = mulsign_neg_(cos_theta_t_abs, cos_theta_i);
+}
+
+/* ThinDielectric: r' = r + trt + tr^3t + .. of a pane, thindielectric.cpp:152-155 in its order of operations: r = fresnel(|cos theta_i|, eta), r *= 2 / (1 + r) */
+HAR_HD float thin_reflectance(float eta, float cos_theta_i) {
+    float r, cos_theta_t, eta_it, eta_ti; fresnel_dielectric(fabsf(cos_theta_i), eta, r, cos_theta_t, eta_it, eta_ti);
+    r *= 2.f / (1.f + r);
+    return r;
 }
 
 /* fresnel_conductor(), fresnel.h:93-116 */
@@ -291,7 +302,11 @@ HAR_HD float lerp_gather(const float *data, float x, uint32_t size) {
  * filled and read by the kernels of scenes with a roughness map only (HAR_SCENE_ALPHAMAP; every other kernel reads DBsdf::alpha_u / ::alpha_v as it did) */
 struct BsdfInputs { Vec3 slot0, slot1; const float *table; float alpha_u, alpha_v; };
 
-HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC && B.type != BSDF_CONDUCTOR; }          /* BSDFFlags::Smooth */
+/* The three helpers that read HAR_SCENE_THIN -- bsdf_is_smooth, bsdf_component_count (below) and mask_null_index (har_scene.h) -- default to TYPES = 0, the kernels of
+ * scenes without a pane; the kernels of pane scenes pass their TYPES and host code that must know the model passes HAR_SCENE_THIN */
+#define HAR_SCENE_THIN 0x20000u
+template <uint32_t TYPES = 0u>
+HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC && B.type != BSDF_CONDUCTOR && !((TYPES & HAR_SCENE_THIN) != 0u && B.type == BSDF_THINDIELECTRIC); }          /* BSDFFlags::Smooth */
 /* material class of a BSDF record for the per-material shading queues: its model when both sides of the surface evaluate the same model (plain records,
  * `twosided` with one nested BSDF or a same-model pair), HAR_MAT_GENERIC for a `twosided` pair of two different models (the generic kernel serves it) */
 #define HAR_MAT_GENERIC 6u
@@ -349,7 +364,7 @@ static_assert((HAR_SCENE_ATTR & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1
 #define HAR_SCENE_BUMPMAP_TYPES (HAR_SCENE_NORMALMAP_TYPES | HAR_SCENE_BUMPMAP)
 #define HAR_SCENE_NMAP_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP)
 #define HAR_SCENE_RECORD_BITS (HAR_SCENE_COMPOSITE | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP)
-#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP | HAR_SCENE_ALPHAMAP /* below */)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
+#define HAR_SCENE_WIDE_ROUTE (HAR_SCENE_WIDEST | HAR_SCENE_NORMALMAP | HAR_SCENE_BUMPMAP | HAR_SCENE_ALPHAMAP /* below */ | HAR_SCENE_THIN /* below */)      /* the scenes that are planned on the widest-kernel route (HAR_SCENE_WIDEST stays the template argument it was) */
 static_assert((HAR_SCENE_NORMALMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x8000u | 0x80000000u)) == 0u, "HAR_SCENE_NORMALMAP collides with another scene bit");
 static_assert((HAR_SCENE_BUMPMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 0x1000u | 0x2000u | 0x4000u | 0x80000000u)) == 0u, "HAR_SCENE_BUMPMAP collides with another scene bit");
 /* ... and a roughconductor record whose `alpha` is a bitmap (BF_ALPHA_TEX): the roughness is looked up at every vertex on such a record and rides in BsdfInputs.  A scene
@@ -360,6 +375,21 @@ static_assert((HAR_SCENE_BUMPMAP & (0xffu | 0x100u | 0x200u | 0x400u | 0x800u | 
 #define HAR_SCENE_ALPHAMAP_TYPES (HAR_SCENE_BUMPMAP_TYPES | HAR_SCENE_ALPHAMAP)
 #define HAR_SCENE_ALPHAMAP_LEAN_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_ALPHAMAP)      /* ... without a blend / mask / normalmap / bumpmap record in the scene: no composite code */
 static_assert((HAR_SCENE_ALPHAMAP & (0xffffu | 0x80000000u)) == 0u, "HAR_SCENE_ALPHAMAP collides with another scene bit");
+/* ... and a `thindielectric` record (type 10): a leaf model whose transmission lobe is a NULL lobe.  Its code must not reach the kernels of other scenes, so the record sets
+ * this bit in DScene::bsdf_types instead of a model bit, and the scene runs a widest set of its own, TYPES = HAR_SCENE_THIN_TYPES = the roughness-map set | HAR_SCENE_THIN
+ * (blend / mask / normalmap / bumpmap records and roughness maps may sit next to it, and a blend / mask record may name it; a scene that also holds a `mesh_attribute`
+ * texture is refused when it is lowered).  Like HAR_SCENE_ALPHAMAP the bit reaches the leaf models; every line of the model sits behind a test of it.  The set carries the
+ * mask code, so the null-lobe bookkeeping of `path` (ShadeResult::non_null, ChunkPlan::valid_shade) is the mask scenes', generalised to "the sampled lobe is null" */
+#define HAR_SCENE_THIN_TYPES (HAR_SCENE_ALPHAMAP_TYPES | HAR_SCENE_THIN)
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_THIN bit is read: thindielectric 2 -- delta reflection, null transmission -- in the kernels and host twins that carry the model) */
+HAR_HD uint32_t bsdf_component_count(uint32_t type) { return (type == 1u || type == 3u || type == 5u || ((TYPES & HAR_SCENE_THIN) != 0u && type == (uint32_t) BSDF_THINDIELECTRIC)) ? 2u : 1u; }
+#define HAR_SCENE_THIN_LEAN_TYPES (HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_THIN)      /* ... without a blend / mask / normalmap / bumpmap record or a roughness map in the scene: no composite code; the null-lobe bookkeeping tests (MASK | THIN) */
+static_assert((HAR_SCENE_THIN & (0x1ffffu | 0x80000000u)) == 0u, "HAR_SCENE_THIN collides with another scene bit");
+/* the bit a record of `type` sets in DScene::bsdf_types: its model bit, or the scene bit of a record / model that has one */
+HAR_HD uint32_t bsdf_scene_bit(uint32_t type) {
+    return type == BSDF_BLEND ? HAR_SCENE_BLEND : type == BSDF_MASK ? HAR_SCENE_MASK : type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP :
+           type == BSDF_THINDIELECTRIC ? HAR_SCENE_THIN : 1u << type;
+}
 #define HAR_SCENE_ENVMAP 0x100u           /* the scene has an environment MAP (emitter type 2), a MESH area light (type 3) or a POINT light (type 4): kernels of other scenes compile that code out */
 
 /* fresnel_diffuse_reflectance (include/mitsuba/render/fresnel.h:327-355), evaluated on the host when a `plastic` record is (re)built */
@@ -497,6 +527,22 @@ HAR_HD void bsdf_sample_one(const DBsdf &B, const BsdfInputs &in, Vec3 wi, float
     bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;     /* dr::zeros<BSDFSample3f>() */
     float cos_theta_i = wi.z;
     const uint32_t type = HAR_BSDF_SINGLE(TYPES) ? (uint32_t) HAR_BSDF_SINGLE_TYPE(TYPES) : B.type;
+    if ((TYPES & HAR_SCENE_THIN) != 0u && type == (uint32_t) BSDF_THINDIELECTRIC) {                /* thindielectric.cpp:142-191 */
+        /* component 0 = delta reflection, 1 = the null lobe (straight through, eta 1); r' = r + trt + tr^3t + .. = r * (2 / (1 + r)).  With one of the two disabled the
+         * other is taken with probability 1 and carries r' / t' in its weight (:167-171).  The transport mode changes nothing; sample2 is not read */
+        const bool has_reflection = !CTX || ctx.is_enabled(LOBE_DELTA_REFLECTION, 0u), has_transmission = !CTX || ctx.is_enabled(LOBE_NULL, 1u);
+        if (CTX && !has_reflection && !has_transmission) return;
+        const float r = thin_reflectance(B.eta, cos_theta_i), t = 1.f - r;
+        const bool both = has_reflection && has_transmission;
+        const bool selected_r = both ? sample1 <= r : has_reflection;
+        bs.pdf = both ? (selected_r ? r : t) : 1.f;
+        bs.delta = true; bs.type = selected_r ? (uint32_t) LOBE_DELTA_REFLECTION : (uint32_t) LOBE_NULL; bs.comp = selected_r ? 0u : 1u;
+        bs.wo = selected_r ? reflect_local(wi) : Vec3(-wi.x, -wi.y, -wi.z);
+        bs.eta = 1.f;
+        bs.weight = selected_r ? in.slot1 : in.slot0;                      /* weight 1 times the colour (a colour that was not given is stored as 1) */
+        if (CTX && !both) bs.weight = selected_r ? in.slot1 * r : in.slot0 * t;
+        return;
+    }
     switch (type) {
     case BSDF_DIFFUSE: {                                                     /* diffuse.cpp:100-124 */
         if (CTX && !ctx.is_enabled(LOBE_DIFFUSE_REFLECTION)) return;

@@ -123,6 +123,12 @@ int run_chunk(HarSceneImpl *S, HarIntegratorImpl *I, const DSensor &C, int mode,
         return fail("bumpmap: a scene with a `bumpmap` record has no item-writing adjoint or record-tape shading kernel (its gradients take the in-place commit of the replay cache)");
     if ((S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) && (rec_w || rec_r || (mode == MODE_PRB_ADJOINT && !(plan.inline_commit && (cache_mode == CACHE_READ || cache_mode == TAPE_READ)))))
         return fail("roughness map: a scene with a bitmap `alpha` has no item-writing adjoint or record-tape shading kernel (its gradients take the in-place commit of the replay cache)");
+    /* (a pane among plain models -- the lean set -- has the item-writing adjoint that forward mode reads) */
+    const bool thin_lean_fwd = (S->ds.bsdf_types & HAR_SCENE_WIDE_ROUTE) == HAR_SCENE_THIN && I->forward_mode && !rec_w && !rec_r;
+    if (plan.mq_on && (S->ds.bsdf_types & HAR_SCENE_THIN))
+        return fail("thindielectric: `material_queues` cannot serve a scene with a `thindielectric` record (the model has no material class of its own; its scenes run one shading kernel per flavour)");
+    if ((S->ds.bsdf_types & HAR_SCENE_THIN) && !thin_lean_fwd && (rec_w || rec_r || (mode == MODE_PRB_ADJOINT && !(plan.inline_commit && (cache_mode == CACHE_READ || cache_mode == TAPE_READ)))))
+        return fail("thindielectric: a scene with a `thindielectric` record has no item-writing adjoint or record-tape shading kernel (its gradients take the in-place commit of the replay cache)");
     const uint32_t grid = plan.grid, tgrid = plan.tgrid;
     if (rec_r) return commit_pass(S, I, nb, n, grid, grad_refl, s);
     if (!tape_r) HIP_TRY(hipMemsetAsync(cnt_alive(I, 0), 0, used, s));      /* the replay reads the primal pass's wavefront sizes */
@@ -685,7 +691,9 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     const bool bump = (S->ds.bsdf_types & HAR_SCENE_BUMPMAP) != 0u;          /* ... and a `bumpmap` record: the height map's gradient and the nested colours' likewise */
     const bool amap = (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) != 0u;          /* ... and a roughness map: groups 0 / 1 of a textured record go into the map's texels, by the in-place commit too */
     const bool amap_only = amap && (S->ds.bsdf_types & HAR_SCENE_WIDE_ROUTE) == HAR_SCENE_ALPHAMAP;      /* ... without a composite record: the one wide-route scene whose alpha / eta / k gradients exist */
-    const char *const comp = amap_only ? "roughness map" : bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
+    const bool thin = (S->ds.bsdf_types & HAR_SCENE_THIN) != 0u;          /* ... and a `thindielectric` record: the pane has no gradient of its own; everything else in the scene takes the in-place commit of its set */
+    const bool thin_only = thin && (S->ds.bsdf_types & HAR_SCENE_WIDE_ROUTE) == HAR_SCENE_THIN;      /* ... among plain models: the lean set, whose commit has the alpha / eta / k / slot-1 terms */
+    const char *const comp = thin ? "thindielectric" : amap_only ? "roughness map" : bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
     /* ... and the texels of the environment map (har_integrator_set_grad_envmap): the same two terms, the same route */
     const bool env_texels = I->set.grad_envmap && S->hs.has_envmap;
     int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !env_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
@@ -739,9 +747,9 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
         if (I->set.grad_bsdf_params && attr_only) return fail("mesh_attribute: gradients of alpha / eta / k / specular colours are not produced for scenes with a `mesh_attribute` texture (the attributes' are)");
         if (I->set.grad_bsdf_params && amap && !amap_only)
             return fail(std::string("roughness map: alpha texel gradients (and alpha / eta / k / specular colours) are not produced for a scene that also holds a `") + comp + "` record: a roughconductor nested in a blendbsdf / mask / normalmap / bumpmap keeps its forward render only");
-        if (I->set.grad_bsdf_params && !amap_only) return fail(std::string(comp) + ": gradients of alpha / eta / k / specular colours are not produced for scenes with a " + (bump ? "bumpmap record (the height map and the nested BSDF's colour slot 0 are)" : nmap ? "normalmap record (the normal map and the nested BSDF's colour slot 0 are)" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask record (the opacity and the nested BSDF's colour slot 0 are)" : "blend record (the weight and the nested BSDFs' colour slot 0 are)"));
+        if (I->set.grad_bsdf_params && !amap_only && !thin_only) return fail(std::string(comp) + ": gradients of alpha / eta / k / specular colours are not produced for scenes with a " + (thin ? "thindielectric record next to a blendbsdf / mask / normalmap / bumpmap record or a roughness map (colour slot 0 of the other BSDFs, texels and emitter radiances are)" : bump ? "bumpmap record (the height map and the nested BSDF's colour slot 0 are)" : nmap ? "normalmap record (the normal map and the nested BSDF's colour slot 0 are)" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask record (the opacity and the nested BSDF's colour slot 0 are)" : "blend record (the weight and the nested BSDFs' colour slot 0 are)"));
         if (!I->set.use_cache || I->shape_on) return fail(std::string(comp) + ": gradients need the replay cache and cannot be combined with vertex-position gradients");
-        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail(std::string(comp) + ": gradients of a scene with a " + (amap_only ? "roughness-map" : bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute texture" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blend") + " record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
+        if (bounce_limit(I) > HAR_REPLAY_CACHE_BOUNCES) return fail(std::string(comp) + ": gradients of a scene with a " + (thin ? "thindielectric" : amap_only ? "roughness-map" : bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute texture" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blend") + " record: max_depth must not exceed " + std::to_string(HAR_REPLAY_CACHE_BOUNCES) + " (the cached bounces)");
         if (!W.adjoint_inline) return fail(std::string(comp) + ": gradients need the in-place commit (HAR_ADJOINT_INLINE=0 is set)");
     }
     if (I->set.grad_bsdf_params) {
@@ -797,6 +805,8 @@ int har_render_forward(HarScene S, HarIntegrator I, const HarSensor *sensor, uin
     if (I->set.type != HAR_INTEGRATOR_PRB) return fail("render_forward is implemented by the `prb` integrator");
     if (!film || !tangent_reflectance) return fail("null film / tangent buffers");
     if (I->shape_on) return fail("render_forward: tangents of vertex positions are not implemented (use render_backward for shape gradients)");
+    if ((S->ds.bsdf_types & HAR_SCENE_THIN) && (S->ds.bsdf_types & HAR_SCENE_WIDE_ROUTE) != HAR_SCENE_THIN)
+        return fail("thindielectric: render_forward is not implemented for a scene that holds a `thindielectric` record next to a blendbsdf / mask / normalmap / bumpmap record, a roughness map or a `mesh_attribute` texture (that kernel set has no item-writing adjoint)");
     if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: render_forward is not implemented for a scene with a bitmap `alpha` (forward-mode tangents of alpha texels)");
     if (S->ds.bsdf_types & HAR_SCENE_BUMPMAP) return fail("bumpmap: render_forward is not implemented for a scene with a `bumpmap` record (forward-mode tangents of the height map and of nested parameters)");
     if (S->ds.bsdf_types & HAR_SCENE_NORMALMAP) return fail("normalmap: render_forward is not implemented for a scene with a `normalmap` record (forward-mode tangents of the normal map and of nested parameters)");
@@ -850,7 +860,7 @@ int har_render_forward(HarScene S, HarIntegrator I, const HarSensor *sensor, uin
 static bool record_has_smooth_lobe(const HostScene &hs, int32_t index) {
     if (index < 0 || (size_t) index >= hs.bsdfs.size()) return false;
     const DBsdf &b = hs.bsdfs[(size_t) index];
-    return bsdf_is_smooth(b) && (b.back < 0 || bsdf_is_smooth(hs.bsdfs[(size_t) b.back]));
+    return bsdf_is_smooth<HAR_SCENE_THIN>(b) && (b.back < 0 || bsdf_is_smooth<HAR_SCENE_THIN>(hs.bsdfs[(size_t) b.back]));
 }
 
 int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const *grad_positions) {
@@ -865,6 +875,7 @@ int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const 
         const size_t nm = S->hs.meshes.size();
         /* their adjoint goes through items, which carry one (record, direct, relative) triple per vertex: a blend vertex has three */
         /* ... and the barycentrics an attribute is looked up at move with the positions (Mesh::barycentric_coordinates): not differentiated */
+        if (S->ds.bsdf_types & HAR_SCENE_THIN) return fail("thindielectric: vertex-position gradients are not produced for a scene with a `thindielectric` record");
         if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("vertex-position gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: vertex-position gradients are not produced for a scene with a bitmap `alpha`");
         if (S->ds.bsdf_types & HAR_SCENE_BUMPMAP) return fail("vertex-position gradients are not produced for a scene with a `bumpmap` record");
@@ -911,6 +922,7 @@ int har_integrator_set_grad_instances(HarIntegrator I, HarScene S, float *grad_t
     uint32_t n = 0;
     if (grad_to_world) {
         if (!S) return fail("null scene");
+        if (S->ds.bsdf_types & HAR_SCENE_THIN) return fail("thindielectric: instance to_world gradients are not produced for a scene with a `thindielectric` record");
         if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("instance to_world gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: instance to_world gradients are not produced for a scene with a bitmap `alpha`");
         if (S->ds.bsdf_types & HAR_SCENE_BUMPMAP) return fail("instance to_world gradients are not produced for a scene with a `bumpmap` record");

@@ -1372,7 +1372,7 @@ __global__ __launch_bounds__(kBlock, (RECORD && TYPES == HAR_BSDF_ONLY_DIFFUSE &
             lane = st.lane - lane_base;
             /* `path` in a scene with a mask record (ChunkPlan::valid_shade): valid_ray |= a non-null lobe was sampled here (path.cpp:307-308).  The chunk's per-lane validity
              * flags, cleared by run_chunk, arrive in the `grad_extra` argument, which no MODE_PATH kernel reads otherwise (the kernels' argument list stays what it was) */
-            if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH && grad_extra && R.non_null) grad_extra[lane] = 1.f;
+            if ((TYPES & (HAR_SCENE_MASK | HAR_SCENE_THIN)) != 0u && MODE == MODE_PATH && grad_extra && R.non_null) grad_extra[lane] = 1.f;
             if (MODE == MODE_PRB_ADJOINT && INLINE) {
                 if (tape_read) { const float4 a = tape.la_in[i]; const float2 c2 = tape.lb_in[i]; Lr = Vec3(a.x, a.y, a.z); dlr = Vec3(a.w, c2.x, c2.y); }
                 else { const float4 r = result[lane], d4 = dL[lane]; Lr = Vec3(r.x, r.y, r.z); dlr = Vec3(d4.x, d4.y, d4.z); }
@@ -2440,6 +2440,18 @@ __global__ void k_api_bsdf_sample_amap(DScene S, uint32_t bsdf, BsdfCtx ctx, uin
     if (i >= n) return;
     bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP>(S, bsdf, ctx, n, i, wi, uv, s1, s2, geom, !(active && !active[i]), wo, pdf, weight, eta, stype, scomp);
 }
+/* ... of a scene that holds a `thindielectric` record (HAR_SCENE_THIN): both families of entries over the set that also carries the thin leaf model.  Kernels of their own */
+__global__ void k_api_bsdf_eval_pdf_thin(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom, const uint8_t *active, float *value, float *pdf) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_eval_pdf_si_lane<HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN>(S, bsdf, ctx, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+}
+__global__ void k_api_bsdf_sample_thin(DScene S, uint32_t bsdf, BsdfCtx ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom, const uint8_t *active,
+                                       float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN>(S, bsdf, ctx, n, i, wi, uv, s1, s2, geom, !(active && !active[i]), wo, pdf, weight, eta, stype, scomp);
+}
 /* har_bsdf_alpha: the roughness record `bsdf` evaluates at n uv points (bsdf_alpha_lane) */
 __global__ void k_api_bsdf_alpha(DScene S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v) {
     uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -2556,6 +2568,41 @@ void launch_shade(int mode, hipStream_t s, uint32_t grid, const DScene &S, const
     const TexelQueues tq = tq_in ? *tq_in : no_tq;
     const MaterialQueues no_mq{ nullptr, nullptr, 0u, 0u };
     const TapeArrays tape = tape_in ? *tape_in : TapeArrays{ nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+    if (S.bsdf_types & HAR_SCENE_THIN) {
+        /* a scene with a `thindielectric` record: the roughness-map set (blend / mask / normalmap / bumpmap records and roughness maps may sit next to the pane, and a
+         * blend / mask record may name it) plus the thin leaf model and the null-lobe bookkeeping by the sampled lobe's type.  Three shading kernels: forward, prb primal
+         * and the in-place adjoint commit of a cached / taped bounce.  No item-writing adjoint and no EXTRA flavour in THIS set: run_chunk's callers refuse forward mode
+         * and alpha / eta / k gradients for a pane next to a composite record or a roughness map, and position gradients for every pane scene, before any launch (har_capi.hip) */
+        if (!(S.bsdf_types & (HAR_SCENE_RECORD_BITS | HAR_SCENE_ALPHAMAP))) {
+            /* ... a pane among plain BSDF models -- the window in a room, the feature's main use -- runs the generic set plus the thin leaf (HAR_SCENE_THIN_LEAN_TYPES) and does
+             * not carry the composite code.  That set has five flavours: forward, prb primal, the in-place adjoint commit, that commit with the alpha / eta / k / slot-1
+             * terms of the rough models on the OTHER surfaces (EXTRA), and the item-writing adjoint that forward mode reads */
+            constexpr uint32_t L = HAR_SCENE_THIN_LEAN_TYPES;
+            if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4) && grad_extra)
+                hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, L, false, true, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, grad_extra, no_mq, 0u, tape);
+            else if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+                hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, L, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+            else if (mode == MODE_PATH)
+                hipLaunchKernelGGL((k_shade<MODE_PATH, L>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags, or null (run_chunk) */, no_mq, 0u, tape);
+            else if (mode == MODE_PRB_PRIMAL)
+                hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, L>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+            else
+                hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, L>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+            return;
+        }
+        constexpr uint32_t T = HAR_SCENE_THIN_TYPES;
+        if (mode == MODE_PRB_ADJOINT && grad_tex && (rc.mode == 2 || rc.mode == 4))
+            hipLaunchKernelGGL((k_shade<MODE_PRB_ADJOINT, T, false, true>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, grad_tex, tq, nullptr, no_mq, 0u, tape);
+        else if (mode == MODE_PATH)
+            hipLaunchKernelGGL((k_shade<MODE_PATH, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, grad_extra /* the validity flags, or null (run_chunk) */, no_mq, 0u, tape);
+        else if (mode == MODE_PRB_PRIMAL)
+            hipLaunchKernelGGL((k_shade<MODE_PRB_PRIMAL, T>), g, b, 0, s, S, P, lane_base, shard_cap, count_in, in, h0, h1, out, count_out, items, item_count, result, rc, pass_rng, dL, grad_slots, no_geo, nullptr, no_tq, nullptr, no_mq, 0u, tape);
+        else {
+            fprintf(stderr, "hip_ad_rgb: launch_shade: a scene with a `thindielectric` record has no shading kernel for mode %d without the in-place commit\n", mode);
+            abort();
+        }
+        return;
+    }
     if (S.bsdf_types & HAR_SCENE_ALPHAMAP) {
         /* a scene with a roughconductor record whose roughness is a bitmap: the bumpmap set (the record may sit under or next to blend / mask / normalmap / bumpmap records)
          * plus the lookup of the roughness at every vertex.  Four shading kernels: forward, prb primal, the in-place adjoint commit, and that commit with the alpha / eta /
@@ -2879,17 +2926,20 @@ void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const u
 }
 void launch_api_bsdf_eval_pdf_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom,
                                  const uint8_t *active, float *value, float *pdf) {
+    if (S.bsdf_types & HAR_SCENE_THIN) { hipLaunchKernelGGL(k_api_bsdf_eval_pdf_thin, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf); return; }
     if (S.bsdf_types & HAR_SCENE_ALPHAMAP) { hipLaunchKernelGGL(k_api_bsdf_eval_pdf_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf); return; }
     hipLaunchKernelGGL(k_api_bsdf_eval_pdf_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf);
 }
 void launch_api_bsdf_sample_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2, const float *geom,
                                const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
+    if (S.bsdf_types & HAR_SCENE_THIN) { hipLaunchKernelGGL(k_api_bsdf_sample_thin, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp); return; }
     if (S.bsdf_types & HAR_SCENE_ALPHAMAP) { hipLaunchKernelGGL(k_api_bsdf_sample_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp); return; }
     hipLaunchKernelGGL(k_api_bsdf_sample_bump, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, geom, active, wo, pdf, weight, eta, stype, scomp);
 }
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf) {
-    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, nullptr, active, value, pdf);
+    if (S.bsdf_types & HAR_SCENE_THIN) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_thin, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, nullptr, active, value, pdf);
+    else if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, nullptr, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_eval_pdf_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_eval_pdf<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, active, value, pdf);
@@ -2897,7 +2947,8 @@ void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, con
 }
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp) {
-    if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_sample_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, nullptr, active, wo, pdf, weight, eta, stype, scomp);
+    if (S.bsdf_types & HAR_SCENE_THIN) hipLaunchKernelGGL(k_api_bsdf_sample_thin, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, nullptr, active, wo, pdf, weight, eta, stype, scomp);
+    else if (S.bsdf_types & HAR_SCENE_ALPHAMAP) hipLaunchKernelGGL(k_api_bsdf_sample_amap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, nullptr, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_NORMALMAP) hipLaunchKernelGGL(k_api_bsdf_sample_nmap, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_MASK) hipLaunchKernelGGL(k_api_bsdf_sample_mask, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);
     else if (S.bsdf_types & HAR_SCENE_BLEND) hipLaunchKernelGGL(k_api_bsdf_sample<true>, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, s1, s2, active, wo, pdf, weight, eta, stype, scomp);

@@ -169,7 +169,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     if (MODE == MODE_PRB_ADJOINT && EXTRA) { for (int g = 0; g < 5; ++g) { R.x_dir[g] = Vec3(0.f); R.x_rel[g] = Vec3(0.f); } R.x_ind = false; }
     if (MODE == MODE_PRB_ADJOINT) { R.lt_hit_emitter = -1; R.lt_nee_emitter = -1; R.lt_hit_uv[0] = R.lt_hit_uv[1] = R.lt_nee_uv[0] = R.lt_nee_uv[1] = 0.f; }
     if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_BLEND) != 0u) { R.bl_rec[0] = R.bl_rec[1] = 0xffffffffu; R.bl_dir[0] = R.bl_dir[1] = R.bl_rel[0] = R.bl_rel[1] = Vec3(0.f); R.bl_ind = false; }
-    if ((TYPES & HAR_SCENE_MASK) != 0u) R.non_null = false;
+    if ((TYPES & (HAR_SCENE_MASK | HAR_SCENE_THIN)) != 0u) R.non_null = false;
     if (MODE == MODE_PRB_ADJOINT && (TYPES & HAR_SCENE_NORMALMAP) != 0u) { R.nm_rec = 0xffffffffu; R.nm_ind = false; for (int k = 0; k < 3; ++k) { R.nm_dir[k] = Vec3(0.f); R.nm_rel[k] = Vec3(0.f); } }
     if (MODE == MODE_PRB_ADJOINT) { R.em_index = -1; R.nee_emitter = -1; R.em_unit = Vec3(0.f); R.contrib_unit = Vec3(0.f); R.nee_flags = 0u; R.cos_em = 0.f; R.nee_p = Vec3(0.f); R.nee_n = Vec3(0.f); R.nee_w = Vec3(0.f); }
     uint64_t rng = st.rng;
@@ -235,11 +235,20 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     }
 
     bool active_next = (depth + 1u < P.max_depth) && valid;
-    if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH && !active_next && valid) {
+    if ((TYPES & (HAR_SCENE_MASK | HAR_SCENE_THIN)) != 0u && MODE == MODE_PATH && !active_next && valid) {
         /* the path ends at this surface.  JIT order: the lane still draws this iteration's numbers, and valid_ray takes the sampled lobe's type (path.cpp:263-267,307-308):
          * at a mask record the third draw decides, sample1 < opacity.  Scalar order: the early exit (:227-231), valid_ray |= the surface is an emitter */
         if (P.flags & HAR_SHADE_SCALAR_DRAWS) R.non_null = emitter >= 0;
-        else {
+        else if ((TYPES & HAR_SCENE_THIN) != 0u) {
+            /* kernels of scenes with a thin dielectric: any record that can return a null lobe -- the thin leaf, a mask, a blend over a thin leaf */
+            BsdfSide vs; R.non_null = true;
+            if (bsdf_side(S, M.bsdf, si.wi, vs)) {
+                const DBsdf VB = S.bsdfs[vs.index];
+                TexTaps vt; const BsdfInputs vin = bsdf_inputs(S, VB, si.uv_x, si.uv_y, vt, aa);
+                uint64_t r = rng; pcg32_next_float(r, inc); pcg32_next_float(r, inc);
+                R.non_null = !sample_takes_null_lobe<TYPES>(S, VB, vin, vs.wi, pcg32_next_float(r, inc));
+            }
+        } else {
             BsdfSide vs; R.non_null = true;
             if (bsdf_side(S, M.bsdf, si.wi, vs) && S.bsdfs[vs.index].type == BSDF_MASK) {
                 const DBsdf VB = S.bsdfs[vs.index];
@@ -281,7 +290,7 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     const BumpGeom *const bg = ((TYPES & HAR_SCENE_BUMPMAP) != 0u && bump) ? &bgeom : nullptr;
     const bool composite = blend || mask || nmap || bump;
     const bool smooth = HAR_BSDF_SINGLE(TYPES) ? (HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_DIELECTRIC && HAR_BSDF_SINGLE_TYPE(TYPES) != (uint32_t) BSDF_CONDUCTOR)
-                                               : (composite ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth(B));
+                                               : (composite ? (B.flags & BF_BLEND_SMOOTH) != 0u : bsdf_is_smooth<TYPES>(B));
     if (!(P.flags & HAR_SHADE_SCALAR_DRAWS) || smooth) { ex = pcg32_next_float(rng, inc); ey = pcg32_next_float(rng, inc); }
     DirSample ds; ds.pdf = 0.f; ds.d = Vec3(0.f); ds.p = Vec3(0.f); ds.n = Vec3(0.f); ds.dist = 0.f;
     Vec3 em_weight(0.f); float em_unit = 0.f; uint32_t em_sampled = 0;
@@ -351,7 +360,8 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
     BsdfEval ev; bsdf_eval_pdf<TYPES>(S, side, bin, side_ok, wo_em, ev, BsdfCtx(), si.uv_x, si.uv_y, ((TYPES & HAR_SCENE_BLEND) != 0u && MODE != MODE_PATH) ? &cg : nullptr, aa, bg);
     BsdfSample bs; bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
     if (MODE == MODE_PATH || active_next) bsdf_sample<TYPES>(S, side, bin, side_ok, s1, s2x, s2y, bs, BsdfCtx(), si.uv_x, si.uv_y, aa, bg);
-    if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH) R.non_null = !(mask && bs.type == LOBE_NULL);        /* path.cpp:307-308 (si is valid here) */
+    if ((TYPES & HAR_SCENE_THIN) != 0u && MODE == MODE_PATH) R.non_null = bs.type != LOBE_NULL;                   /* ... whichever record sampled it: a thin leaf, alone or under a blend / mask, or a mask */
+    else if ((TYPES & HAR_SCENE_MASK) != 0u && MODE == MODE_PATH) R.non_null = !(mask && bs.type == LOBE_NULL);        /* path.cpp:307-308 (si is valid here) */
 
     /* ---- NEE contribution (path.cpp:271-281, prb.py:210-216); visibility is resolved by the shadow kernel */
     R.contrib = Vec3(0.f); R.contrib_b = Vec3(0.f); R.dLr_drho = Vec3(0.f); R.dLr_drho_unit = Vec3(0.f); R.rho = bin.slot0;

@@ -150,7 +150,8 @@ inline ChunkPlan plan_chunk(const Switches &W, const Settings &I, const SceneFac
     P.alpha_miss = (mode == MODE_PATH && F.env_emitter >= 0 && !I.hide_emitters) ? 1.f : 0.f;
     /* a scene with a mask record, `path`, no visible environment (with one every sample is valid from the start): the flags come out of shading, asked for or not -- the
      * radiance of an invalid sample is dropped.  prb keeps depth != 0 (prb.py:332: null interactions count), i.e. k_alpha_flags */
-    P.valid_shade = mode == MODE_PATH && (F.bsdf_types & HAR_SCENE_MASK) != 0u && P.alpha_miss == 0.f;
+    /* ... and a scene with a `thindielectric` record likewise: its transmission lobe is a null lobe (thindielectric.cpp:126), whichever record sampled it */
+    P.valid_shade = mode == MODE_PATH && (F.bsdf_types & (HAR_SCENE_MASK | HAR_SCENE_THIN)) != 0u && P.alpha_miss == 0.f;
     if (P.valid_shade) P.alpha_flags = false;
     return P;
 }

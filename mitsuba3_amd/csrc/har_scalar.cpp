@@ -65,7 +65,7 @@ struct BoundScene {
         S.n_emitters = (uint32_t) hs.emitters.size(); S.n_meshes = (uint32_t) hs.meshes.size();
         S.n_bsdfs = (uint32_t) hs.bsdfs.size(); S.n_insts = (uint32_t) hs.insts.size(); S.n_textures = (uint32_t) hs.textures.size();
         S.env_emitter = hs.env_emitter;
-        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+        S.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) S.bsdf_types |= bsdf_scene_bit(b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
         for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) S.bsdf_types |= HAR_SCENE_ATTR;
         for (const DBsdf &b : hs.bsdfs) if (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX)) S.bsdf_types |= HAR_SCENE_ALPHAMAP;
         S.envmap = nullptr; S.emitter_cdf = hs.emitter_cdf.data();
@@ -120,14 +120,15 @@ Vec3 sample_scalar(const DScene &S, const ShadeParams &P, uint64_t &rng, Vec3 o,
         if (stats) { stats->vertices++; stats->closest_rays++; }   /* one loop iteration of PathIntegrator::sample: what the wavefront's bounce counters add up to */
         ShadeResult R;
         R.next.rng = st.rng;                                      /* a path that ends before this iteration's draws (path.cpp:226-227 `break`) leaves the stream where it is */
-        if (S.bsdf_types & HAR_SCENE_ALPHAMAP) shade_lane<MODE_PATH, HAR_SCENE_ALPHAMAP_TYPES>(S, P, st, hit, R);      /* a roughness map: the bumpmap set plus the lookup (no `mesh_attribute` texture next to it) */
+        if (S.bsdf_types & HAR_SCENE_THIN) shade_lane<MODE_PATH, HAR_SCENE_THIN_TYPES>(S, P, st, hit, R);      /* a thin dielectric: the roughness-map set plus the thin leaf and the null-lobe bookkeeping by lobe type */
+        else if (S.bsdf_types & HAR_SCENE_ALPHAMAP) shade_lane<MODE_PATH, HAR_SCENE_ALPHAMAP_TYPES>(S, P, st, hit, R);      /* a roughness map: the bumpmap set plus the lookup (no `mesh_attribute` texture next to it) */
         else if (S.bsdf_types & HAR_SCENE_ATTR) shade_lane<MODE_PATH, HAR_SCENE_ATTR_TYPES>(S, P, st, hit, R);        /* only scenes with a `mesh_attribute` texture solve the barycentrics */
         else if (S.bsdf_types & HAR_SCENE_BUMPMAP) shade_lane<MODE_PATH, HAR_SCENE_BUMPMAP_TYPES>(S, P, st, hit, R);      /* ... with a `bumpmap` record the bump frame as well */
         else if (S.bsdf_types & HAR_SCENE_NORMALMAP) shade_lane<MODE_PATH, HAR_SCENE_NORMALMAP_TYPES>(S, P, st, hit, R);      /* ... with a `normalmap` record the perturbed and the tangent frames */
         else shade_lane<MODE_PATH, HAR_SCENE_MASK_TYPES>(S, P, st, hit, R);
         /* path.cpp:307-308; in a scene with a `mask` record the vertex decides (a null lobe does not make the sample valid: ShadeResult::non_null, which also follows the
          * scalar branch's early exit, :227-231, where HAR_SHADE_SCALAR_DRAWS is set) */
-        valid_ray = valid_ray || ((S.bsdf_types & HAR_SCENE_MASK) ? R.non_null : hit.t != HAR_INF);
+        valid_ray = valid_ray || ((S.bsdf_types & (HAR_SCENE_MASK | HAR_SCENE_THIN)) ? R.non_null : hit.t != HAR_INF);
         if (R.add_emission) result = Vec3(fma_(R.em_a.x, R.em_b.x, result.x), fma_(R.em_a.y, R.em_b.y, result.y), fma_(R.em_a.z, R.em_b.z, result.z));
         if (R.item && R.item_ray) {                                /* the emitter sample's shadow ray (path.cpp:271-281; ray_test inside sample_emitter_direction) */
             Hit h2; ScalarStack s2;
@@ -382,7 +383,7 @@ extern "C" int har_bsdf_eval_pdf_si_host(const HarSceneDesc *desc, uint32_t bsdf
         if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
         if (n == 0) return 0;
         if (!wi || !uv || !wo || !geom) return har_set_error("null input arrays");
-        for (uint32_t i = 0; i < n; ++i) bsdf_eval_pdf_si_lane<HAR_SCENE_ALPHAMAP>(B.ds, bsdf, c, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
+        for (uint32_t i = 0; i < n; ++i) bsdf_eval_pdf_si_lane<HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN>(B.ds, bsdf, c, n, i, wi, uv, wo, geom, !(active && !active[i]), value, pdf);
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_eval_pdf_si_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_eval_pdf_si_host: ") + ex.what()); }
@@ -401,7 +402,7 @@ extern "C" int har_bsdf_sample_si_host(const HarSceneDesc *desc, uint32_t bsdf, 
         if (ctx) { if (ctx->mode > 1u) return har_set_error("HarBSDFContext::mode must be 0 (TransportMode::Radiance) or 1 (TransportMode::Importance)"); c.mode = ctx->mode; c.type_mask = ctx->type_mask; c.component = ctx->component; }
         if (n == 0) return 0;
         if (!wi || !uv || !sample2 || !geom || !wo || !pdf || !weight) return har_set_error("null input / output arrays");
-        for (uint32_t i = 0; i < n; ++i) bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP>(B.ds, bsdf, c, n, i, wi, uv, sample1, sample2, geom, !(active && !active[i]), wo, pdf, weight, eta, sampled_type, sampled_component);
+        for (uint32_t i = 0; i < n; ++i) bsdf_sample_si_lane<HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN>(B.ds, bsdf, c, n, i, wi, uv, sample1, sample2, geom, !(active && !active[i]), wo, pdf, weight, eta, sampled_type, sampled_component);
         return 0;
     } catch (const std::bad_alloc &) { return har_set_error("har_bsdf_sample_si_host: out of memory"); }
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_si_host: ") + ex.what()); }
@@ -561,7 +562,7 @@ extern "C" int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, c
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);          /* (the host entries always carry the roughness lookup) */
-                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_eval_pdf<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN, true>(S, side, in, ok, Vec3(wo[i], wo[n + i], wo[2 * (size_t) n + i]), ev, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             if (value) { value[i] = ev.value.x; value[n + i] = ev.value.y; value[2 * (size_t) n + i] = ev.value.z; }
             if (pdf) pdf[i] = ev.pdf;
@@ -589,7 +590,7 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
             if (!(active && !active[i])) {
                 BsdfSide side; const bool ok = bsdf_side(S, bsdf, Vec3(wi[i], wi[n + i], wi[2 * (size_t) n + i]), side);
                 TexTaps taps; const BsdfInputs in = bsdf_inputs<HAR_SCENE_ALPHAMAP>(S, S.bsdfs[side.index], uv[i], uv[n + i], taps);
-                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
+                bsdf_sample<HAR_BSDF_ALL_TYPES | HAR_SCENE_NMAP_RECORD_BITS | HAR_SCENE_ALPHAMAP | HAR_SCENE_THIN, true>(S, side, in, ok, sample1 ? sample1[i] : 0.f, sample2[i], sample2[n + i], b, bsdf_side_ctx<true>(S, bsdf, side, c), uv[i], uv[n + i]);
             }
             wo[i] = b.wo.x; wo[n + i] = b.wo.y; wo[2 * (size_t) n + i] = b.wo.z; pdf[i] = b.pdf;
             weight[i] = b.weight.x; weight[n + i] = b.weight.y; weight[2 * (size_t) n + i] = b.weight.z;

@@ -539,9 +539,10 @@ HAR_HD bool bsdf_side(const DScene &S, uint32_t index, Vec3 wi, BsdfSide &side) 
     return false;
 }
 /* BSDF::component_count() of a record: the model's, or for a blend the two nested records' (blendbsdf.cpp:94-97) */
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_THIN bit is read) */
 HAR_HD uint32_t bsdf_record_component_count(const DScene &S, const DBsdf &B) {
-    if (B.type == BSDF_BLEND) return bsdf_component_count(S.bsdfs[B.table].type) + bsdf_component_count(S.bsdfs[B.pad].type);
-    return bsdf_component_count(B.type);
+    if (B.type == BSDF_BLEND) return bsdf_component_count<TYPES>(S.bsdfs[B.table].type) + bsdf_component_count<TYPES>(S.bsdfs[B.pad].type);
+    return bsdf_component_count<TYPES>(B.type);
 }
 /* The context a nested BSDF of a `twosided` record sees (twosided.cpp:129-146, 164-180): the front side and a one-BSDF `twosided` get the caller's context as it
  * is; the back side of a two-BSDF pair gets `component - component_count(front)` (uint32 arithmetic, as in the reference) unless the component is "all" */
@@ -573,7 +574,7 @@ HAR_HD void blend_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
     if (cg) { cg->d[0] = Vec3(0.f); cg->d[1] = Vec3(0.f); }
     if (CTX && ctx.component != 0xffffffffu) {                   /* :167-175, :185-191, :205-215: one nested BSDF, its value scaled, its pdf as it is */
-        const uint32_t n0 = bsdf_component_count(S.bsdfs[child[0]].type);
+        const uint32_t n0 = bsdf_component_count<TYPES>(S.bsdfs[child[0]].type);
         const bool first = ctx.component < n0;
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const float k = first ? 1.f - w : w;
@@ -609,7 +610,7 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
     bool inside; const float w = blend_weight(B, in, inside);
     const uint32_t child[2] = { (uint32_t) B.table, B.pad };
     if (CTX && ctx.component != 0xffffffffu) {                   /* :116-126 */
-        const uint32_t n0 = bsdf_component_count(S.bsdfs[child[0]].type);
+        const uint32_t n0 = bsdf_component_count<TYPES>(S.bsdfs[child[0]].type);
         const bool first = ctx.component < n0;
         BsdfCtx ctx2 = ctx; if (!first) ctx2.component -= n0;
         const DBsdf &N = S.bsdfs[child[first ? 0 : 1]];
@@ -639,9 +640,10 @@ HAR_HD void blend_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, 
  * the kernels of scenes that hold such a record carry this code (TYPES & HAR_SCENE_MASK).  eval_opacity (:225-227) = clip(opacity->eval_1(si), 0, 1): the blend weight's
  * arithmetic, `inside` included.  Components: the nested BSDF's, then the null lobe at the last index (:107-113). */
 HAR_HD float mask_opacity(const DBsdf &B, const BsdfInputs &in, bool &inside) { return blend_weight(B, in, inside); }
+template <uint32_t TYPES = 0u>          /* (only the HAR_SCENE_THIN bit is read: a nested thin dielectric has two components) */
 HAR_HD uint32_t mask_null_index(const DScene &S, const DBsdf &B) {
     const DBsdf &N = S.bsdfs[B.pad];
-    uint32_t c = bsdf_component_count(N.type);
+    uint32_t c = bsdf_component_count<TYPES>(N.type);
     if (N.flags & BF_TWOSIDED) c += N.back >= 0 ? bsdf_component_count(S.bsdfs[N.back].type) : c;        /* twosided.cpp:86-100: the front BSDF's components, then the back's -- also when both are ONE BSDF */
     return c;
 }
@@ -653,7 +655,7 @@ HAR_HD void mask_eval_pdf(const DScene &S, const DBsdf &B, const BsdfInputs &in,
     bool inside; const float o = mask_opacity(B, in, inside);
     bool transmission = true, nested = true;
     if (CTX) {
-        const uint32_t null_index = mask_null_index(S, B);
+        const uint32_t null_index = mask_null_index<TYPES>(S, B);
         transmission = ctx.is_enabled(LOBE_NULL, null_index);
         nested = ctx.component == 0xffffffffu || ctx.component < null_index;
     }
@@ -676,7 +678,7 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
     constexpr uint32_t LEAF = TYPES & ~HAR_SCENE_COMPOSITE;
     bs.wo = Vec3(0.f); bs.pdf = 0.f; bs.weight = Vec3(0.f); bs.eta = 0.f; bs.delta = false; bs.type = 0u; bs.comp = 0u;
     bool inside; float o = mask_opacity(B, in, inside);
-    const uint32_t null_index = mask_null_index(S, B);
+    const uint32_t null_index = mask_null_index<TYPES>(S, B);
     if (CTX) {
         const bool transmission = ctx.is_enabled(LOBE_NULL, null_index), nested = ctx.component == 0xffffffffu || ctx.component < null_index;
         if (!transmission && !nested) return;
@@ -692,6 +694,30 @@ HAR_HD void mask_sample(const DScene &S, const DBsdf &B, const BsdfInputs &in, V
         return;
     }
     bs.wo = Vec3(-wi.x, -wi.y, -wi.z); bs.pdf = 1.f - o; bs.weight = Vec3(1.f); bs.eta = 1.f; bs.delta = true; bs.type = LOBE_NULL; bs.comp = null_index;
+}
+
+/* Kernels of scenes with a thin dielectric (HAR_SCENE_THIN): would bsdf_sample<TYPES>, default context, return the NULL lobe for `sample1` at the record B that serves
+ * this side?  The decision alone, in the arithmetic of the sample functions -- a thin leaf (sample1 <= r' reflects), a mask record (sample1 < opacity takes the nested
+ * BSDF with sample1 / opacity, which may be a thin leaf), a blend record whose sampled child is a thin leaf.  What `path` needs at the LAST vertex of a path, where the
+ * JIT variants draw the sample and valid_ray takes its type (path.cpp:263-267, 307-308) but nothing else of it is used. */
+template <uint32_t TYPES>
+HAR_HD bool sample_takes_null_lobe(const DScene &S, const DBsdf &B, const BsdfInputs &in, Vec3 wi, float s1) {
+    if (B.type == BSDF_THINDIELECTRIC) return !(s1 <= thin_reflectance(B.eta, wi.z));
+    if (B.type == BSDF_MASK) {
+        bool inside; const float o = mask_opacity(B, in, inside);
+        if (!(s1 < o)) return true;
+        BsdfSide ns;
+        if (bsdf_side(S, B.pad, wi, ns) && S.bsdfs[ns.index].type == BSDF_THINDIELECTRIC) return !(s1 / o <= thin_reflectance(S.bsdfs[ns.index].eta, ns.wi.z));
+        return false;
+    }
+    if (B.type == BSDF_BLEND) {
+        bool inside; const float w = blend_weight(B, in, inside);
+        const bool m0 = s1 > w, m1 = s1 <= w;
+        if (!m0 && !m1) return false;
+        const DBsdf &N = S.bsdfs[m0 ? (uint32_t) B.table : B.pad];
+        if (N.type == BSDF_THINDIELECTRIC) return !((m0 ? (s1 - w) / (1.f - w) : s1 / w) <= thin_reflectance(N.eta, wi.z));
+    }
+    return false;
 }
 
 /* ---- NormalMap (src/bsdfs/normalmap.cpp), record type 8: slot 0 is the normal-map colour (Texture::eval_3: a constant rgb or a three-channel bitmap), DBsdf::pad names

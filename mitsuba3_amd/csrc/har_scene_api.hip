@@ -40,7 +40,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
             const DBsdf &b = hs.bsdfs[k];
             uint32_t c = std::min<uint32_t>(b.type, BSDF_TYPE_COUNT - 1u);
             if ((b.flags & BF_TWOSIDED) && b.back >= 0 && hs.bsdfs[(size_t) b.back].type != b.type) c = HAR_MAT_GENERIC;
-            if (b.type == BSDF_BLEND || b.type == BSDF_MASK || b.type == BSDF_NORMALMAP || b.type == BSDF_BUMPMAP) c = HAR_MAT_GENERIC;      /* two models at one vertex / a nested model and a null lobe: the generic bucket of the block-local sort */
+            if (b.type == BSDF_BLEND || b.type == BSDF_MASK || b.type == BSDF_NORMALMAP || b.type == BSDF_BUMPMAP || b.type == BSDF_THINDIELECTRIC) c = HAR_MAT_GENERIC;      /* two models at one vertex / a nested model and a null lobe / the thin leaf, which has no class of its own: the generic bucket of the block-local sort */
             cls[k] = c;
         }
         for (DMesh &m : hs.meshes) { m.pad1 = m.bsdf < cls.size() ? cls[m.bsdf] : 0u; S->mat_classes |= 1u << m.pad1; }
@@ -83,7 +83,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
     D.n_emitters = (uint32_t) hs.emitters.size(); D.n_meshes = (uint32_t) hs.meshes.size();
     D.n_bsdfs = (uint32_t) hs.bsdfs.size(); D.n_insts = (uint32_t) hs.insts.size(); D.n_textures = (uint32_t) hs.textures.size();
     D.env_emitter = hs.env_emitter;
-    D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= (b.type == BSDF_BLEND ? HAR_SCENE_BLEND : b.type == BSDF_MASK ? HAR_SCENE_MASK : b.type == BSDF_NORMALMAP ? HAR_SCENE_NORMALMAP : b.type == BSDF_BUMPMAP ? HAR_SCENE_BUMPMAP : 1u << b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
+    D.bsdf_types = 0; for (const DBsdf &b : hs.bsdfs) D.bsdf_types |= bsdf_scene_bit(b.type) | ((b.flags & BF_TWOSIDED) ? 0x80000000u : 0u);
     for (const DBsdf &b : hs.bsdfs) if (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX)) D.bsdf_types |= HAR_SCENE_ALPHAMAP;      /* a roughness map: the set that also looks the roughness up */
     if (hs.has_envmap || hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) D.bsdf_types |= HAR_SCENE_ENVMAP;
     for (const DEmitter &e : hs.emitters) if (e.type == 7u) D.bsdf_types |= HAR_SCENE_TEXLIGHT;      /* (has_mesh_emitters is set with it: the generic emitter kernels + the texel-distribution code) */

@@ -214,7 +214,7 @@ bool scene_set_bsdf_params_host(HostScene &hs, uint32_t index, const HarBSDF &in
     }
     for (float v : { in.alpha_u, in.alpha_v, in.eta, in.eta_c[0], in.eta_c[1], in.eta_c[2], in.k_c[0], in.k_c[1], in.k_c[2], in.reflectance2[0], in.reflectance2[1], in.reflectance2[2] })
         if (!std::isfinite(v)) { err = "BSDF parameter is not finite"; return false; }
-    const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
+    const bool needs_eta = b.type == BSDF_DIELECTRIC || b.type == BSDF_THINDIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC;
     if (needs_eta && !(in.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
     if (b.type == BSDF_ROUGHPLASTIC && in.eta == 1.f) { err = "The interior and exterior indices of refraction must be positive and differ!"; return false; }
     if (b.type == BSDF_ROUGHPLASTIC && in.alpha_u != in.alpha_v) { err = "The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!"; return false; }
@@ -310,7 +310,7 @@ static bool build_envmap(HostScene &hs, const HarTexture &img, const HarEmitter 
 
 /* the two mesh bits of the public header are the ones the kernels test (har_scene.h) */
 static_assert((uint32_t) MESH_TANGENT_FRAME == HAR_MESH_TANGENT_FRAME && (uint32_t) MESH_FRAME_FLIPPED == HAR_MESH_FRAME_FLIPPED, "HarMesh::flags and DMesh::flags disagree");
-static_assert((uint32_t) BF_NM_FLIP == HAR_BSDF_NM_FLIP && (uint32_t) BF_NM_SHADOW == HAR_BSDF_NM_SHADOW && (uint32_t) BSDF_NORMALMAP == HAR_BSDF_NORMALMAP && (uint32_t) BSDF_BUMPMAP == HAR_BSDF_BUMPMAP, "HarBSDF and DBsdf disagree");
+static_assert((uint32_t) BF_NM_FLIP == HAR_BSDF_NM_FLIP && (uint32_t) BF_NM_SHADOW == HAR_BSDF_NM_SHADOW && (uint32_t) BSDF_NORMALMAP == HAR_BSDF_NORMALMAP && (uint32_t) BSDF_BUMPMAP == HAR_BSDF_BUMPMAP && (uint32_t) BSDF_THINDIELECTRIC == HAR_BSDF_THINDIELECTRIC, "HarBSDF and DBsdf disagree");
 
 bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     if (d.top_mesh_count > d.mesh_count) { err = "top_mesh_count exceeds mesh_count"; return false; }
@@ -365,17 +365,23 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.bsdf_count; ++i) {
         const HarBSDF &b = d.bsdfs[i];
-        if (b.type > BSDF_BUMPMAP) { err = "unsupported BSDF type (diffuse, dielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask, normalmap, bumpmap and twosided are implemented in hip_ad_rgb)"; return false; }
+        if (b.type > BSDF_THINDIELECTRIC) { err = "unsupported BSDF type (diffuse, dielectric, thindielectric, conductor, plastic, roughconductor, roughplastic, blendbsdf, mask, normalmap, bumpmap and twosided are implemented in hip_ad_rgb)"; return false; }
         if (b.texture >= (int32_t) d.texture_count) { err = "BSDF references a texture that does not exist"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
         /* ... and BSDFFlags::Null is part of BSDFFlags::Transmission: `twosided` over a `mask`, on either side */
         if ((b.flags & BF_TWOSIDED) && (b.type == BSDF_MASK || (b.back >= 0 && d.bsdfs[b.back].type == BSDF_MASK))) { err = "twosided over `mask`: Only materials without a transmission component can be nested!"; return false; }
+        /* ... and so is the thin dielectric's transmission lobe (thindielectric.cpp:126; twosided.cpp:79-83) */
+        if ((b.flags & BF_TWOSIDED) && (b.type == BSDF_THINDIELECTRIC || (b.back >= 0 && d.bsdfs[b.back].type == BSDF_THINDIELECTRIC))) { err = "twosided over `thindielectric`: Only materials without a transmission component can be nested!"; return false; }
+        if (b.type == BSDF_THINDIELECTRIC) {
+            if (b.texture >= 0 && (d.textures[b.texture].mode & HAR_TEX_MESH_ATTRIBUTE)) { err = "thindielectric: a `mesh_attribute` texture as specular_transmittance (slot 0) is not supported (a constant or a `bitmap` is)"; return false; }
+            if (b.flags & BF_ALPHA_TEX) { err = "thindielectric: HAR_BSDF_ALPHA_TEX on a `thindielectric` record (the model has no roughness)"; return false; }
+        }
         /* `twosided` over a `normalmap`: the one-BSDF form, twosided(normalmap(X)); a pair with a normalmap on either side is not supported */
         if ((b.flags & BF_TWOSIDED) && b.back >= 0 && (b.type == BSDF_NORMALMAP || d.bsdfs[b.back].type == BSDF_NORMALMAP)) { err = "twosided over `normalmap`: the two-BSDF form is not supported (nest ONE normalmap: twosided(normalmap(X)))"; return false; }
         /* ... and over a `bumpmap`, likewise */
         if ((b.flags & BF_TWOSIDED) && b.back >= 0 && (b.type == BSDF_BUMPMAP || d.bsdfs[b.back].type == BSDF_BUMPMAP)) { err = "twosided over `bumpmap`: the two-BSDF form is not supported (nest ONE bumpmap: twosided(bumpmap(X)))"; return false; }
         if ((b.flags & BF_TWOSIDED) && b.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
-        if ((b.type == BSDF_DIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC) && !(b.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
+        if ((b.type == BSDF_DIELECTRIC || b.type == BSDF_THINDIELECTRIC || b.type == BSDF_ROUGHPLASTIC || b.type == BSDF_PLASTIC) && !(b.eta > 0.f)) { err = "The interior and exterior indices of refraction must be positive!"; return false; }
         if (b.type == BSDF_ROUGHPLASTIC && b.eta == 1.f) { err = "The interior and exterior indices of refraction must be positive and differ!"; return false; }
         if (b.type == BSDF_ROUGHPLASTIC && b.alpha_u != b.alpha_v) { err = "The 'roughplastic' plugin currently does not support anisotropic microfacet distributions!"; return false; }
         DBsdf db{}; db.type = b.type; db.texture = b.texture; db.r = b.reflectance[0]; db.g = b.reflectance[1]; db.b = b.reflectance[2];
@@ -392,9 +398,9 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 if (c.type == BSDF_MASK) { err = "blendbsdf: a nested `mask` BSDF is not supported (put the `mask` outside, over plain BSDF models)"; return false; }
                 if (c.type == BSDF_NORMALMAP) { err = "blendbsdf: a nested `normalmap` BSDF is not supported (nested BSDFs are plain BSDF models)"; return false; }
                 if (c.type == BSDF_BUMPMAP) { err = "blendbsdf: a nested `bumpmap` BSDF is not supported (nested BSDFs are plain BSDF models)"; return false; }
-                if (c.type >= BSDF_TYPE_COUNT || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
-                if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
-                if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_BLEND_SMOOTH;
+                if (!bsdf_is_leaf(c.type) || (c.flags & BF_TWOSIDED)) { err = "blendbsdf: nested BSDFs must be plain BSDF models in this variant"; return false; }
+                if ((b.flags & BF_TWOSIDED) && (c.type == BSDF_DIELECTRIC || c.type == BSDF_THINDIELECTRIC)) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
+                if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR && c.type != BSDF_THINDIELECTRIC) db.flags |= BF_BLEND_SMOOTH;
             }
             db.table = b.nested[0]; db.pad = (uint32_t) b.nested[1];
         } else if (b.type == BSDF_MASK) {                   /* MaskBSDF (mask.cpp:93-114): one nested record, named by index; it may be a `twosided` (one BSDF or a pair) */
@@ -405,8 +411,8 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             if (c.type == BSDF_MASK) { err = "mask: unsupported BSDF type of the nested record: a nested `mask` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type == BSDF_NORMALMAP) { err = "mask: unsupported BSDF type of the nested record: a nested `normalmap` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
             if (c.type == BSDF_BUMPMAP) { err = "mask: unsupported BSDF type of the nested record: a nested `bumpmap` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)"; return false; }
-            if (c.type >= BSDF_TYPE_COUNT) { err = "mask: unsupported BSDF type of the nested record"; return false; }
-            if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_MASK_SMOOTH;
+            if (!bsdf_is_leaf(c.type)) { err = "mask: unsupported BSDF type of the nested record"; return false; }
+            if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR && c.type != BSDF_THINDIELECTRIC) db.flags |= BF_MASK_SMOOTH;
             if ((c.flags & BF_TWOSIDED) && c.back >= 0) {
                 if (c.back >= (int32_t) d.bsdf_count) { err = "twosided BSDF references a back-side BSDF that does not exist"; return false; }
                 const HarBSDF &k = d.bsdfs[c.back];
@@ -424,6 +430,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 err = std::string("normalmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : c.type == BSDF_BUMPMAP ? "bumpmap" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
                 return false;
             }
+            if (c.type == BSDF_THINDIELECTRIC) { err = "normalmap: unsupported BSDF type of the nested record: a nested `thindielectric` is not supported (a pane has no frame to perturb: its lobes are a mirror direction and a straight line)"; return false; }
             if (c.type >= BSDF_TYPE_COUNT) { err = "normalmap: unsupported BSDF type of the nested record"; return false; }
             if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
             if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
@@ -445,6 +452,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 err = std::string("bumpmap: unsupported BSDF type of the nested record: a nested `") + (c.type == BSDF_BLEND ? "blendbsdf" : c.type == BSDF_MASK ? "mask" : c.type == BSDF_BUMPMAP ? "bumpmap" : "normalmap") + "` is not supported (nested BSDFs are plain BSDF models, or `twosided` over them)";
                 return false;
             }
+            if (c.type == BSDF_THINDIELECTRIC) { err = "bumpmap: unsupported BSDF type of the nested record: a nested `thindielectric` is not supported (a pane has no frame to perturb: its lobes are a mirror direction and a straight line)"; return false; }
             if (c.type >= BSDF_TYPE_COUNT) { err = "bumpmap: unsupported BSDF type of the nested record"; return false; }
             if ((b.flags & BF_TWOSIDED) && c.type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }   /* twosided.cpp:79-83 */
             if (c.type != BSDF_DIELECTRIC && c.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
@@ -455,7 +463,8 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
                 if (k.type != BSDF_DIELECTRIC && k.type != BSDF_CONDUCTOR) db.flags |= BF_NM_SMOOTH;
             }
             db.pad = (uint32_t) b.nested[0];
-        } else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH | BF_NM_FLIP | BF_NM_SHADOW);
+        } else if (b.type == BSDF_THINDIELECTRIC) db.flags = 0u;          /* ThinDielectric (thindielectric.cpp:107-128): eta and the two colours, no switch */
+        else db.flags &= ~(uint32_t) (BF_MONO | BF_BLEND_SMOOTH | BF_NM_FLIP | BF_NM_SHADOW);
         /* a roughness map (roughconductor.cpp:195-198): behind HAR_BSDF_ALPHA_TEX -- and only there -- nested[0] / nested[1] name the bitmaps of alpha_u / alpha_v
          * (-1: that axis keeps its constant); `table` / `pad` are free in a roughconductor record */
         if (b.flags & BF_ALPHA_TEX) {
@@ -491,6 +500,9 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
         /* ... and a roughness map: its kernels are the bumpmap set plus the lookup, which does not look attributes up */
         bool any_amap = false; for (const DBsdf &b : hs.bsdfs) any_amap = any_amap || (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX) != 0u);
         if (any_amap) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "roughness map: a scene with a bitmap `alpha` and a `mesh_attribute` texture is not supported"; return false; }
+        /* ... and a thin dielectric: its kernels are the roughness-map set plus the thin leaf */
+        bool any_thin = false; for (const DBsdf &b : hs.bsdfs) any_thin = any_thin || b.type == BSDF_THINDIELECTRIC;
+        if (any_thin) for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "thindielectric: a scene with a `thindielectric` BSDF and a `mesh_attribute` texture is not supported"; return false; }
         for (uint32_t m = 0; m < d.mesh_count; ++m) {
             DMesh &dm = hs.meshes[m];
             const bool under = hs.bsdfs[dm.bsdf].type == BSDF_NORMALMAP;
@@ -534,7 +546,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
         const HarBSDF &b = d.bsdfs[i];
         if (!(b.flags & BF_TWOSIDED) || b.back < 0 || d.bsdfs[b.back].type != BSDF_BLEND) continue;
         for (int k = 0; k < 2; ++k)
-            if (d.bsdfs[d.bsdfs[b.back].nested[k]].type == BSDF_DIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }
+            if (d.bsdfs[d.bsdfs[b.back].nested[k]].type == BSDF_DIELECTRIC || d.bsdfs[d.bsdfs[b.back].nested[k]].type == BSDF_THINDIELECTRIC) { err = "Only materials without a transmission component can be nested!"; return false; }
     }
     for (uint32_t i = 0; i < d.emitter_count; ++i) {
         const HarEmitter &e = d.emitters[i];
