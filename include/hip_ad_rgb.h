@@ -201,6 +201,16 @@ typedef struct HarEmitter {
                              (BitmapTexture::sample_position, bitmap.cpp:622-660, over a DiscreteDistribution2D of the texels' luminance) and the uv mapped onto the shape by
                              Rectangle::eval_parameterization (rectangle.cpp:215-237).  The bitmap's to_uv must map the unit square onto itself (bitmap.cpp:976-992).  Its
                              texels are parameters of the scene (har_scene_set_texture re-derives the distribution) but no gradient is produced for them */
+    /*                       8 = projector (src/emitters/projector.cpp): the reciprocal of the perspective camera, a delta-position emitter that projects its `irradiance`
+                             along the +z axis of to_world -- sampled with MIS weight 1, never hit, not seen by escaping rays.  to_world / to_local = the transform and its
+                             inverse (a singular one is refused), `radiance_texture` = the irradiance bitmap's index in `textures` (its resolution sets the aspect; a
+                             `mesh_attribute` record is refused) or 0xffffffff for the constant irradiance in `radiance` (resolution 1 x 1), normal[0] = `scale`,
+                             normal[1] = x_fov in degrees (parse_fov of `fov` / `focal_length` / `fov_axis` at the texture's aspect, src/render/sensor.cpp:142-190);
+                             `mesh` and `inv_area` are not read.  har_scene_set_delta_emitter replaces to_world / to_local / normal[0..1] (and the constant) in place --
+                             har_scene_set_emitter_radiance / _device refuse a projector by name: the lowered colour is irradiance * scale;
+                             the texels go through har_scene_set_texture.  `prb` gradients: the texels with har_integrator_set_grad_light_texels -- deposited WITHOUT
+                             `scale`, so d / d texels = scale * deposit and d / d scale = <deposit, texels>, exact at zero; a constant through grad_emitters, as
+                             d / d (irradiance * scale).  Vertex-position / instance gradients, har_render_forward and har_multi_create are refused for such a scene */
     uint32_t mesh;
     float radiance[3];
     float to_world[12];   /* column-major 3x4 */
@@ -763,6 +773,14 @@ int har_bsdf_eval_pdf_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSD
                            const uint8_t *active, float *value, float *pdf);
 int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, const HarBSDFContext *ctx, uint32_t n, const float *wi, const float *uv, const float *sample1,
                          const float *sample2, const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *sampled_type, uint32_t *sampled_component);
+/* Emitter::sample_direction of a `projector` (emitter type 8; Projector::sample_direction, src/emitters/projector.cpp:202-244) at n reference points, ref_p 3 x n;
+ * `sample` (2 x n) may be NULL: the projector ignores it.  Out: d 3 x n, dist n, pdf n (1 inside the frustum, 0 outside), p 3 x n, n 3 x n, uv 2 x n (computed for
+ * every lane, whatever it is), spec 3 x n; a lane whose `active` byte is 0 writes zeros.  Other emitter types are refused by name.  The host entry lowers the scene as
+ * har_render_scalar does; the device entry runs the same per-lane function in a kernel on `stream` (DEVICE pointers). */
+int har_emitter_sample_direction_host(const HarSceneDesc *desc, uint32_t emitter, uint32_t n, const float *ref_p, const float *sample, const uint8_t *active,
+                                      float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec);
+int har_emitter_sample_direction(HarScene scene, uint32_t emitter, uint32_t n, const float *ref_p, const float *sample, const uint8_t *active,
+                                 float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec, void *stream);
 /* d value / d {alpha_u, alpha_v, eta, k} of record `bsdf` (a plain model, possibly twosided) at n tuples on the HOST, by the per-lane code of the shading kernels that
  * carry those terms: 3 x n each, default context; a roughness map is looked up at uv. */
 int har_bsdf_eval_extra_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *wi /*[3][n]*/, const float *uv /*[2][n]*/, const float *wo /*[3][n]*/,

@@ -213,6 +213,8 @@ SIGNATURES = {
     "har_bsdf_alpha": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp]),
     "har_bsdf_eval_extra_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
     "har_bsdf_alpha_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, f32p]),
+    "har_emitter_sample_direction_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.c_uint32, f32p, f32p, vp, f32p, f32p, f32p, f32p, f32p, f32p, f32p]),
+    "har_emitter_sample_direction": (C.c_int, [vp, C.c_uint32, C.c_uint32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "har_bsdf_sample_host": (C.c_int, [C.POINTER(HarSceneDesc), C.c_uint32, C.POINTER(HarBSDFContext), C.c_uint32, f32p, f32p, f32p, f32p, vp, f32p, f32p, f32p, f32p, u32p, u32p]),
     "har_render_aovs": (C.c_int, [vp, vp, C.POINTER(HarSensor), C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_uint32, u32p, vp, vp]),
     "har_transform_translate": (C.c_int, [f32p, f32p]),

@@ -597,7 +597,7 @@ def _cube(props):
 _PLUGIN_KINDS = {
     'scene': 'scene', 'path': 'integrator', 'prb': 'integrator', 'aov': 'integrator', 'perspective': 'sensor', 'orthographic': 'sensor', 'thinlens': 'sensor', 'batch': 'sensor', 'hdrfilm': 'film', 'independent': 'sampler',
     'diffuse': 'bsdf', 'dielectric': 'bsdf', 'conductor': 'bsdf', 'plastic': 'bsdf', 'roughconductor': 'bsdf', 'roughplastic': 'bsdf', 'thindielectric': 'bsdf', 'twosided': 'bsdf', 'blendbsdf': 'bsdf', 'mask': 'bsdf', 'normalmap': 'bsdf', 'bumpmap': 'bsdf',
-    'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter',
+    'area': 'emitter', 'constant': 'emitter', 'envmap': 'emitter', 'point': 'emitter', 'spot': 'emitter', 'directional': 'emitter', 'projector': 'emitter',
     'rectangle': 'shape', 'cube': 'shape', 'mesh': 'shape', 'ply': 'shape', 'obj': 'shape', 'serialized': 'shape', 'shapegroup': 'shape', 'instance': 'shape',
     'gaussian': 'rfilter', 'box': 'rfilter', 'tent': 'rfilter', 'mitchell': 'rfilter', 'catmullrom': 'rfilter', 'lanczos': 'rfilter',
     'rgb': 'texture', 'bitmap': 'texture', 'mesh_attribute': 'texture',
@@ -626,7 +626,7 @@ def _object_kind(v):
             return kind
     g = globals()
     for name, kind in (('Sensor', 'sensor'), ('Integrator', 'integrator'), ('ShapeGroup', 'shape'), ('Instance', 'shape'), ('Scene', 'scene'), ('AreaLight', 'emitter'),
-                       ('ConstantEmitter', 'emitter'), ('EnvmapEmitter', 'emitter'), ('PointLight', 'emitter'), ('SpotLight', 'emitter'), ('DirectionalEmitter', 'emitter')):
+                       ('ConstantEmitter', 'emitter'), ('EnvmapEmitter', 'emitter'), ('PointLight', 'emitter'), ('SpotLight', 'emitter'), ('DirectionalEmitter', 'emitter'), ('Projector', 'emitter')):
         if name in g and isinstance(v, g[name]):
             return kind
     return None
@@ -1906,6 +1906,74 @@ class DirectionalEmitter:
         self.irradiance = _rgb_value(props.get('irradiance', {'type': 'rgb', 'value': 1.0}), 1.0, bounded=False, uniform='irradiance')      # get_emissive_texture("irradiance", 1.f), :80
 
 
+def _parse_fov(props, aspect):
+    """parse_fov (src/render/sensor.cpp:142-196): the horizontal field of view in degrees from `fov` + `fov_axis`, or `focal_length`, at `aspect` = width / height"""
+    if 'fov' in props and 'focal_length' in props:
+        raise RuntimeError("Please specify either a focal length ('focal_length') or a field of view ('fov')!")
+    if 'fov' in props:
+        fov = float(props['fov']); axis = str(props.get('fov_axis', 'x')).lower()
+        if axis == 'smaller':
+            axis = 'y' if aspect > 1 else 'x'
+        elif axis == 'larger':
+            axis = 'x' if aspect > 1 else 'y'
+    else:
+        fl = str(props.get('focal_length', '50mm'))
+        try:
+            value = float(fl[:-2] if fl.endswith('mm') else fl)
+        except ValueError:
+            raise RuntimeError("Could not parse the focal length (must be of the form <x>mm, where <x> is a positive integer)!")
+        fov = 2.0 * math.degrees(math.atan(math.sqrt(36 * 36 + 24 * 24) / (2.0 * value))); axis = 'diagonal'
+    if axis == 'x':
+        result = fov
+    elif axis == 'y':
+        result = math.degrees(2.0 * math.atan(math.tan(0.5 * math.radians(fov)) * aspect))
+    elif axis == 'diagonal':
+        width = 2.0 * math.tan(0.5 * math.radians(fov)) / math.sqrt(1.0 + 1.0 / (aspect * aspect))
+        result = math.degrees(2.0 * math.atan(width * 0.5))
+    else:
+        raise RuntimeError("The 'fov_axis' parameter must be set to one of 'smaller', 'larger', 'diagonal', 'x', or 'y'!")
+    if result <= 0.0 or result >= 180.0:
+        raise RuntimeError("The horizontal field of view must be in the range [0, 180]!")
+    return result
+
+
+class Projector:
+    """Projector (src/emitters/projector.cpp): the reciprocal of the perspective camera -- a point at the origin of `to_world` that projects `irradiance` (an `rgb`
+    value, or a `bitmap` of three channels or one) along the local +z axis through the perspective camera's pixel-to-direction map, times `scale`.  `fov`, `focal_length`
+    and `fov_axis` are read as a sensor reads them (parse_fov), at the aspect of the irradiance texture (1 for a constant).  EmitterFlags::DeltaPosition: only emitter
+    sampling finds it, with MIS weight 1.  Not implemented (nothing on the `path` / `prb` route calls them): sample_ray, sample_position, sample_wavelengths and
+    eval_direction on its own."""
+
+    def __init__(self, props):
+        _check_props("projector", props, ('irradiance', 'scale', 'to_world', 'fov', 'focal_length', 'fov_axis', 'sampling_weight'), free_children=False)
+        self.sampling_weight = _sampling_weight(props)
+        self.to_world = props.get('to_world', ScalarTransform4f())
+        if abs(float(np.linalg.det(np.asarray(self.to_world.matrix, np.float64).reshape(4, 4)))) == 0.0:
+            raise RuntimeError("projector: to_world is singular")
+        self.scale = float(np.float32(props.get('scale', 1.0)))                    # :124
+        if not math.isfinite(self.scale):
+            raise RuntimeError("projector: `scale` is not finite")
+        irr = props.get('irradiance', {'type': 'rgb', 'value': 1.0})              # get_emissive_texture("irradiance", 1.f), :126
+        self.texture = None; self.tex_mode = 0; self.tex_to_uv = None; self.tex_index = None; self.channels = 3
+        if isinstance(irr, dict) and irr.get('type') == 'mesh_attribute':
+            raise RuntimeError("projector: a `mesh_attribute` as property \"irradiance\" is not implemented by hip_ad_rgb (an emitter has no shape to read an attribute of)")
+        if isinstance(irr, dict) and irr.get('type') == 'bitmap':
+            raw = irr['data'] if 'data' in irr else (irr['bitmap'].data if isinstance(irr.get('bitmap'), Bitmap) else None)
+            if raw is not None and (len(raw.shape) == 2 or raw.shape[2] == 1):
+                self.channels = 1
+            self.texture, self.tex_mode, self.tex_to_uv = _bitmap_from_props(irr)
+            if not np.isfinite(self.texture).all():
+                raise RuntimeError("projector: the irradiance bitmap must be finite")
+            self.irradiance = _f32([0.0, 0.0, 0.0])
+            h, w = self.texture.shape[:2]
+        else:
+            if isinstance(irr, dict) and irr.get('type') != 'rgb':
+                raise RuntimeError("projector: property \"irradiance\" takes an `rgb` value or a `bitmap` in hip_ad_rgb (texture plugin \"%s\" is not implemented for it)" % irr.get('type'))
+            self.irradiance = _rgb_value(irr, 1.0, bounded=False)
+            h, w = 1, 1                                                            # a uniform texture's resolution() is 1 x 1 (texture.cpp)
+        self.x_fov = float(np.float32(_parse_fov(props, w / float(h))))            # :128-129
+
+
 class EnvmapEmitter:
     """EnvironmentMapEmitter (src/emitters/envmap.cpp): lat-long radiance image, importance sampled by luminance * sin(theta)."""
 
@@ -2270,8 +2338,9 @@ class Integrator:
                 out[k] = torch.zeros(1 if what == "thin_ior" else 3, dtype=torch.float32, device=dev)
         if self.light_texel_gradients:            # the light's bitmap is a texture of the scene like any other: its gradient sits in its entry of grad_textures
             for k, (kind, i) in scene._pose_keys().items():
-                if kind == "emitter_tex":
+                if kind == "emitter_tex" and scene.emitters[i].get("type") != 8:
                     out[k] = g_tex[scene.emitters[i]["light"].tex_index]
+        out.update(scene._projector_gradients(g_tex if self.light_texel_gradients else None, g_emit if self.emitter_gradients else None, out))
         if envmap_keys:
             out.update(scene._envmap_gradients(g_tex[scene.emitters[envmap_keys["env_data"][1]]["mesh"]], envmap_keys))
         out.update(g_pos)
@@ -2305,6 +2374,10 @@ def _render_forward(self, scene, params=None, sensor=0, seed=0, spp=0, tangents=
     if tangents is None:
         tangents = {k: v.grad for k, v in (params or {}).items() if getattr(v, 'requires_grad', False) and getattr(v, 'grad', None) is not None}
     keys = scene._param_keys(); akeys = scene._attr_keys()
+    proj = [k for k in tangents if scene._pose_keys().get(k, (None,))[0] in ("proj_scale", "emitter_tex") and scene.emitters[scene._pose_keys()[k][1]].get("type") == 8]
+    proj += [k for k in tangents if k in scene._param_keys() and scene._param_keys()[k][0] == "emit" and scene.emitters[scene._param_keys()[k][1]].get("type") == 8]
+    if proj:
+        raise RuntimeError("projector: render_forward(): forward-mode tangents of %s are not implemented in hip_ad_rgb (use render_backward)" % proj)
     unknown = [k for k in tangents if k not in keys and k not in akeys]
     if unknown:
         raise RuntimeError("render_forward(): %s are not differentiable parameters of the `prb` forward mode (available: %s)" % (unknown, sorted(keys)))
@@ -2616,7 +2689,7 @@ class Scene:
         # Scene::emitters() order = declaration order of the children (scene.cpp:40-70): shapes with an area emitter and
         # stand-alone emitters; the uniform emitter selection of sample_emitter() depends on it
         self._emitter_order = [key for key, obj in children.items()
-                               if (isinstance(obj, Mesh) and obj.emitter is not None) or isinstance(obj, (ConstantEmitter, EnvmapEmitter, PointLight, SpotLight, DirectionalEmitter))]
+                               if (isinstance(obj, Mesh) and obj.emitter is not None) or isinstance(obj, (ConstantEmitter, EnvmapEmitter, PointLight, SpotLight, DirectionalEmitter, Projector))]
         self.emitters = [None] * len(self._emitter_order)
         if sum(isinstance(o, (ConstantEmitter, EnvmapEmitter)) for o in children.values()) > 1:
             raise RuntimeError("Only one environment emitter can be specified per scene.")
@@ -2635,6 +2708,14 @@ class Scene:
             elif isinstance(obj, DirectionalEmitter):           # HarEmitter type 6: `radiance` = irradiance, the transform (light travels along its +z)
                 self.emitters[self._emitter_order.index(key)] = dict(type=6, mesh=0xffffffff, radiance=obj.irradiance, to_world=obj.to_world.col_major_3x4(),
                                                                      to_local=obj.to_world.inverse().col_major_3x4(), normal=[0.0] * 3, inv_area=0.0, sampling_weight=obj.sampling_weight)
+            elif isinstance(obj, Projector):                    # HarEmitter type 8: transform + inverse, normal = (scale, x_fov, -), the bitmap in the texture table
+                tex = 0xffffffff
+                if obj.texture is not None:
+                    tex = obj.tex_index = len(self.textures)
+                    self.textures.append(obj.texture); self.texture_modes.append(obj.tex_mode); self.texture_to_uv.append(obj.tex_to_uv)
+                self.emitters[self._emitter_order.index(key)] = dict(type=8, mesh=0xffffffff, radiance=obj.irradiance, to_world=obj.to_world.col_major_3x4(),
+                                                                     to_local=obj.to_world.inverse().col_major_3x4(), normal=[obj.scale, obj.x_fov, 0.0], inv_area=0.0,
+                                                                     sampling_weight=obj.sampling_weight, radiance_texture=tex, light=obj if obj.texture is not None else None)
             elif isinstance(obj, EnvmapEmitter):                # the radiance image travels in the texture table
                 self.emitters[self._emitter_order.index(key)] = dict(
                     type=2, mesh=len(self.textures), radiance=[obj.scale, 1.0 if obj.mis_compensation else 0.0, 0.0],
@@ -3035,6 +3116,8 @@ class Scene:
                 keys[key + ".intensity.value"] = ("emit", i)
             elif e["type"] == 6:                                  # DirectionalEmitter::traverse (directional.cpp:93-97)
                 keys[key + ".irradiance.value"] = ("emit", i)
+            elif e["type"] == 8 and e.get("light") is None:       # Projector::traverse (projector.cpp:136-141): `irradiance` -- a uniform one here, a bitmap under _pose_keys
+                keys[key + ".irradiance.value"] = ("emit", i)
         return keys
 
     @_static_table
@@ -3411,6 +3494,11 @@ class Scene:
                                 # requires_grad) produces their gradients
                 keys[key + ".scale"] = ("env_scale", i); keys[key + ".to_world"] = ("emitter_to_world", i)
                 keys[key + ".data"] = ("env_data", i)          # the texel tensor in the reference's layout: H x (W + 2) x 3, real column x at x + 1 (envmap.cpp:146-188)
+            if t == 8:          # Projector::traverse (projector.cpp:136-141): `scale` (Differentiable: with the irradiance's gradient switch), `to_world` (NonDifferentiable);
+                                # a bitmap irradiance: `data` (Differentiable: `light_texel_gradients`) and `to_uv`, BitmapTexture::traverse (bitmap.cpp:463-475)
+                keys[key + ".scale"] = ("proj_scale", i); keys[key + ".to_world"] = ("emitter_to_world", i)
+                if self.emitters[i].get("light") is not None:
+                    keys[key + ".irradiance.data"] = ("emitter_tex", i); keys[key + ".irradiance.to_uv"] = ("emitter_to_uv", i)
             if t == 5:          # SpotLight::traverse (spot.cpp:115-116): the cone, in degrees -- updatable here; their gradient (the reference marks them Differentiable) is refused
                 keys[key + ".cutoff_angle"] = ("cutoff_angle", i); keys[key + ".beam_width"] = ("beam_width", i)
             # Emitter::traverse (src/render/emitter.cpp:13): `sampling_weight`, NonDifferentiable; an area light is a child of its shape ('<shape>.emitter.*')
@@ -3447,8 +3535,11 @@ class Scene:
         if kind == "env_data":             # one halo column on each side carrying a copy of the opposite edge (envmap.cpp:146-188, refresh_halo)
             t = np.asarray(self.textures[self.emitters[b]["mesh"]], np.float32)
             return np.ascontiguousarray(np.concatenate([t[:, -1:], t, t[:, :1]], axis=1))
+        if kind == "proj_scale":
+            return np.asarray([self.emitters[b]["normal"][0]], np.float32)
         if kind == "emitter_tex":
-            return np.array(self.emitters[b]["light"].texture, np.float32)
+            light = self.emitters[b]["light"]
+            return np.array(light.texture[:, :, :1] if getattr(light, 'channels', 3) == 1 else light.texture, np.float32)
         if kind in ("to_uv", "emitter_to_uv"):
             if kind == "emitter_to_uv":
                 b = self.emitters[b]["light"]
@@ -3563,6 +3654,15 @@ class Scene:
         if kind == "emitter_tex":      # BitmapTexture::parameters_changed -> rebuild_internals (bitmap.cpp:484-493): new texels, new texel distribution
             light = self.emitters[b]["light"]
             v = np.ascontiguousarray(np.asarray(value, np.float32))
+            if self.emitters[b].get("type") == 8:      # a projector's irradiance: any finite texels (nothing is sampled from them); a bitmap of another resolution is refused
+                h, w = light.texture.shape[:2]
+                if v.shape != (h, w, light.channels) or not np.isfinite(v).all():
+                    raise RuntimeError("projector: the irradiance bitmap must keep its shape %s and be finite" % ((h, w, light.channels),))
+                v = np.ascontiguousarray(np.repeat(v, 3, axis=2)) if light.channels == 1 else v
+                light.texture = v; self.textures[light.tex_index] = v
+                if self._h is not None:
+                    check(lib().har_scene_set_texture(self._h, light.tex_index, _fp(v)))
+                return
             if v.shape != light.texture.shape or not np.isfinite(v).all():
                 raise RuntimeError("area: the radiance bitmap must keep its shape %s and be finite" % (light.texture.shape,))
             if not (v >= 0).all() or float(v.sum()) <= 0.0:
@@ -3581,7 +3681,7 @@ class Scene:
             if not np.isfinite(m).all() or float(np.linalg.det(m[:2, :2].astype(np.float64))) == 0.0:
                 raise RuntimeError("bitmap: 'to_uv' is singular")
             rows = [float(x) for x in m[:2, :].reshape(-1)]
-            if kind == "emitter_to_uv":
+            if kind == "emitter_to_uv" and not isinstance(b, Projector):          # (a projector never samples positions from its bitmap)
                 _check_sampling_transform(rows)
             b.tex_to_uv = rows; self.texture_to_uv[b.tex_index] = rows
             if self._h is not None:
@@ -3605,6 +3705,11 @@ class Scene:
             if not math.isfinite(sc):
                 raise RuntimeError("envmap: 'scale' is not finite")
             e["radiance"] = [sc] + [float(x) for x in e["radiance"][1:]]
+        elif kind == "proj_scale":
+            sc = float(np.asarray(value, np.float32).reshape(-1)[0])
+            if not math.isfinite(sc):
+                raise RuntimeError("projector: `scale` is not finite")
+            e["normal"] = [sc] + [float(x) for x in e["normal"][1:]]
         elif kind in ("cutoff_angle", "beam_width"):
             nrm = [float(x) for x in e["normal"]]; nrm[0 if kind == "cutoff_angle" else 1] = float(np.asarray(value, np.float32).reshape(-1)[0])
             e["normal"] = nrm                                        # the pair is validated once both values of an update() are in (_validate_spots)
@@ -3620,7 +3725,7 @@ class Scene:
             inv = np.linalg.inv(m)
             e["to_world"] = [float(x) for x in m[:3, :].T.reshape(-1)]; e["to_local"] = [float(x) for x in inv[:3, :].T.reshape(-1)]
         self.emitters[b] = e
-        if self._h is not None and e.get("type", 0) in (4, 5, 6) and kind not in ("cutoff_angle", "beam_width"):
+        if self._h is not None and e.get("type", 0) in (4, 5, 6, 8) and kind not in ("cutoff_angle", "beam_width"):
             # the record of a delta emitter is re-lowered IN PLACE (har_scene_set_delta_emitter): the scene handle and the acceleration data survive a moved light.
             # (cone values arrive one by one and are validated as a pair at the end of update(): _validate_spots pushes the record then)
             self._push_delta_emitter(b)
@@ -3649,6 +3754,32 @@ class Scene:
         g_data = torch.zeros((D.shape[0], D.shape[1] + 2, 3), dtype=torch.float32, device=D.device)
         g_data[:, 1:-1, :] = D * float(self.emitters[i]["radiance"][0])
         return {key_d: g_data, key_s: (D.double() * data.double()).sum().to(torch.float32).reshape(1)}
+
+    def _projector_gradients(self, g_tex, g_emit, out):
+        """the gradients of the projectors' `irradiance` and `scale` from what the library deposits.  A bitmap (with `light_texel_gradients`): D, the adjoint of the
+        lookup WITHOUT `scale` in the bitmap's entry of grad_textures -- d / d data = scale * D (summed over the channels of a one-channel bitmap, which is stored three
+        times), d / d scale = <D, data>.  A constant (with `emitter_gradients`): the row of grad_emitters is d / d (irradiance * scale) -- d / d irradiance = scale * row,
+        d / d scale = <row, irradiance>.  Both are exact where `scale`, texels or the colour are zero."""
+        torch = _torch(); res = {}
+        keys = {(kind, i): k for k, (kind, i) in self._pose_keys().items() if kind in ("proj_scale", "emitter_tex")}
+        for i, e in enumerate(self.emitters):
+            if e.get("type") != 8:
+                continue
+            scale = float(np.float32(e["normal"][0])); light = e.get("light")
+            if light is not None and g_tex is not None:
+                D = g_tex[light.tex_index]
+                data = torch.as_tensor(np.asarray(light.texture, np.float32), device=D.device)
+                g = D * scale
+                res[keys[("emitter_tex", i)]] = g.sum(dim=2, keepdim=True) if light.channels == 1 else g
+                res[keys[("proj_scale", i)]] = (D.double() * data.double()).sum().to(torch.float32).reshape(1)
+            elif light is None and g_emit is not None:
+                row = g_emit[i]
+                c = torch.as_tensor(np.asarray(e["radiance"], np.float32), device=row.device)
+                for k, (kind, b) in self._param_keys().items():
+                    if kind == "emit" and b == i:
+                        res[k] = row * scale
+                res[keys[("proj_scale", i)]] = (row.double() * c.double()).sum().to(torch.float32).reshape(1)
+        return res
 
     def _gradients(self, g_refl, g_tex, g_emit=None, alpha_maps=False):
         out = {}
@@ -3742,8 +3873,10 @@ class SceneParameters(dict):
         if key in sc._position_keys() or key in sc._instance_keys() or key in sc._rect_keys():
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
         if sc._pose_keys().get(key, (None,))[0] == "emitter_tex":
+            if sc.emitters[sc._pose_keys()[key][1]].get("type") == 8:          # projector.cpp:139: Differentiable
+                return ParamFlags.Differentiable
             return ParamFlags.Differentiable | ParamFlags.Discontinuous
-        if sc._pose_keys().get(key, (None,))[0] in ("env_data", "env_scale"):          # envmap.cpp:203-208; `prb` with `envmap_gradients`
+        if sc._pose_keys().get(key, (None,))[0] in ("env_data", "env_scale", "proj_scale"):          # envmap.cpp:203-208; `prb` with `envmap_gradients`; projector.cpp:138
             return ParamFlags.Differentiable
         return ParamFlags.NonDifferentiable
 
@@ -4003,6 +4136,8 @@ class SceneParameters(dict):
                 continue                    # the value the scene already holds (values without a version counter -- numpy arrays -- are pushed every call)
             new_mark = (t, getattr(t, "_version", None), sc._h.value if sc._h is not None else None)      # recorded once the push below went through
             on_gpu = hasattr(t, "is_cuda") and t.is_cuda and sc._h is not None
+            if kind == "emit" and sc.emitters[b].get("type") == 8:
+                on_gpu = False          # a projector's record holds irradiance * scale: re-lowered on the host (har_scene_set_delta_emitter)
             if on_gpu:
                 # the scene's copy is the value AT update(): snapshot on the device (a later in-place edit of the tensor is not an update), host mirror refreshed lazily
                 v = t.detach().to(torch.float32).contiguous()
@@ -4030,7 +4165,9 @@ class SceneParameters(dict):
             if kind == "emit":
                 sc._device_values.pop(("emit", b), None)
                 sc.emitters[b]["radiance"] = np.ascontiguousarray(v.reshape(3))
-                if sc._h is not None:
+                if sc._h is not None and sc.emitters[b].get("type") == 8:
+                    sc._push_delta_emitter(b)
+                elif sc._h is not None:
                     check(lib().har_scene_set_emitter_radiance(sc._h, b, _fp(sc.emitters[b]["radiance"])))
             elif kind == "tex":
                 sc._device_values.pop(("tex", b.tex_index), None)
@@ -4277,7 +4414,7 @@ def _mk_scene(props, named, key):
         if k == 'type' or k in children:
             continue
         obj = _resolve(v, named, k) if isinstance(v, dict) else v
-        if isinstance(obj, (Mesh, Sensor, Integrator, BSDF, ShapeGroup, Instance, ConstantEmitter, EnvmapEmitter, PointLight, SpotLight, DirectionalEmitter)):
+        if isinstance(obj, (Mesh, Sensor, Integrator, BSDF, ShapeGroup, Instance, ConstantEmitter, EnvmapEmitter, PointLight, SpotLight, DirectionalEmitter, Projector)):
             if isinstance(obj, ShapeGroup):
                 named[k] = obj
             children[k] = obj
@@ -4364,7 +4501,7 @@ for _name, _fn in {
     'hdrfilm': lambda p, n, k: Film(p),
     'independent': lambda p, n, k: Sampler(p),
     'diffuse': lambda p, n, k: BSDF(p, id=k), 'dielectric': lambda p, n, k: BSDF(p, id=k), 'roughconductor': lambda p, n, k: BSDF(p, id=k),
-    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'thindielectric': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'bumpmap': _mk_bumpmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p),
+    'roughplastic': lambda p, n, k: BSDF(p, id=k), 'conductor': lambda p, n, k: BSDF(p, id=k), 'plastic': lambda p, n, k: BSDF(p, id=k), 'thindielectric': lambda p, n, k: BSDF(p, id=k), 'twosided': _mk_twosided, 'blendbsdf': _mk_blendbsdf, 'mask': _mk_mask, 'normalmap': _mk_normalmap, 'bumpmap': _mk_bumpmap, 'constant': lambda p, n, k: ConstantEmitter(p), 'envmap': lambda p, n, k: EnvmapEmitter(p), 'point': lambda p, n, k: PointLight(p), 'spot': lambda p, n, k: SpotLight(p), 'directional': lambda p, n, k: DirectionalEmitter(p), 'projector': lambda p, n, k: Projector(p),
     'rectangle': lambda p, n, k: _shape_common(_rectangle(p), p, n),
     'cube': lambda p, n, k: _shape_common(_cube(p), p, n),
     'mesh': _mk_mesh, 'ply': _mk_ply, 'obj': _mk_obj, 'serialized': _mk_serialized,
@@ -4421,7 +4558,7 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
             raise RuntimeError("scalar_rgb renders are not differentiable (the reference's scalar variants have no AD either); use hip_ad_rgb")
         return _render_scalar(scene, integrator, sensor, seed, spp)
     keys = [k for k, v in (params or {}).items() if getattr(v, 'requires_grad', False)]
-    fixed = [k for k in keys if k in scene._pose_keys() and scene._pose_keys()[k][0] not in ("emitter_tex", "env_data", "env_scale")]      # (a light's radiance bitmap IS differentiable: area.cpp:64-70; an environment map's `data` and `scale`: envmap.cpp:203-208)
+    fixed = [k for k in keys if k in scene._pose_keys() and scene._pose_keys()[k][0] not in ("emitter_tex", "env_data", "env_scale", "proj_scale")]      # (a light's radiance bitmap IS differentiable: area.cpp:64-70; an environment map's `data` and `scale`: envmap.cpp:203-208)
     if fixed:       # ParamFlags::NonDifferentiable in the reference's traverse(): dr.enable_grad on them has no effect there; here it is said
         raise RuntimeError("%s are not differentiable parameters in hip_ad_rgb (placement of sensors and delta emitters: ParamFlags::NonDifferentiable in the reference; "
                            "a spot light's cutoff_angle / beam_width: Differentiable there, updatable but without a gradient here)" % fixed)
@@ -4450,8 +4587,11 @@ def render(scene, params=None, sensor=0, integrator=None, seed=0, seed_grad=0, s
             overrides['shape_gradients'] = sorted(set(list(integrator_ad.shape_gradients or [])) | set(shape_keys))
         if any((k in scene._bsdf_param_keys() and scene._bsdf_param_keys()[k][0] not in _THIN_PARAMS) or getattr(scene._param_keys().get(k, (None, None))[1], 'kind', None) == 'alphamap' for k in keys) and not integrator_ad.bsdf_parameter_gradients:
             overrides['bsdf_parameter_gradients'] = True
-        if any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) and not integrator_ad.light_texel_gradients:
+        proj_scales = [scene._pose_keys()[k][1] for k in keys if scene._pose_keys().get(k, (None,))[0] == "proj_scale"]          # a projector's `scale`: the switch of its irradiance
+        if (any(scene._pose_keys().get(k, (None,))[0] == "emitter_tex" for k in keys) or any(scene.emitters[i].get("light") is not None for i in proj_scales)) and not integrator_ad.light_texel_gradients:
             overrides['light_texel_gradients'] = True
+        if any(scene.emitters[i].get("light") is None for i in proj_scales) and not integrator_ad.emitter_gradients:
+            overrides['emitter_gradients'] = True
         if any(scene._pose_keys().get(k, (None,))[0] in ("env_data", "env_scale") for k in keys) and not integrator_ad.envmap_gradients:
             overrides['envmap_gradients'] = True
         if any(v[0] == "emit" for k, v in scene._param_keys().items() if k in keys) and not integrator_ad.emitter_gradients:

@@ -329,6 +329,10 @@ HAR_HD bool bsdf_is_smooth(const DBsdf &B) { return B.type != BSDF_DIELECTRIC &&
 /* ... and an area light that radiates a BITMAP (emitter type 7): its texel-distribution code costs the generic kernels registers they do not have (128, spills), so
  * only scenes with such a light run kernels that carry it: TYPES = HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT */
 #define HAR_SCENE_TEXLIGHT 0x400u
+/* ... and a `projector` (emitter type 8).  A presence bit of DScene::bsdf_types only, never a template argument: a scene that holds one also sets HAR_SCENE_TEXLIGHT and
+ * runs that kernel set (its emitter dispatch carries the projector's branch next to the bitmap light's), so the kernels of every other scene are what they were; the host
+ * reads the bit where something is refused for such a scene (vertex-position / instance gradients, forward-mode tangents, device groups) */
+#define HAR_SCENE_PROJECTOR 0x40000u
 /* ... and a `blendbsdf` record (type 6): two models run at one vertex, which no kernel of another scene pays for.  A scene with such a record runs ONE widest
  * instantiation per launch, TYPES = HAR_BSDF_ALL_TYPES | HAR_SCENE_ENVMAP | HAR_SCENE_TEXLIGHT | HAR_SCENE_BLEND; every line of blend code sits behind a test of this bit */
 #define HAR_SCENE_BLEND 0x800u

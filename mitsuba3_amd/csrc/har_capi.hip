@@ -696,7 +696,7 @@ static int backward_range(HarScene S, HarIntegrator I, const HarSensor *sensor, 
     const char *const comp = thin ? "thindielectric" : amap_only ? "roughness map" : bump ? "bumpmap" : nmap ? "normalmap" : attr_only ? "mesh_attribute" : (S->ds.bsdf_types & HAR_SCENE_MASK) ? "mask" : "blendbsdf";      /* (the refusals below are scene-wide: one such record anywhere in the scene) */
     /* ... and the texels of the environment map (har_integrator_set_grad_envmap): the same two terms, the same route */
     const bool env_texels = I->set.grad_envmap && S->hs.has_envmap;
-    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !env_texels && !blend && chunk <= (1u << 29)) ? 2 : 1;
+    int tape = !tape_ok ? 0 : (tape_kind_env >= 2 && !I->set.grad_bsdf_params && !light_texels && !env_texels && !blend && !(S->ds.bsdf_types & HAR_SCENE_PROJECTOR) /* (the record tape does not carry ds.uv: a projector scene takes the state tape) */ && chunk <= (1u << 29)) ? 2 : 1;
     tape = std::min(tape, I->bw_tape_max);
     /* The tapes are the large workspaces (record tape 69 B, state tape 115 B per lane and bounce against 25 B for the lane-indexed cache: 28 - 90 GB for a 2^26-lane chunk
      * at max_depth 6 - 12).  When the device -- or the host's allocator pool, shared with the caller's tensors -- cannot hold one, step down instead of failing: record
@@ -805,6 +805,7 @@ int har_render_forward(HarScene S, HarIntegrator I, const HarSensor *sensor, uin
     if (I->set.type != HAR_INTEGRATOR_PRB) return fail("render_forward is implemented by the `prb` integrator");
     if (!film || !tangent_reflectance) return fail("null film / tangent buffers");
     if (I->shape_on) return fail("render_forward: tangents of vertex positions are not implemented (use render_backward for shape gradients)");
+    if (S->ds.bsdf_types & HAR_SCENE_PROJECTOR) return fail("projector: render_forward is not implemented for a scene that holds a `projector` (forward-mode tangents of its irradiance and `scale`)");
     if ((S->ds.bsdf_types & HAR_SCENE_THIN) && (S->ds.bsdf_types & HAR_SCENE_WIDE_ROUTE) != HAR_SCENE_THIN)
         return fail("thindielectric: render_forward is not implemented for a scene that holds a `thindielectric` record next to a blendbsdf / mask / normalmap / bumpmap record, a roughness map or a `mesh_attribute` texture (that kernel set has no item-writing adjoint)");
     if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: render_forward is not implemented for a scene with a bitmap `alpha` (forward-mode tangents of alpha texels)");
@@ -875,6 +876,7 @@ int har_integrator_set_grad_positions(HarIntegrator I, HarScene S, float *const 
         const size_t nm = S->hs.meshes.size();
         /* their adjoint goes through items, which carry one (record, direct, relative) triple per vertex: a blend vertex has three */
         /* ... and the barycentrics an attribute is looked up at move with the positions (Mesh::barycentric_coordinates): not differentiated */
+        if (S->ds.bsdf_types & HAR_SCENE_PROJECTOR) return fail("projector: vertex-position gradients are not produced for a scene that holds a `projector` (the uv that eval_direction re-attaches to a moving shading point, projector.cpp:282-288, is not differentiated)");
         if (S->ds.bsdf_types & HAR_SCENE_THIN) return fail("thindielectric: vertex-position gradients are not produced for a scene with a `thindielectric` record");
         if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("vertex-position gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: vertex-position gradients are not produced for a scene with a bitmap `alpha`");
@@ -922,6 +924,7 @@ int har_integrator_set_grad_instances(HarIntegrator I, HarScene S, float *grad_t
     uint32_t n = 0;
     if (grad_to_world) {
         if (!S) return fail("null scene");
+        if (S->ds.bsdf_types & HAR_SCENE_PROJECTOR) return fail("projector: instance to_world gradients are not produced for a scene that holds a `projector` (the uv that eval_direction re-attaches to a moving shading point, projector.cpp:282-288, is not differentiated)");
         if (S->ds.bsdf_types & HAR_SCENE_THIN) return fail("thindielectric: instance to_world gradients are not produced for a scene with a `thindielectric` record");
         if (S->ds.bsdf_types & HAR_SCENE_ATTR) return fail("instance to_world gradients are not produced for a scene with a `mesh_attribute` texture");
         if (S->ds.bsdf_types & HAR_SCENE_ALPHAMAP) return fail("roughness map: instance to_world gradients are not produced for a scene with a bitmap `alpha`");

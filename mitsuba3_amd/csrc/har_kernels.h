@@ -210,6 +210,8 @@ void launch_api_bsdf_sample_si(hipStream_t s, const DScene &S, uint32_t bsdf, co
 void launch_api_bsdf_alpha(hipStream_t s, const DScene &S, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v);
 void launch_api_bsdf_eval_pdf(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const uint8_t *active,
                               float *value, float *pdf);
+void launch_api_emitter_sample_direction(hipStream_t s, const DScene &S, uint32_t emitter, uint32_t n, const float *ref_p, const uint8_t *active,
+                                         float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec);
 void launch_api_bsdf_sample(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *s1, const float *s2,
                             const uint8_t *active, float *wo, float *pdf, float *weight, float *eta, uint32_t *stype, uint32_t *scomp);
 /* ax / ay: the aperture samples of a thin lens (null = (0.5, 0.5), the centre of the lens; pinhole cameras ignore them) */

@@ -2924,6 +2924,17 @@ void launch_api_pdf_emitter(hipStream_t s, const DScene &S, uint32_t n, const ui
 void launch_api_sampler_next(hipStream_t s, uint32_t n, uint64_t *state, const uint64_t *inc, const uint8_t *active, float *out, int dims) {
     hipLaunchKernelGGL(k_api_sampler_next, dim3(blocks_for(n)), dim3(kBlock), 0, s, n, state, inc, active, out, dims);
 }
+/* Emitter::sample_direction of projector `emitter` at n reference points (har_emitter_sample_direction): one lane per point, the function the shading kernels call */
+__global__ void k_api_emitter_sample_direction(DScene S, uint32_t emitter, uint32_t n, const float *ref_p, const uint8_t *active,
+                                               float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec) {
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    projector_sample_direction_lane(S, emitter, n, i, ref_p, !(active && !active[i]), d, dist, pdf, p, nrm, uv, spec);
+}
+void launch_api_emitter_sample_direction(hipStream_t s, const DScene &S, uint32_t emitter, uint32_t n, const float *ref_p, const uint8_t *active,
+                                         float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec) {
+    hipLaunchKernelGGL(k_api_emitter_sample_direction, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, emitter, n, ref_p, active, d, dist, pdf, p, nrm, uv, spec);
+}
 void launch_api_bsdf_eval_pdf_si(hipStream_t s, const DScene &S, uint32_t bsdf, const BsdfCtx &ctx, uint32_t n, const float *wi, const float *uv, const float *wo, const float *geom,
                                  const uint8_t *active, float *value, float *pdf) {
     if (S.bsdf_types & HAR_SCENE_THIN) { hipLaunchKernelGGL(k_api_bsdf_eval_pdf_thin, dim3(blocks_for(n)), dim3(kBlock), 0, s, S, bsdf, ctx, n, wi, uv, wo, geom, active, value, pdf); return; }

@@ -194,6 +194,8 @@ extern "C" {
 int har_multi_create(const HarSceneDesc *desc, int integrator_type, int32_t max_depth, int32_t rr_depth, uint32_t chunk_lanes, const int *devices, uint32_t n_devices,
                      HarMulti *out) {
     if (!desc || !out || !devices || n_devices == 0) return har_set_error("har_multi_create: null argument / no device");
+    for (uint32_t e = 0; e < desc->emitter_count; ++e)
+        if (desc->emitters && desc->emitters[e].type == 8u) return har_set_error("projector: a DeviceGroup (har_multi_create) is not implemented for a scene that holds a `projector` (the replicas' parameter updates and gradient reduction do not carry it)");
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) return har_set_error("hip_ad_rgb requires a HIP device (no CPU fallback)");
     bool distinct = true;

@@ -336,6 +336,15 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
             textured_area_sample_direction(S, S.emitters[index], si.p, ex, ey, ds, em_weight, lt ? &em_unit : nullptr, lt ? lt_uv : nullptr);
             if (lt) lt_sampled = true;
             if (lt && MODE == MODE_PRB_ADJOINT) { R.lt_nee_emitter = (int32_t) index; R.lt_nee_uv[0] = lt_uv[0]; R.lt_nee_uv[1] = lt_uv[1]; }
+        } else if ((TYPES & HAR_SCENE_TEXLIGHT) != 0u && S.emitters[index].type == 8u) {
+            /* a projector (kernels of scenes with a bitmap light or a projector: the host sets HAR_SCENE_TEXLIGHT for both).  As the scene's only emitter its record comes
+             * from the kernel arguments (DScene::emitter0).  Its bitmap's texels take the route of a bitmap light's: the unit weight (without `scale`) and ds.uv */
+            const DEmitter &PE = (S.n_emitters == 1u && S.emitter0_valid == 1u) ? S.emitter0 : S.emitters[index];
+            const bool lt = MODE != MODE_PATH && (P.flags & HAR_SHADE_LIGHT_TEXELS) != 0u && PE.mesh != 0xffffffffu;
+            float lt_uv[2] = { 0.f, 0.f };
+            projector_sample_direction(S, PE, si.p, ds, em_weight, MODE != MODE_PATH ? &em_unit : nullptr, lt ? lt_uv : nullptr); em_delta = true;
+            if (lt) lt_sampled = true;
+            if (lt && MODE == MODE_PRB_ADJOINT && ds.pdf != 0.f) { R.lt_nee_emitter = (int32_t) index; R.lt_nee_uv[0] = lt_uv[0]; R.lt_nee_uv[1] = lt_uv[1]; }
         }
         /* a scene with ONE emitter (the bench scenes): its record travels with the kernel arguments (DScene::emitter0), i.e. in scalar registers, instead of being gathered
          * by every lane -- six vector loads less in a kernel that is bound by the number of its memory transactions (k_shade, docs/rounds/r05.md item 11) */
@@ -374,7 +383,8 @@ HAR_HD void shade_lane(const DScene &S, const ShadeParams &P, const PathState &s
                 R.dLr_drho = ((st.throughput * mis_em) * ev.d_slot0) * em_weight;
                 R.dLr_drho_unit = ((st.throughput * mis_em) * ev.d_slot0) * em_unit;
                 /* em_weight = radiance * em_unit for `area` / `constant` emitters (prb.py:198-206, attached eval_emitter_direction) */
-                R.nee_emitter = ((P.flags & HAR_SHADE_EMITTER_GRADS) && S.emitters[em_sampled].type != 2u && S.emitters[em_sampled].type != 7u) ? (int32_t) em_sampled : -1;
+                R.nee_emitter = ((P.flags & HAR_SHADE_EMITTER_GRADS) && S.emitters[em_sampled].type != 2u && S.emitters[em_sampled].type != 7u &&
+                                 !((TYPES & HAR_SCENE_TEXLIGHT) != 0u && S.emitters[em_sampled].type == 8u && S.emitters[em_sampled].mesh != 0xffffffffu)) ? (int32_t) em_sampled : -1;
                 R.contrib_unit = ((st.throughput * mis_em) * ev.value) * em_unit;
                 if ((TYPES & HAR_SCENE_BLEND) != 0u && composite)
                     for (int k = 0; k < 2; ++k) R.bl_dir[k] = ((st.throughput * mis_em) * cg.d[k]) * em_weight;

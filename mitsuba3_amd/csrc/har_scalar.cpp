@@ -603,6 +603,26 @@ extern "C" int har_bsdf_sample_host(const HarSceneDesc *desc, uint32_t bsdf, con
     catch (const std::exception &ex) { return har_set_error(std::string("har_bsdf_sample_host: ") + ex.what()); }
 }
 
+/* Emitter::sample_direction of a projector on the host: projector_sample_direction_lane (har_scene.h), the function k_api_emitter_sample_direction runs per lane.  The
+ * twin of har_emitter_sample_direction. */
+extern "C" int har_emitter_sample_direction_host(const HarSceneDesc *desc, uint32_t emitter, uint32_t n, const float *ref_p, const float *sample, const uint8_t *active,
+                                                 float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec) {
+    try {
+        if (!desc) return har_set_error("null argument");
+        BoundScene B; std::string e;
+        if (!lower_scene(*desc, B.hs, e)) return har_set_error(e);
+        B.bind();
+        if (emitter >= B.hs.emitters.size()) return har_set_error("invalid emitter index");
+        if (B.hs.emitters[emitter].type != 8u) return har_set_error("har_emitter_sample_direction_host: implemented for a `projector` (emitter type 8); the other emitters are sampled by the renders only");
+        (void) sample;          /* Projector::sample_direction ignores its sample (projector.cpp:203) */
+        if (n == 0) return 0;
+        if (!ref_p || !d || !dist || !pdf || !p || !nrm || !uv || !spec) return har_set_error("null input / output arrays");
+        for (uint32_t i = 0; i < n; ++i) projector_sample_direction_lane(B.ds, emitter, n, i, ref_p, !(active && !active[i]), d, dist, pdf, p, nrm, uv, spec);
+        return 0;
+    } catch (const std::bad_alloc &) { return har_set_error("har_emitter_sample_direction_host: out of memory"); }
+    catch (const std::exception &ex) { return har_set_error(std::string("har_emitter_sample_direction_host: ") + ex.what()); }
+}
+
 /* The looked-up roughness of record `bsdf` at n uv points (uv 2 x n) on the host: bsdf_alpha_lane (har_scene.h), the function k_api_bsdf_alpha runs per lane -- alpha_u,
  * alpha_v after the lookup and before Microfacet's max(., 1e-4); the constants of a record without a roughness map.  The twin of har_bsdf_alpha. */
 extern "C" int har_bsdf_alpha_host(const HarSceneDesc *desc, uint32_t bsdf, uint32_t n, const float *uv, float *alpha_u, float *alpha_v) {

@@ -24,7 +24,8 @@ struct DTexture { const float *data; uint32_t w, h; uint32_t mode, pad; float uv
 /* type 0: AreaLight on a rectangle (to_world, normal, inv_area, mesh); type 1: ConstantBackgroundEmitter
  * (src/emitters/constant.cpp): to_world[0..2] = bounding sphere centre, to_world[3] = radius, mesh = 0xffffffff; type 2: environment map
  * (DEnvmap); type 3: AreaLight on a triangle mesh: mesh, inv_area = 1 / surface area, to_world[0] / [1] = bit patterns of the offset of its
- * table in DScene::emitter_cdf and of its face count, to_world[2] = sum of the face areas */
+ * table in DScene::emitter_cdf and of its face count, to_world[2] = sum of the face areas; types 4 - 6 (point / spot / directional), 7 (bitmap area light) and 8
+ * (projector): at their sample_direction functions below */
 #ifndef HAR_SHADING_TRIS
 /* 1 (default since round 5): compute_si reads ONE pre-gathered 96-byte block per face (its three vertex records, DScene::shade_tris) instead of face -> three scattered
  * vertices: one level of dependent loads less, one or two cache lines instead of three or four.  Bracketed A/B on one box (profiles/r05_ab_shading_tris.txt): k_shade
@@ -1334,6 +1335,52 @@ HAR_HD float textured_area_pdf_direction(const DScene &S, const DEmitter &E, Vec
     float tu = u, tv = v;
     if (T.mode & HAR_TEX_HAS_UV_XF) { tu = fma_(T.uvm[1], v, fma_(T.uvm[0], u, T.uvm[2])); tv = fma_(T.uvm[4], v, fma_(T.uvm[3], u, T.uvm[5])); }
     return bitmap_pdf_texture(T, S.emitter_cdf + as_u32(E.radiance[1]), tu, tv) * (dist * dist) / (E.radiance[2] * -dp);
+}
+
+/* ---- Projector (src/emitters/projector.cpp), emitter type 8: the reciprocal of the perspective camera.  The record (DEmitter keeps its size: DScene::emitter0 passes
+ * one as kernel arguments) holds to_world^-1 in to_world[0..11], `mesh` = the irradiance bitmap's index in DScene::textures (0xffffffff: a constant irradiance),
+ * radiance = the bits of that index in [0] (where light_texel_commit reads it) or, for a constant, irradiance * scale; inv_area = the bits of the offset of its block in
+ * DScene::emitter_cdf, normal = (scale, x_fov in degrees, -) as the host handed them in.  The block, HAR_PROJECTOR_TABLE floats (projector_table_fill in
+ * har_scene_host.cpp): [0..3] the live coefficients m00, m02, m11, m12 of the two uv rows of camera_to_sample (perspective_projection(size, size, 0, x_fov, 1e-4, 1e4),
+ * sensor.h:234-269: u = (m00 x + m02 z) / z, v = (m11 y + m12 z) / z), [4..6] the translation of to_world, [7..9] to_world * (0, 0, 1), [10] scale, [11] x_fov */
+#define HAR_PROJECTOR_TABLE 12u
+/* Projector::sample_direction (projector.cpp:202-244).  `unit` (optional): the weight the sample carries per unit of the irradiance LOOKUP, pi / (z^2 * -dot(n, d)) --
+ * `scale` left out, as for the environment map: spec = lookup * scale * unit for a bitmap, (irradiance * scale) * unit for a constant; `uv_out`: ds.uv.  A lane outside
+ * the frustum never touches the bitmap (its uv may be anything, NaN included). */
+HAR_HD void projector_sample_direction(const DScene &S, const DEmitter &E, Vec3 ref_p, DirSample &ds, Vec3 &spec, float *unit = nullptr, float *uv_out = nullptr) {
+    const float *tab = S.emitter_cdf + as_u32(E.inv_area);
+    const Vec3 it_local = xf_point(E.to_world, ref_p);                                      /* :208 */
+    const float inv_w = rcp_(it_local.z);                                                    /* :211, the homogeneous divide (w = z) */
+    const float u = fma_(tab[0], it_local.x, tab[1] * it_local.z) * inv_w, v = fma_(tab[2], it_local.y, tab[3] * it_local.z) * inv_w;
+    const bool active = u >= 0.f && u <= 1.f && v >= 0.f && v <= 1.f && it_local.z > 0.f;   /* :212 */
+    ds.p = Vec3(tab[4], tab[5], tab[6]); ds.n = Vec3(tab[7], tab[8], tab[9]);                /* :222-223 */
+    if (uv_out) { uv_out[0] = u; uv_out[1] = v; }
+    ds.pdf = active ? 1.f : 0.f;
+    ds.d = ds.p - ref_p;
+    const float dist_squared = dot3(ds.d, ds.d);
+    ds.dist = sqrtf(dist_squared);
+    ds.d = ds.d * rcp_(ds.dist);                                                             /* :229-232 */
+    const float denom = (it_local.z * it_local.z) * -dot3(ds.n, ds.d);                       /* :240-241 */
+    spec = Vec3(0.f);
+    if (active) {
+        if (E.mesh != 0xffffffffu) spec = texture_eval_uv(S.textures[E.mesh], u, v) * (HAR_PI * tab[10] / denom);
+        else spec = Vec3(E.radiance[0], E.radiance[1], E.radiance[2]) * (HAR_PI / denom);    /* (`scale` is in the record's colour) */
+    }
+    if (unit) *unit = active ? HAR_PI / denom : 0.f;
+}
+
+/* One lane of the array-valued Emitter::sample_direction of a projector (k_api_emitter_sample_direction and its host twin, har_emitter_sample_direction_host): rows
+ * d (3), dist, pdf, p (3), n (3), uv (2), spec (3) of n lanes each; a lane whose `active` byte is 0 writes zeros.  The record is the one the renders sample (for a
+ * constant irradiance `scale` is in its colour). */
+HAR_HD void projector_sample_direction_lane(const DScene &S, uint32_t emitter, uint32_t n, uint32_t i, const float *ref_p, bool active,
+                                            float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec) {
+    const size_t i1 = (size_t) n + i, i2 = 2 * (size_t) n + i;
+    DirSample ds; ds.p = Vec3(0.f); ds.n = Vec3(0.f); ds.d = Vec3(0.f); ds.dist = 0.f; ds.pdf = 0.f;
+    Vec3 w(0.f); float q[2] = { 0.f, 0.f };
+    if (active) projector_sample_direction(S, S.emitters[emitter], Vec3(ref_p[i], ref_p[i1], ref_p[i2]), ds, w, nullptr, q);
+    d[i] = ds.d.x; d[i1] = ds.d.y; d[i2] = ds.d.z; dist[i] = ds.dist; pdf[i] = ds.pdf;
+    p[i] = ds.p.x; p[i1] = ds.p.y; p[i2] = ds.p.z; nrm[i] = ds.n.x; nrm[i1] = ds.n.y; nrm[i2] = ds.n.z;
+    uv[i] = q[0]; uv[i1] = q[1]; spec[i] = w.x; spec[i1] = w.y; spec[i2] = w.z;
 }
 
 /* PerspectiveCamera::sample_ray (src/sensors/perspective.cpp:200-237); CAM: DSensor, or DCamera (a child of a batch sensor).  For projection 0 and 1 ONLY: in a

@@ -87,6 +87,7 @@ int har_scene_create(const HarSceneDesc *desc, HarScene *out) {
     for (const DBsdf &b : hs.bsdfs) if (b.type == BSDF_ROUGHCONDUCTOR && (b.flags & BF_ALPHA_TEX)) D.bsdf_types |= HAR_SCENE_ALPHAMAP;      /* a roughness map: the set that also looks the roughness up */
     if (hs.has_envmap || hs.has_mesh_emitters || hs.has_point_emitters || !hs.emitter_distr.empty()) D.bsdf_types |= HAR_SCENE_ENVMAP;
     for (const DEmitter &e : hs.emitters) if (e.type == 7u) D.bsdf_types |= HAR_SCENE_TEXLIGHT;      /* (has_mesh_emitters is set with it: the generic emitter kernels + the texel-distribution code) */
+    if (hs.has_projector) D.bsdf_types |= HAR_SCENE_TEXLIGHT | HAR_SCENE_PROJECTOR;      /* a projector: the same set (har_bsdf.h) */
     for (const HostTexture &t : hs.textures) if (t.mode & HAR_TEX_ATTRIBUTE) D.bsdf_types |= HAR_SCENE_ATTR;      /* a `mesh_attribute` texture: the widest set that also looks attributes up */
     /* the depth-first bound of the BVH must fit the traversal stacks (LDS entries + HBM spill columns): a deeper scene is refused here instead of
      * rendering with rays that overflow (an overflowing ray is a miss + a status word that only har_render_stats reads) */
@@ -137,6 +138,10 @@ int har_scene_set_delta_emitter(HarScene S, uint32_t emitter, const HarEmitter *
     if (refresh_host_geometry(S, nullptr)) return 1;            /* a directional light's record follows the scene's bounding sphere: the host's vertices / transforms must be current */
     std::string e;
     if (!scene_set_delta_emitter_host(S->hs, emitter, *record, e)) return fail(e);
+    if (S->hs.emitters[emitter].type == 8u) {          /* a projector: its block of the side table was re-derived with the record */
+        const uint32_t off = as_u32(S->hs.emitters[emitter].inv_area);
+        HIP_TRY(hipMemcpy(const_cast<float *>(S->ds.emitter_cdf) + off, S->hs.emitter_cdf.data() + off, HAR_PROJECTOR_TABLE * sizeof(float), hipMemcpyHostToDevice));
+    }
     HIP_TRY(hipMemcpy(const_cast<DEmitter *>(S->ds.emitters), S->hs.emitters.data(), S->hs.emitters.size() * sizeof(DEmitter), hipMemcpyHostToDevice));
     if (S->hs.emitters.size() == 1) { S->ds.emitter0 = S->hs.emitters[0]; S->ds.emitter0_valid = 1u; }
     return 0;
@@ -158,6 +163,8 @@ int har_scene_set_emitter_radiance(HarScene S, uint32_t emitter, const float rgb
     DEmitter &e = S->hs.emitters[emitter];
     if (e.type == 2u) return fail("an environment map has no constant radiance");
     if (e.type == 7u) return fail("this area light radiates a bitmap: update the texture (har_scene_set_texture)");
+    if (e.type == 8u) return fail(e.mesh != 0xffffffffu ? "projector: this projector's irradiance is a bitmap: update the texture (har_scene_set_texture)"
+                                                       : "projector: the record's colour is irradiance * scale: replace the record (har_scene_set_delta_emitter), which takes both");
     e.radiance[0] = rgb[0]; e.radiance[1] = rgb[1]; e.radiance[2] = rgb[2];
     HIP_TRY(hipMemcpy(const_cast<DEmitter *>(S->ds.emitters) + emitter, &e, sizeof(DEmitter), hipMemcpyHostToDevice));
     if (S->hs.emitters.size() == 1) { S->ds.emitter0 = e; S->ds.emitter0_valid = 1u; }
@@ -254,6 +261,8 @@ int har_scene_set_emitter_radiance_device(HarScene S, uint32_t emitter, const fl
     if (!dev_rgb) return fail("null device pointer");
     if (S->hs.emitters[emitter].type == 2u) return fail("an environment map has no constant radiance");
     if (S->hs.emitters[emitter].type == 7u) return fail("this area light radiates a bitmap: update the texture (har_scene_set_texture_device)");
+    if (S->hs.emitters[emitter].type == 8u) return fail(S->hs.emitters[emitter].mesh != 0xffffffffu ? "projector: this projector's irradiance is a bitmap: update the texture (har_scene_set_texture_device)"
+                                                                                                    : "projector: the record's colour is irradiance * scale: replace the record (har_scene_set_delta_emitter), which takes both");
     HIP_TRY(hipMemcpyAsync(const_cast<float *>(S->ds.emitters[0].radiance) + (size_t) emitter * (sizeof(DEmitter) / sizeof(float)), dev_rgb, 3 * sizeof(float),
                            hipMemcpyDeviceToDevice, (hipStream_t) stream));
     S->emitter_host_stale = true; S->last_push_stream = (hipStream_t) stream; S->last_push_valid = true;
@@ -802,6 +811,17 @@ int har_bsdf_sample(HarScene S, uint32_t bsdf, const HarBSDFContext *ctx, uint32
     if (n == 0) return 0;
     if (!wi || !uv || !sample2 || !wo || !pdf || !weight) return fail("null input / output arrays");
     launch_api_bsdf_sample((hipStream_t) stream, S->ds, bsdf, c, n, wi, uv, sample1, sample2, active, wo, pdf, weight, eta, sampled_type, sampled_component);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+int har_emitter_sample_direction(HarScene S, uint32_t emitter, uint32_t n, const float *ref_p, const float *sample, const uint8_t *active,
+                                 float *d, float *dist, float *pdf, float *p, float *nrm, float *uv, float *spec, void *stream) {
+    if (!S || emitter >= S->hs.emitters.size()) return fail("invalid emitter index");
+    if (S->hs.emitters[emitter].type != 8u) return fail("har_emitter_sample_direction: implemented for a `projector` (emitter type 8); the other emitters are sampled by the renders only");
+    (void) sample;          /* Projector::sample_direction ignores its sample (projector.cpp:203) */
+    if (n == 0) return 0;
+    if (!ref_p || !d || !dist || !pdf || !p || !nrm || !uv || !spec) return fail("null input / output arrays");
+    launch_api_emitter_sample_direction((hipStream_t) stream, S->ds, emitter, n, ref_p, active, d, dist, pdf, p, nrm, uv, spec);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -165,6 +165,43 @@ void build_roughplastic_tables(HostScene &hs, uint32_t index) {
 
 } // namespace
 
+/* Projector (src/emitters/projector.cpp:123-164), emitter type 8: the record and its HAR_PROJECTOR_TABLE block of hs.emitter_cdf at `off` (layout: har_scene.h) from the
+ * description -- to_world / to_local, normal[0] = `scale`, normal[1] = x_fov in degrees (parse_fov at the irradiance texture's aspect), radiance = a constant irradiance,
+ * radiance_texture = the bitmap (0xffffffff: none).  camera_to_sample = perspective_projection(size, size, 0, x_fov, 1e-4, 1e4) (sensor.h:234-269) with size = the
+ * texture's resolution (1 x 1 for a constant): scale(-1/2, -aspect/2, 1) * translate(-1, -1/aspect, 0) * perspective(x_fov), whose two uv rows are
+ * (-cot/2, 0, 1/2, 0) and (0, -aspect cot/2, (-aspect/2)(-1/aspect), 0) in the float arithmetic of Transform::perspective (transform.h:420-437) and the matrix product. */
+static bool lower_projector(HostScene &hs, const HarEmitter &e, DEmitter &de, uint32_t off, std::string &err) {
+    const float scale = e.normal[0], x_fov = e.normal[1];
+    if (!std::isfinite(scale)) { err = "projector: `scale` is not finite"; return false; }
+    if (!(x_fov > 0.f && x_fov < 180.f)) { err = "projector: the field of view must lie in (0, 180) degrees"; return false; }
+    for (int k = 0; k < 12; ++k) if (!std::isfinite(e.to_world[k]) || !std::isfinite(e.to_local[k])) { err = "projector: to_world is singular or not finite"; return false; }
+    const float *m = e.to_world;          /* column-major 3 x 4 */
+    const float det = m[0] * (m[4] * m[8] - m[5] * m[7]) - m[3] * (m[1] * m[8] - m[2] * m[7]) + m[6] * (m[1] * m[5] - m[2] * m[4]);
+    if (!(std::fabs(det) > 0.f) || !std::isfinite(det)) { err = "projector: to_world is singular or not finite"; return false; }
+    uint32_t w = 1, h = 1;
+    if (e.radiance_texture != 0xffffffffu) {
+        if (e.radiance_texture >= hs.textures.size()) { err = "projector: `irradiance` references a bitmap that does not exist"; return false; }
+        const HostTexture &t = hs.textures[e.radiance_texture];
+        if (t.mode & HAR_TEX_MESH_ATTRIBUTE) { err = "projector: a `mesh_attribute` as `irradiance` is not implemented (an emitter cannot read a mesh attribute)"; return false; }
+        w = t.w; h = t.h;
+    }
+    de.type = 8u; de.mesh = e.radiance_texture;
+    std::memcpy(de.to_world, e.to_local, 48);
+    de.normal[0] = scale; de.normal[1] = x_fov; de.normal[2] = 0.f;
+    std::memcpy(&de.inv_area, &off, 4);
+    if (e.radiance_texture != 0xffffffffu) { const uint32_t tex = e.radiance_texture; std::memcpy(&de.radiance[0], &tex, 4); de.radiance[1] = 0.f; de.radiance[2] = 0.f; }
+    else for (int k = 0; k < 3; ++k) de.radiance[k] = e.radiance[k] * scale;
+    const float aspect = (float) (int) w / (float) (int) h;
+    const float tan_ = (float) std::tan((double) (x_fov * .5f * (HAR_PI / 180.f))), cot = 1.f / tan_;
+    float *tab = hs.emitter_cdf.data() + off;
+    tab[0] = -0.5f * cot; tab[1] = -0.5f * -1.f;
+    tab[2] = (-0.5f * aspect) * cot; tab[3] = (-0.5f * aspect) * (-1.f / aspect);
+    tab[4] = m[9]; tab[5] = m[10]; tab[6] = m[11];
+    tab[7] = m[6]; tab[8] = m[7]; tab[9] = m[8];          /* to_world * (0, 0, 1): the third column, not normalised (projector.cpp:223) */
+    tab[10] = scale; tab[11] = x_fov;
+    return true;
+}
+
 /* the part of an emitter's record that depends on nothing but its own description: every field of the area / constant / point records, SpotLight::update, the direction of
  * a directional light (lower_scene adds what hangs on the scene: texel tables, face tables, the bounding sphere) */
 bool lower_plain_emitter(const HarEmitter &e, DEmitter &de, std::string &err) {
@@ -188,7 +225,14 @@ bool lower_plain_emitter(const HarEmitter &e, DEmitter &de, std::string &err) {
  * `position` / `to_world` / cone update; the sampling weight stays the distribution's business (har_scene_set_emitter_sampling_weights) */
 bool scene_set_delta_emitter_host(HostScene &hs, uint32_t index, const HarEmitter &e, std::string &err) {
     if (index >= hs.emitters.size()) { err = "invalid emitter index"; return false; }
-    if (e.type < 4 || e.type > 6 || hs.emitters[index].type != e.type) { err = "only the record of a point / spot / directional emitter can be replaced in place, by one of the same type"; return false; }
+    if (e.type == 8 && hs.emitters[index].type == 8u) {      /* Projector::parameters_changed: `to_world`, `scale`, the field of view; the irradiance stays the texture it was (its texels: har_scene_set_texture) */
+        DEmitter de = hs.emitters[index];
+        if (e.radiance_texture != de.mesh) { err = "projector: the irradiance of a projector cannot change between a bitmap and a constant, or to another bitmap, in place"; return false; }
+        if (!lower_projector(hs, e, de, as_u32(de.inv_area), err)) return false;
+        hs.emitters[index] = de;
+        return true;
+    }
+    if (e.type < 4 || e.type > 6 || hs.emitters[index].type != e.type) { err = "only the record of a point / spot / directional / projector emitter can be replaced in place, by one of the same type"; return false; }
     for (int k = 0; k < 12; ++k) if (!std::isfinite(e.to_world[k]) || !std::isfinite(e.to_local[k])) { err = "emitter transform is not finite"; return false; }
     DEmitter de = hs.emitters[index];
     if (!lower_plain_emitter(e, de, err)) return false;
@@ -536,7 +580,7 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             }
             for (uint32_t i = 0; i < d.emitter_count; ++i) {
                 const HarEmitter &e = d.emitters[i];
-                const uint32_t t = e.type == 2u ? e.mesh : e.type == 7u ? e.radiance_texture : 0xffffffffu;
+                const uint32_t t = e.type == 2u ? e.mesh : e.type == 7u ? e.radiance_texture : 0xffffffffu;      /* (a projector's `irradiance` is refused by name: lower_projector) */
                 if (t < hs.textures.size() && (hs.textures[t].mode & HAR_TEX_MESH_ATTRIBUTE)) { err = "mesh_attribute: an emitter cannot read a mesh attribute (area `radiance`, envmap)"; return false; }
             }
         }
@@ -550,9 +594,9 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
     }
     for (uint32_t i = 0; i < d.emitter_count; ++i) {
         const HarEmitter &e = d.emitters[i];
-        if (e.type > 7) { err = "unsupported emitter type (`area`, `constant`, `envmap`, `point`, `spot` and `directional` are implemented)"; return false; }
+        if (e.type > 8) { err = "unsupported emitter type (`area`, `constant`, `envmap`, `point`, `spot`, `directional` and `projector` are implemented)"; return false; }
         if (!(e.sampling_weight >= 0.f) || !std::isfinite(e.sampling_weight)) { err = "DiscreteDistribution: entries must be non-negative!"; return false; }      /* distr_1d.h:247-248 */
-        const bool area = e.type == 0 || e.type == 3 || e.type == 7, point = e.type >= 4 && e.type <= 6;      /* the delta emitters */
+        const bool area = e.type == 0 || e.type == 3 || e.type == 7, point = (e.type >= 4 && e.type <= 6) || e.type == 8;      /* the delta emitters */
         if (area && e.mesh >= d.top_mesh_count) { err = "area emitter must be attached to a top-level mesh"; return false; }
         if (!area && !point && hs.env_emitter >= 0) { err = "Only one environment emitter can be specified per scene."; return false; }   /* scene.cpp:64-65 */
         if (!area && !point) hs.env_emitter = (int32_t) i;
@@ -562,7 +606,12 @@ bool lower_scene(const HarSceneDesc &d, HostScene &hs, std::string &err) {
             if (!build_envmap(hs, d.textures[e.mesh], e, err)) return false;
         }
         DEmitter de{};
-        if (!lower_plain_emitter(e, de, err)) return false;
+        if (e.type == 8) {            /* Projector: the record and its block of emitter_cdf (lower_projector) */
+            const uint32_t off = (uint32_t) hs.emitter_cdf.size();
+            hs.emitter_cdf.resize(off + HAR_PROJECTOR_TABLE);
+            if (!lower_projector(hs, e, de, off, err)) return false;
+            hs.has_projector = true;
+        } else if (!lower_plain_emitter(e, de, err)) return false;
         if (e.type == 7) {            /* AreaLight with a bitmap radiance: the texel distribution (see texel_table_fill) lives in emitter_cdf, the record holds where */
             if (e.radiance_texture >= d.texture_count) { err = "area emitter references a bitmap that does not exist"; return false; }
             const HostTexture &t = hs.textures[e.radiance_texture];

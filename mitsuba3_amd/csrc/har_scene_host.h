@@ -39,6 +39,7 @@ struct HostScene {
     std::vector<float> env_tex, env_warp; DEnvmap envmap{}; bool has_envmap = false;
     std::vector<float> emitter_cdf; bool has_mesh_emitters = false;      /* face-area tables of the mesh area lights (emitter type 3) */
     bool has_point_emitters = false;                                     /* emitter type 4 (delta position): shaded by the kernels with the generic emitter code */
+    bool has_projector = false;                                          /* emitter type 8: the scene runs the kernel set of bitmap lights (HAR_SCENE_TEXLIGHT), which carries its branch */
     /* Scene::m_emitter_distr (scene.cpp:120-141): empty when every sampling_weight is 1; else pmf[n] then cdf[n] (DScene::emitter_distr) */
     std::vector<float> emitter_distr; float emitter_sum = 0.f, emitter_norm = 0.f; uint32_t emitter_valid_lo = 0, emitter_valid_hi = 0;
     /* fills the texture / emitter-distribution fields of a DScene whose array pointers the caller has set (device or host copies) */
